@@ -8,7 +8,11 @@
 One "step" = one pass of the hot path (encode + decode) over one batch that is already resident in HBM.
 Multi-GPU: utterances are independent, so each rank owns its own batch (weak scaling); the only collective is the
 one-off RCCL broadcast of the weights from rank 0 (`python bench.py --gpus N` spawns the N ranks itself when it was not
-started by torchrun).  Rank 0 prints ONE JSON line with the contract fields plus
+started by torchrun).  Rank 0 prints ONE JSON line with the contract fields (`metric`, `value`, `unit`, `ms_per_step` = the
+mean of exactly --steps timed steps after --warmup untimed ones, ...).  That is all a plain run does.
+`--dump-outputs DIR` writes what the last timed step computed (codec: `codes`, `wav`; lm / gpt: the frame's tokens; e2e: the
+generated pcm) as DIR/<name>.npy in float32; the inputs are seeded, so two builds given the same arguments can be compared.
+`--full` adds everything else the line used to carry:
   * `roofline` (dominant kernel: the fp32-MFMA windowed GEMM, timed per launch with HIP events on the launch stream in an
     extra instrumented step) and `cpu_baseline` (the CPU oracle timed on this host on a bounded sample),
   * `timing`: median / p95 of >= 50 individually synchronised steps, next to the contract's K-step mean,
@@ -16,7 +20,9 @@ started by torchrun).  Rank 0 prints ONE JSON line with the contract fields plus
     "RVQ code-index exact-match" half of the metric), and
   * on the single-GPU run the sub-objects `lm_b1` (BASELINE configs[2]: Moshi-7B-shaped LMGen.step, batch 1) and `e2e_b1`
     (the north-star target: Mimi encode -> LMGen.step -> Mimi decode per 80 ms frame, batch 1), each with its own
-    `ms_per_step`, `timing`, `roofline` and `cpu_baseline` (skip with --no-sub).
+    `ms_per_step`, `timing`, `roofline` and `cpu_baseline` (skip with --no-sub); the multi-GPU line carries `e2e_b32` instead.
+The other workloads (--workload lm / e2e / gpt) likewise time their steps only, and add `timing`, `roofline` and `cpu_baseline`
+under --full.
 """
 import argparse
 import json
@@ -71,6 +77,11 @@ def parse():
     ap.add_argument("--no-sub", action="store_true", help="codec: skip the lm_b1 / e2e_b1 sub-benchmarks of the single-GPU line")
     ap.add_argument("--sub-steps", type=int, default=60, help="timed frames of the lm_b1 / e2e_b1 sub-benchmarks (>= 50: median + p95)")
     ap.add_argument("--timing-samples", type=int, default=50, help="individually synchronised steps behind `timing` (median, p95)")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beyond the headline figure: `roofline` (extra "
+                    "instrumented step), `timing` samples, the parity sample, the CPU baselines and, on the codec line, the sub-benchmarks "
+                    "of the other configurations.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "as DIR/<name>.npy (float32; at most 64 MB in all, beyond that a fixed seeded sample of every array)")
     args = ap.parse_args()
     if args.lm_batch is None:
         args.lm_batch = 32 if args.workload == "gpt" else 1
@@ -297,6 +308,26 @@ def _quiesce_host():
     torch.cuda.synchronize()
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every tensor of `arrays` as out_dir/<name>.npy in float32 (code and token ids are < 2^24: exact).  A set larger
+    than DUMP_BUDGET_BYTES keeps the same seeded sample of flat positions of each array on every run, so that two builds given the same
+    arguments can be compared element for element.  `None` entries (no output yet in a streaming step) are skipped."""
+    import numpy as np
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    keep = min(1.0, DUMP_BUDGET_BYTES / max(1, sum(4 * v.numel() for v in arrays.values())))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        x = v.detach().cpu().float()
+        if keep < 1.0:
+            x = x.reshape(-1)
+            idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(0))[:int(x.numel() * keep)].sort().values
+            x = x[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), x.numpy())
+
+
 def _timed_loop(step, warmup, steps, world, dev):
     """The contract's timing: `warmup` untimed steps, then EXACTLY `steps` steps between barrier + synchronize on both sides,
     MAX over ranks.  `step(i)` runs step number i (0-based over warm-up + timed)."""
@@ -427,9 +458,9 @@ def build_lm(args, rank, world, dev, stats_key="broadcast"):
     return cfg, LMModel.from_state_dict(sd, cfg, kv_dtype=torch.bfloat16 if args.kv_dtype == "bf16" else torch.float32), n_params
 
 
-def run_lm(args, rank, world, dev, lm=None, steps=None, warmup=None, cpu=True):
+def run_lm(args, rank, world, dev, lm=None, steps=None, warmup=None, cpu=True, dump=None):
     """BASELINE configs[2]: one step = one 80 ms frame of LMGen.step (temporal step + 8 depth steps + sampling).  Returns the
-    result dict on rank 0 (None elsewhere)."""
+    result dict on rank 0 (None elsewhere).  `dump`: directory for the last timed frame's tokens (--dump-outputs)."""
     from rstnet_amd import ops
     from rstnet_amd.lm.model import LMGen
     cfg, model, n_params = lm if lm is not None else build_lm(args, rank, world, dev)
@@ -446,13 +477,36 @@ def run_lm(args, rank, world, dev, lm=None, steps=None, warmup=None, cpu=True):
             st = model.transformer._streaming_state
             st.pos.fill_(args.lm_context)
             st.offset_cpu = args.lm_context
-        elapsed = _timed_loop(lambda i: gen.step(user[i]), warmup, steps, world, dev)
-        samples = _sample_steps(lambda i: gen.step(user[warmup + steps + i]), n_samples)
+        last = {}
+
+        def step(i):
+            last["tokens"] = gen.step(user[i])
+        elapsed = _timed_loop(step, warmup, steps, world, dev)
+        if dump and rank == 0:
+            dump_outputs(dump, last)
+        samples = _sample_steps(lambda i: gen.step(user[warmup + steps + i]), n_samples) if args.full else None
         # which form the timed frames' temporal stack took (ops.TEMPORAL_FRAME = "auto": the persistent launch from 2048 ring steps on)
         temporal_path = ("one persistent launch (rst_temporal_decode_frame)" if getattr(model.transformer._streaming_state, "tables", None) is not None
                          else "five launches per layer")
     if rank != 0:
         return None
+    ms_frame = elapsed / steps * 1e3
+    result = {
+        "metric": METRIC,
+        "value": round(B * world * steps / elapsed, 2), "unit": "frames/s", "n_gpus": world, "steps": steps,
+        "warmup": warmup, "ms_per_step": round(ms_frame, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "bf16 weights, f32 activations", "data": "synthetic",
+        "config": {"workload": f"LMGen.step (temporal + 8-step depth transformer + sampling), BASELINE.json configs[2], {args.lm_config}",
+                   "batch_per_gpu": B, "params": n_params, "context_frames": args.lm_context + warmup + steps,
+                   "kv_dtype": str(model.kv_dtype).replace("torch.", "") if hasattr(model, "kv_dtype") else "float32",
+                   "sampling": "greedy" if args.greedy else "temp 0.8/0.7 top-k 250/25", "hip_graphs": True,
+                   "temporal_stack": temporal_path, "parallelism": f"replica x{world}"},
+        "x_realtime_per_stream": round(steps / elapsed / 12.5, 2),
+    }
+    if _dist(world):
+        result["multi_gpu"] = _multi_gpu_block(world)
+    if not args.full:
+        return result
     # roofline of the dominant kernel (weight-streaming GEMV): one extra frame, eager (no graph), HIP events per launch
     os.environ["NO_CUDA_GRAPH"] = "1"
     gen2 = LMGen(model, use_sampling=not args.greedy)
@@ -478,7 +532,6 @@ def run_lm(args, rank, world, dev, lm=None, steps=None, warmup=None, cpu=True):
             d[0] += 1; d[1] += e0.elapsed_time(e1); d[2] += nb
         for shp, (n, t, nb) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
             print(f"  gemv B,N,K={shp}: {n:4d} launches {t:8.3f} ms  {nb / t / 1e6:8.1f} GB/s", file=sys.stderr)
-    ms_frame = elapsed / steps * 1e3
     timing = _timing(samples)
     frame_bytes = nbytes + depth_bytes
     kern = "gemv_" if B <= 2 else "gemm_skinny"       # packed and fp32-input (x32) forms of the bf16 skinny GEMM
@@ -486,17 +539,7 @@ def run_lm(args, rank, world, dev, lm=None, steps=None, warmup=None, cpu=True):
     tag = "lm" if B <= 2 else f"lm{B}"
     if args.lm_context:
         tag += f"_ctx{args.lm_context}"
-    result = {
-        "metric": METRIC,
-        "value": round(B * world * steps / elapsed, 2), "unit": "frames/s", "n_gpus": world, "steps": steps,
-        "warmup": warmup, "ms_per_step": round(ms_frame, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "bf16 weights, f32 activations", "data": "synthetic",
-        "config": {"workload": f"LMGen.step (temporal + 8-step depth transformer + sampling), BASELINE.json configs[2], {args.lm_config}",
-                   "batch_per_gpu": B, "params": n_params, "context_frames": args.lm_context + warmup + steps,
-                   "kv_dtype": str(model.kv_dtype).replace("torch.", "") if hasattr(model, "kv_dtype") else "float32",
-                   "sampling": "greedy" if args.greedy else "temp 0.8/0.7 top-k 250/25", "hip_graphs": True,
-                   "temporal_stack": temporal_path, "parallelism": f"replica x{world}"},
-        "x_realtime_per_stream": round(steps / elapsed / 12.5, 2),
+    result.update({
         "timing": timing,
         "roofline": {"bound": "hbm", "kernel": ("gemv_kernel / gemv_norm_kernel / gemv_ksplit_kernel" if B <= 2 else "gemm_skinny_kernel / gemm_skinny_x32_kernel") + " (bf16 weight streaming)",
                      "achieved": round(nbytes / ms / 1e6, 1),
@@ -513,14 +556,12 @@ def run_lm(args, rank, world, dev, lm=None, steps=None, warmup=None, cpu=True):
                                       "achieved": round(depth_bytes / depth_ms / 1e6, 1), "frac": round(depth_bytes / depth_ms / 1e6 / HBM_PEAK_GBS, 4),
                                       "bound": "in-launch hand-off latency (~250 dependent all-to-all edges), not bandwidth"}
                                      if depth else None)},
-    }
+    })
     _with_rocprof(result["roofline"], kern, tag, nbytes / max(1, len(gemv)), HBM_PEAK_GBS)
     if result["roofline"]["rocprof"] is None and B <= 2 and args.lm_context:
         # (same kernels, same bytes: only the attention launches differ at a full ring -- the batch-1 trace stands in, and says so)
         _with_rocprof(result["roofline"], kern, "lm", nbytes / max(1, len(gemv)), HBM_PEAK_GBS)
     _settle_roofline(result["roofline"], ms_frame)
-    if _dist(world):
-        result["multi_gpu"] = _multi_gpu_block(world)
     if cpu and not args.no_cpu_baseline and not _dist(world):    # the CPU leg is timed on rank 0 of the single-GPU run only
         result["cpu_baseline"] = lm_cpu_baseline()
     return result
@@ -563,10 +604,10 @@ def build_gpt(args, dev):
     return cfg_d, model, sum(v.numel() for v in model.state_dict().values())
 
 
-def run_gpt(args, rank, world, dev, gpt=None, fp8=None, steps=None, warmup=None, cpu=True):
+def run_gpt(args, rank, world, dev, gpt=None, fp8=None, steps=None, warmup=None, cpu=True, dump=None):
     """BASELINE configs[4]: Qwen-0.5B-shaped litgpt backbone (LoRA adapters merged at load) + codecformer, B streams; one step =
     one frame: text sample + dep_q depth steps with sampling (one graph) + the global T = 1 step of the completed frame (one
-    graph).  Returns the result dict on rank 0 (None elsewhere)."""
+    graph).  Returns the result dict on rank 0 (None elsewhere).  `dump`: directory for the last timed frame's tokens (--dump-outputs)."""
     from rstnet_amd import ops
     from rstnet_amd.lm.generate import GPTGen
     cfg_d, model, n_params = gpt if gpt is not None else build_gpt(args, dev)
@@ -588,9 +629,10 @@ def run_gpt(args, rank, world, dev, gpt=None, fp8=None, steps=None, warmup=None,
     # first frame after the prompt, then every step = ONE graph replay: global step of the completed frame + text sample + dep_q
     # depth steps with their samples, on the session's device-resident token column (GPTGen.step)
     gen.start(h, logits)
+    last = {}
 
     def frame(h, logits):
-        gen.step()
+        last["text"], last["audio"] = gen.step()
         return h, logits
     for _ in range(warmup):
         h, logits = frame(h, logits)
@@ -608,8 +650,10 @@ def run_gpt(args, rank, world, dev, gpt=None, fp8=None, steps=None, warmup=None,
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if dump and rank == 0:
+        dump_outputs(dump, last)
     samples = []
-    for _ in range(max(args.timing_samples, 1) if not _dist(world) else 0):      # median / p95 of individually synchronised frames
+    for _ in range(max(args.timing_samples, 1) if args.full and not _dist(world) else 0):      # median / p95 of individually synchronised frames
         torch.cuda.synchronize()
         ts = time.perf_counter()
         h, logits = frame(h, logits)
@@ -622,6 +666,23 @@ def run_gpt(args, rank, world, dev, gpt=None, fp8=None, steps=None, warmup=None,
         elapsed = float(t.item())
     if rank != 0:
         return None
+    ms_frame = elapsed / steps * 1e3
+    result = {
+        "metric": METRIC,
+        "value": round(B * world * steps / elapsed, 2), "unit": "frames/s", "n_gpus": world, "steps": steps,
+        "warmup": warmup, "ms_per_step": round(ms_frame, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": ("fp8 e4m3 block GEMMs, " if fp8 else "") + "bf16 weights, f32 activations (bf16 hi+lo split on the matrix cores)",
+        "data": "synthetic",
+        "config": {"workload": "GPT (Qwen-1.5-0.5B-shaped litgpt backbone, LoRA r=32 merged) + codecformer: streamed frame = global "
+                               "step + text sample + 8 depth steps with sampling, BASELINE.json configs[4]",
+                   "batch_per_gpu": B, "params": n_params, "sampling": "greedy" if args.greedy else "temp 0.8/0.7 top-k 250/25",
+                   "hip_graphs": True,
+                   "gemm_precision": "fp8 e4m3 (per-row scales) in the global blocks, bf16 hi+lo elsewhere" if fp8 else "bf16 hi+lo",
+                   "parallelism": f"replica x{world}"},
+        "x_realtime_per_stream": round(steps / elapsed / 12.5, 2),
+    }
+    if not args.full:
+        return result
     # roofline of the weight-streaming GEMMs: one extra eager frame with HIP events per launch
     gen2 = GPTGen(model, use_sampling=not args.greedy, n_audio_codes=n_codes, noise=None)
     os.environ["NO_CUDA_GRAPH"] = "1"
@@ -646,7 +707,6 @@ def run_gpt(args, rank, world, dev, gpt=None, fp8=None, steps=None, warmup=None,
             d[0] += 1; d[1] += e0.elapsed_time(e1); d[2] += nb
         for shp, (n, t, nb) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
             print(f"  gemm B,N,K={shp}: {n:4d} launches {t:8.3f} ms  {nb / t / 1e6:8.1f} GB/s", file=sys.stderr)
-    ms_frame = elapsed / steps * 1e3
     # every weight byte a frame streams once: global blocks + LM head (bf16, or e4m3 + scales for the fp8 blocks), the stacked
     # codecformer_in, dep_q x (depth layers + head)
     c = cfg_d
@@ -656,31 +716,17 @@ def run_gpt(args, rank, world, dev, gpt=None, fp8=None, steps=None, warmup=None,
         else (2 * c["codecformer_dim_feedforward"]) // 3
     dep = c["dep_q"] * (c["codecformer_layers"] * (4 * dE * dE + 3 * dH * dE) + c["audio_card"] * dE + dE * c["n_embd"])
     frame_bytes = blk * (1 if fp8 else 2) + 2 * (c["padded_vocab_size"] * c["n_embd"] + dep)
-    result = {
-        "metric": METRIC,
-        "value": round(B * world * steps / elapsed, 2), "unit": "frames/s", "n_gpus": world, "steps": steps,
-        "warmup": warmup, "ms_per_step": round(ms_frame, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": ("fp8 e4m3 block GEMMs, " if fp8 else "") + "bf16 weights, f32 activations (bf16 hi+lo split on the matrix cores)",
-        "data": "synthetic",
-        "config": {"workload": "GPT (Qwen-1.5-0.5B-shaped litgpt backbone, LoRA r=32 merged) + codecformer: streamed frame = global "
-                               "step + text sample + 8 depth steps with sampling, BASELINE.json configs[4]",
-                   "batch_per_gpu": B, "params": n_params, "sampling": "greedy" if args.greedy else "temp 0.8/0.7 top-k 250/25",
-                   "hip_graphs": True,
-                   "gemm_precision": "fp8 e4m3 (per-row scales) in the global blocks, bf16 hi+lo elsewhere" if fp8 else "bf16 hi+lo",
-                   "parallelism": f"replica x{world}"},
-        "x_realtime_per_stream": round(steps / elapsed / 12.5, 2),
-        "roofline": {"bound": "hbm", "kernel": ("gemv_kernel / gemv_norm_kernel / gemv_ksplit_kernel" if B <= 2 else "gemm_skinny_kernel / gemm_skinny_x32_kernel"
-                                                + (" / gemm_skinny_fp8_kernel" if fp8 else "")) + " (weight streaming)",
-                     "achieved": round(nbytes / ms / 1e6, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(nbytes / ms / 1e6 / HBM_PEAK_GBS, 4),
-                     "traffic": pmc_traffic("gemv_" if B <= 2 else "gemm_skinny", "gpt"),
-                     "algorithmic_bytes_per_launch": round(nbytes / max(1, len(gemm))), "launches_per_step": len(gemm),
-                     "avg_launch_ms": round(ms / max(1, len(gemm)), 5), "kernel_ms_per_step": round(ms, 3),
-                     "algorithmic_gb_per_step": round(nbytes / 1e9, 3), "share_of_step_eager": round(ms / ms_frame, 3),
-                     # the whole frame against the HBM roofline: every weight byte of the frame once / the frame time
-                     "frame": {"algorithmic_gb": round(frame_bytes / 1e9, 3), "achieved": round(frame_bytes / ms_frame / 1e6, 1),
-                               "frac": round(frame_bytes / ms_frame / 1e6 / HBM_PEAK_GBS, 4)}},
-    }
+    result["roofline"] = {"bound": "hbm", "kernel": ("gemv_kernel / gemv_norm_kernel / gemv_ksplit_kernel" if B <= 2 else "gemm_skinny_kernel / gemm_skinny_x32_kernel"
+                                                     + (" / gemm_skinny_fp8_kernel" if fp8 else "")) + " (weight streaming)",
+                          "achieved": round(nbytes / ms / 1e6, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": round(nbytes / ms / 1e6 / HBM_PEAK_GBS, 4),
+                          "traffic": pmc_traffic("gemv_" if B <= 2 else "gemm_skinny", "gpt"),
+                          "algorithmic_bytes_per_launch": round(nbytes / max(1, len(gemm))), "launches_per_step": len(gemm),
+                          "avg_launch_ms": round(ms / max(1, len(gemm)), 5), "kernel_ms_per_step": round(ms, 3),
+                          "algorithmic_gb_per_step": round(nbytes / 1e9, 3), "share_of_step_eager": round(ms / ms_frame, 3),
+                          # the whole frame against the HBM roofline: every weight byte of the frame once / the frame time
+                          "frame": {"algorithmic_gb": round(frame_bytes / 1e9, 3), "achieved": round(frame_bytes / ms_frame / 1e6, 1),
+                                    "frac": round(frame_bytes / ms_frame / 1e6 / HBM_PEAK_GBS, 4)}}
     if samples:
         result["timing"] = _timing(samples)
     tag = ("gpt_fp8" if fp8 else "gpt") if B > 2 else f"gpt{B}"
@@ -692,9 +738,10 @@ def run_gpt(args, rank, world, dev, gpt=None, fp8=None, steps=None, warmup=None,
     return result
 
 
-def run_e2e(args, rank, world, dev, lm=None, steps=None, warmup=None, lm_result=None, stats_key="broadcast"):
+def run_e2e(args, rank, world, dev, lm=None, steps=None, warmup=None, lm_result=None, stats_key="broadcast", dump=None):
     """BASELINE configs[3] shape on one GPU: B concurrent streams, each frame = Mimi encode (1920 samples) -> LMGen.step ->
-    Mimi decode; value = B * frames / time.  Returns the result dict on rank 0."""
+    Mimi decode; value = B * frames / time.  Returns the result dict on rank 0.  `dump`: directory for the last timed frame's
+    generated pcm (--dump-outputs)."""
     from rstnet_amd import synth
     from rstnet_amd.codec.mimi import MimiCodec
     from rstnet_amd.lm.model import LMGen
@@ -712,13 +759,15 @@ def run_e2e(args, rank, world, dev, lm=None, steps=None, warmup=None, lm_result=
     gen = LMGen(model, use_sampling=not args.greedy)
     pcm = synth.synth_audio(B, 1920 * (warmup + steps + n_samples), seed=200 + rank).to(dev)
     torch.manual_seed(1234 + rank)
+    last = {}
     with StreamingPipeline(mimi, gen, B) as pipe:
         step = lambda s: pipe.step(pcm[:, :, s * 1920:(s + 1) * 1920].contiguous())     # noqa: E731
-        elapsed = _timed_loop(step, warmup, steps, world, dev)
-        samples = _sample_steps(lambda i: step(warmup + steps + i), n_samples)
+        elapsed = _timed_loop(lambda s: last.update(pcm=step(s)), warmup, steps, world, dev)
+        if dump and rank == 0:
+            dump_outputs(dump, last)
+        samples = _sample_steps(lambda i: step(warmup + steps + i), n_samples) if args.full else None
     if rank != 0:
         return None
-    timing = _timing(samples)
     codec_bytes = 4 * sum(v.numel() for k, v in mimi_sd.items() if v.is_floating_point())
     lm_bytes = lm_result["roofline"]["frame"]["algorithmic_gb"] * 1e9 if lm_result else None
     result = {
@@ -728,11 +777,12 @@ def run_e2e(args, rank, world, dev, lm=None, steps=None, warmup=None, lm_result=
         "scaling": "weak", "vs_baseline": None, "dtype": "codec f32; LM bf16 weights, f32 activations", "data": "synthetic",
         "config": {"workload": f"end-to-end streaming: Mimi encode -> LMGen.step -> Mimi decode, BASELINE.json configs[3] shape, {args.lm_config}",
                    "streams_per_gpu": B, "parallelism": f"replica x{world}, streams sharded"},
-        "x_realtime_per_stream": round(steps / elapsed / 12.5, 2),
-        "timing": timing}
+        "x_realtime_per_stream": round(steps / elapsed / 12.5, 2)}
+    if args.full:
+        timing = result["timing"] = _timing(samples)
     if _dist(world):
         result["multi_gpu"] = _multi_gpu_block(world)
-    if lm_bytes is not None:
+    if args.full and lm_bytes is not None:
         # the frame is weight streaming end to end -- every LM weight byte once (bf16) and every codec weight once (fp32: encoder +
         # decoder halves, each streamed once per frame whatever the number of streams)
         total = lm_bytes + codec_bytes
@@ -842,17 +892,17 @@ def main():
 
     if args.workload in ("lm", "e2e", "gpt"):
         if args.workload == "gpt":
-            res = run_gpt(args, rank, world, dev)
+            res = run_gpt(args, rank, world, dev, dump=args.dump_outputs)
             if rank == 0:
                 print(json.dumps(res), flush=True)
         else:
             lm = build_lm(args, rank, world, dev)
             if args.workload == "lm":
-                res = run_lm(args, rank, world, dev, lm=lm)
+                res = run_lm(args, rank, world, dev, lm=lm, dump=args.dump_outputs)
             else:
                 # the frame's byte count and dominant-kernel launches come from a short LM-only pass (as on the default line)
-                lm_res = run_lm(args, rank, world, dev, lm=lm, steps=4, warmup=3, cpu=False)
-                res = run_e2e(args, rank, world, dev, lm=lm, lm_result=lm_res)
+                lm_res = run_lm(args, rank, world, dev, lm=lm, steps=4, warmup=3, cpu=False) if args.full else None
+                res = run_e2e(args, rank, world, dev, lm=lm, lm_result=lm_res, dump=args.dump_outputs)
             if rank == 0:
                 res.get("cpu_baseline", {}).pop("_seconds_per_frame", None)
                 print(json.dumps(res), flush=True)
@@ -884,10 +934,12 @@ def main():
 
     elapsed = _timed_loop(step, args.warmup, args.steps, world, dev)
     codes, timed_wav = last["codes"], last["wav"]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"codes": codes, "wav": timed_wav})
 
     # ---- roofline of the dominant kernel: one extra instrumented step, HIP events around every GEMM launch
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         ops.PROFILE = []
         step()
         torch.cuda.synchronize()
@@ -951,22 +1003,23 @@ def main():
                        "frames_per_step_per_gpu": frames_per_step, "weights": "random-init (rstnet_amd.synth seed 0)",
                        "parallelism": f"replica x{world}, utterances sharded, RCCL weight broadcast only"},
             "x_realtime_per_stream": round(total_frames / elapsed / 12.5 / (args.batch * world), 1),
-            "roofline": roofline,
         }
+        if args.full:
+            result["roofline"] = roofline
         if _dist(world):
             result["multi_gpu"] = _multi_gpu_block(world)
-        if not _dist(world):
+        if args.full and not _dist(world):
             result["timing"] = _timing(_sample_steps(step, max(args.timing_samples, 1)))
-        if not args.no_check:
+        if args.full and not args.no_check:
             match, err, n, timed_err = parity_sample(model, sd_cpu, audio, codes, timed_wav=timed_wav)
             result["code_exact_match_vs_cpu_oracle"] = match
             result["wav_rel_err_vs_cpu_oracle"] = err
             result["timed_batch_wav_rel_err_vs_cpu_oracle"] = timed_err
             result["parity_sample"] = (f"{n} clips x {args.seconds:g} s of the timed batch: encode codes vs oracle/mimi_oracle.py, decode of the oracle's "
                                        f"codes vs its waveform, and the waveform the timed step decoded at batch {args.batch} vs the oracle's")
-        if not args.no_cpu_baseline and not _dist(world):    # the CPU leg is timed on rank 0 of the single-GPU run only
+        if args.full and not args.no_cpu_baseline and not _dist(world):    # the CPU leg is timed on rank 0 of the single-GPU run only
             result["cpu_baseline"] = cpu_baseline(sd_cpu, args.seconds)
-    if _dist(world) and not args.no_sub:
+    if args.full and _dist(world) and not args.no_sub:
         # BASELINE configs[3] on the multi-GPU line: end-to-end streaming with 32 streams PER GPU (256 over 8 GPUs),
         # streams sharded over the ranks, the LM's weights (15.4 GB of bf16) generated on rank 0 and handed to the others by ONE RCCL
         # broadcast -- what MLLM_v2/moshi/models/loaders.py:142-159 does per process from disk and
@@ -990,7 +1043,7 @@ def main():
                                  "e2e_streams_total": 32 * world, "e2e_per_rank_ms": e2e["multi_gpu"].get("per_rank_ms_per_step"),
                                  "lm_broadcast_gb": round(lb.get("bytes", 0) / 1e9, 2), "lm_broadcast_gb_s": lb.get("gb_per_s"),
                                  "codec_broadcast_gb_s": ((result.get("multi_gpu") or {}).get("weight_broadcast") or {}).get("gb_per_s")}
-    if not _dist(world) and not args.no_sub:
+    if args.full and not _dist(world) and not args.no_sub:
         # the north-star targets ride on the same line: batch-1 LM decode and the batch-1 end-to-end streaming frame
         del audio, last, codes, timed_wav
         model = None

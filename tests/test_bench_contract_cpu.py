@@ -183,6 +183,29 @@ def test_summary_object_is_compact_and_complete():
     assert len(json.dumps(s)) < 1400
 
 
+def test_dump_outputs_writes_float32_and_samples_the_same_positions_past_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: every array as <name>.npy in float32, ids exact; a set past the budget keeps one seeded sample of flat positions
+    per array (the same on every run), within the budget; a `None` output is skipped."""
+    import numpy as np
+    import torch
+    b = _bench_module()
+    codes = torch.randint(0, 2048, (3, 8, 5))
+    wav = torch.randn(3, 1, 5 * 1920)
+    b.dump_outputs(str(tmp_path / "a"), {"codes": codes, "wav": wav, "none": None})
+    assert sorted(os.listdir(tmp_path / "a")) == ["codes.npy", "wav.npy"]
+    got = np.load(tmp_path / "a" / "codes.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 8, 5) and np.array_equal(got, codes.numpy().astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "wav.npy"), wav.numpy())
+    monkeypatch.setattr(b, "DUMP_BUDGET_BYTES", 4 * 1000)
+    for run in ("b", "c"):
+        b.dump_outputs(str(tmp_path / run), {"codes": codes, "wav": wav})
+    sizes = [np.load(tmp_path / "b" / f"{n}.npy").nbytes for n in ("codes", "wav")]
+    assert sum(sizes) <= 4 * 1000 and min(sizes) > 0
+    for n, src in (("codes", codes), ("wav", wav)):
+        x, y = np.load(tmp_path / "b" / f"{n}.npy"), np.load(tmp_path / "c" / f"{n}.npy")
+        assert np.array_equal(x, y) and np.isin(x, src.float().numpy().reshape(-1)).all()
+
+
 @pytest.mark.skipif(TAG < "r04", reason="summary added in round 4")
 def test_default_line_ends_with_the_summary():
     with open(os.path.join(ROOT, "profiles", f"{TAG}_codec_bench.json")) as f:

@@ -123,7 +123,7 @@ def test_bench_multi_gpu_line_carries_the_sharded_end_to_end_run_and_the_lm_broa
     the end-to-end streaming run of BASELINE configs[3] -- 32 streams per GPU, the 15.4 GB LM blob through `broadcast_state_dict` -- with
     its per-rank times and both weight broadcasts in `multi_gpu` and in `summary`."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "3", "--warmup", "2", "--batch", "8",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--full", "--steps", "3", "--warmup", "2", "--batch", "8",
            "--sub-steps", "8", "--no-check", "--no-cpu-baseline", "--timing-samples", "2"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
