@@ -394,9 +394,10 @@ int rst_temporal_decode_frame(const uint64_t* dev_tables, const float* x, float*
  * 32 * ((k / 8) % 2) + row % 32 -- so that every wave-level load is one contiguous kilobyte:
  *   rst_skinny_pack_weight_bf16: w [N][K] row-major -> wp [ceil(N/32)*32][K] in that order (pad rows zero); once per weight.
  *     interleave_halves (gated layers, w = [W_u ; W_v], N % 32 == 0): tile t holds rows 16t.. of W_u then the same rows of W_v.
- *   rst_skinny_pack_act_f32: P(x) of one decode step, split into bf16 hi + lo planes (x = hi + lo to 2^-17: fp32-class
- *     accuracy against the fp32 oracle) -> xp [2][ceil(B/32)*32][K]; mode 0 identity, 1 RMSNorm (alpha, eps), 2 SiLU gate
- *     (x rows = [u ; v] of length 2K) -- the same prologues as rst_gemv_bf16_f32.  K % 16 == 0, ldx % 4 == 0.
+ *   rst_skinny_pack_act_f32: P(x) of one decode step, split into bf16 hi + lo planes (hi = P(x) truncated, lo = the residual
+ *     rounded half-up: |P(x) - hi - lo| <= 2^-16 |P(x)|, fp32-class accuracy against the fp32 oracle) -> xp [2][ceil(B/32)*32][K];
+ *     mode 0 identity, 1 RMSNorm (alpha, eps), 2 SiLU gate (x rows = [u ; v] of length 2K) -- the same prologues as
+ *     rst_gemv_bf16_f32.  K % 16 == 0, ldx % 4 == 0.
  *   rst_gemm_skinny_bf16_f32: y[b][n] = (res +) (bias +) sum_k P(x)[b][k] w[n][k]: weights streamed from HBM exactly once,
  *     one workgroup per 32 (64, 128 for large N) weight rows whose 8 waves split K and meet in LDS in a fixed order
  *     (deterministic, no cross-workgroup reduction).  gate_out (optional, then y may be NULL; wp packed with

@@ -89,8 +89,11 @@ __device__ __forceinline__ long packed_index(int row, int k, int K) {
     return ((((long)(row >> 5) * (K >> 4) + (k >> 4)) * 64) + ((k >> 3) & 1) * 32 + (row & 31)) * 8 + (k & 7);
 }
 
-// 8 fp32 -> bf16 hi (truncated: an exact fp32 prefix, so x - hi is exact) and bf16 lo (residual rounded half-up): x = hi + lo
-// to 2^-17.  v_perm_b32 packs the upper halves of two dwords in one instruction.
+// 8 fp32 -> bf16 hi (truncated: an exact fp32 prefix, so x - hi is exact) and bf16 lo (residual rounded half-up): |x - hi - lo| <=
+// 2^-16 |x|.  The truncated hi leaves |r| = |x - hi| < ulp(hi) <= 2^-7 |x|, so r's exponent is at least 8 below x's; rounding r to
+// bf16 costs at most half an ulp of r, 2^(e_r - 8) <= 2^(e_x - 16) (attained: x = 1 + 2^-8 + 2^-16; rounding hi to nearest instead
+// would give 2^-17).  Subnormal residuals are split like normal ones (fp32 denormals are kept).  v_perm_b32 packs the upper halves of
+// two dwords in one instruction.
 __device__ __forceinline__ void split_hi_lo8(const float (&v)[8], u32x4& hi, u32x4& lo) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {

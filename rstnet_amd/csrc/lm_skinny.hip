@@ -6,7 +6,7 @@
 // Skinny GEMM for 4 < batch <= 64: y[b][n] = (res +) (bias +) sum_k x[b][k] * W[n][k] on the bf16 matrix cores.
 // The weight matrix is streamed from HBM exactly once (the step stays bandwidth-bound up to batch ~64); the contraction runs
 // on v_mfma_f32_32x32x16_bf16 with the fp32 activations split into bf16 hi + lo parts (two MFMAs per step): products carry
-// ~17 mantissa bits of x, i.e. fp32-class accuracy against the fp32 oracle (the reference itself rounds activations to bf16).
+// ~16 mantissa bits of x, i.e. fp32-class accuracy against the fp32 oracle (the reference itself rounds activations to bf16).
 // ======================================================================================================================
 namespace {
 
@@ -36,7 +36,8 @@ __global__ __launch_bounds__(256) void skinny_pack_weight_kernel(const unsigned 
 }
 
 // Prologue + hi/lo split + packing of one activation row per workgroup (pad rows of the last batch tile are zero-filled).
-// hi = fp32 truncated to bf16 (an exact prefix, so x - hi is exact), lo = the residual rounded half-up: x = hi + lo to 2^-17.
+// hi = fp32 truncated to bf16 (an exact prefix, so x - hi is exact), lo = the residual rounded half-up: |x - hi - lo| <= 2^-16 |x|
+// (|x - hi| < 2^-7 |x|, and rounding it to bf16 costs half an ulp of it; derivation at split_hi_lo8, lm_common.h).
 // mode 0: identity; 1: RMSNorm x * alpha * rsqrt(eps + mean(x^2)); 2: SiLU gate, x row = [u ; v] -> silu(u) * v.
 __global__ __launch_bounds__(256) void skinny_pack_act_kernel(const float* __restrict__ x, const float* __restrict__ alpha,
                                                              unsigned short* __restrict__ xp, int B, int K, int ldx, int mode, float eps) {

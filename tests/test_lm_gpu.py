@@ -249,8 +249,11 @@ def test_sampling_plateaus_take_lowest_indices(V, k):
 
 @pytest.mark.parametrize("B,N,K,prologue", [(32, 4096, 4096, 0), (5, 1000, 1024, 1), (17, 96, 2816, 2), (64, 2048, 1024, 0), (1, 64, 32, 0)])
 def test_gemm_skinny_fp8_matches_emulation(B, N, K, prologue):
-    """fp8 e4m3 path: bit-level agreement of the quantisers with torch.float8_e4m3fn (per-row amax / 448 scales) and of the
-    product with the fp32 product of the SAME quantised operands; and a sanity bound against the unquantised product."""
+    """fp8 e4m3 path against the product of the operands quantised here like torch.float8_e4m3fn (per-row amax / 448 scales; the
+    quantisers themselves are compared byte for byte in tests/test_lm_operands_gpu.py): with the identity prologue the operands are the
+    same, so only the summation differs (the fp8 instruction's own ~2^-16 of sum |products|: 1e-4 of the largest output); the RMSNorm /
+    SiLU prologues run in fp32 on the device, and the rare element on the other side of a rounding boundary is one e4m3 code (2^-3
+    relative) away: 2e-3.  And a sanity bound against the unquantised product."""
     g = torch.Generator().manual_seed(B + N + K)
     w = (torch.randn(N, K, generator=g) / K ** 0.5).bfloat16()
     x = torch.randn(B, 2 * K if prologue == 2 else K, generator=g)
@@ -269,7 +272,8 @@ def test_gemm_skinny_fp8_matches_emulation(B, N, K, prologue):
     ref_q = q(px).double() @ q(w.float()).double().t() + res.double()
     y = ops.gemm_skinny_fp8(x.to(DEV), w.to(DEV), prologue=prologue, alpha=alpha.to(DEV) if prologue == 1 else None, eps=1e-8,
                             res=res.to(DEV))
-    assert rel_err(y, ref_q) < 2e-3
+    e = rel_err(y, ref_q)
+    assert e < (1e-4 if prologue == 0 else 2e-3), e
     exact = px.double() @ w.double().t() + res.double()
     assert rel_err(y, exact) < 0.1
     assert torch.equal(y, ops.gemm_skinny_fp8(x.to(DEV), w.to(DEV), prologue=prologue, alpha=alpha.to(DEV) if prologue == 1 else None,
