@@ -312,6 +312,25 @@ int rst_codec_transformer_frame(const float* const* in_proj, const float* const*
 int rst_gemv_bf16_f32(const float* x, const float* alpha, const uint16_t* w, const float* res, const float* bias, float* y,
                       int B, int N, int K, int ldx, int ldy, int prologue, float eps, int gate_out, rst_stream_t stream);
 
+/* Weight-only fp8 storage for the GEMV above (opt-in: LMModel.quantize_weights_("fp8")): the same call sites --
+ * in_proj / out_proj (modules/transformer.py:376-423), gating linear_in / linear_out (modules/gating.py:12-51), text_linear and
+ * depformer_in (models/model.py:364-389) -- with the weight stored as OCP e4m3fn bytes q [N][K] row-major plus one fp32 scale per
+ * row, a power of two s_n = 2^e_n.  Activations and accumulation stay fp32.
+ *   rst_quant_rows_fp8: w bf16 [N][K] (finite; the host refuses anything else) -> q, scale.  e_n = the smallest integer with
+ *     amax_n / 2^e_n <= 448 (from the exponent and mantissa bits of amax_n = max_k |w[n][k]|; an all-zero row takes e_n = 0);
+ *     q[n][k] = w[n][k] / s_n rounded to nearest even (exact division; |w / s| <= 448, so nothing saturates and the NaN codes
+ *     0x7F / 0xFF never appear; e4m3 subnormals round as subnormals).  q * s is exactly a bf16 number.  Any N, K > 0.
+ *   rst_gemv_fp8w_f32: y[b][n] = (res ? res[b][n] : 0) + (bias ? bias[n] : 0) + s_n * sum_k P(x)[b][k] * q[n][k] -- the scale
+ *     multiplies the dot product only.  Arguments as rst_gemv_bf16_f32 (prologue 0 / 1 / 2, gate_out: y[b][n] = silu(row n) *
+ *     (row N/2 + n), each row with its own scale and bias), 1 <= B <= 4, K % 16 == 0, x and q 16-byte aligned, and B * roundup(K,
+ *     1024) <= 32768 (the fp32 activation stage); rst_gemv_fp8w_supported(B, N, K) answers 1 for exactly these shapes -- callers
+ *     take the bf16 route (same values, twice the bytes) for the others.  Schedules as the bf16 GEMV: batch-1 RMSNorm layers with
+ *     N*K >= 2^24, K <= 4096 issue x before the weight stream; batch-1 plain layers with N*K >= 2^24, K >= 2048 split K over the waves. */
+int rst_quant_rows_fp8(const uint16_t* w, uint8_t* q, float* scale, int N, int K, rst_stream_t stream);
+int rst_gemv_fp8w_supported(int B, int N, int K);
+int rst_gemv_fp8w_f32(const float* x, const float* alpha, const uint8_t* q, const float* scale, const float* res, const float* bias,
+                      float* y, int B, int N, int K, int ldx, int ldy, int prologue, float eps, int gate_out, rst_stream_t stream);
+
 /* Two fused forms of the batch <= 2 GEMV for the depth transformer ("depformer", models/model.py:392-428,564-597;
  * "codecformer", models/llama_streaming.py:727-749), whose 8 steps x 6 layers are a chain of ~5 us launches:
  *

@@ -431,3 +431,21 @@ int rst_launch_skinny_pack_act_fp8(const float* x, const float* alpha, unsigned 
 int rst_launch_skinny_pack_weight(const unsigned short* w, unsigned short* wp, int N, int K, int interleave, hipStream_t stream);
 int rst_launch_skinny_pack_act(const float* x, const float* alpha, unsigned short* xp, int B, int K, int ldx, int mode, float eps,
                                hipStream_t stream);
+
+// ---- lm_gemv_fp8.hip: the small-batch GEMV on fp8 (OCP e4m3fn) weights with one power-of-two scale per row, and its quantiser
+struct GemvFp8Params {
+    const float* x;             // [B][ldx] fp32 activations (prologue 2: [B][2K] = [u ; v])
+    const float* alpha;         // prologue 1: RMSNorm gain [K]
+    const unsigned char* q;     // [N][K] e4m3fn bytes
+    const float* scale;         // [N] row scales: multiply the dot product only (the bias is added after the scale)
+    const float* res;           // optional [B][ldy]
+    const float* bias;          // optional [N]
+    float* y;                   // [B][ldy]
+    int B, N, K, ldx, ldy;
+    int prologue;               // 0 none, 1 RMSNorm, 2 SiLU gate
+    int gate_out;               // N even, no res: y[b][n] = silu(row n) * (row N/2 + n), n < N/2, each row with its own scale
+    float eps;
+};
+int rst_gemv_fp8w_supported_impl(int B, int N, int K);
+int rst_launch_gemv_fp8w(const GemvFp8Params& p, hipStream_t stream);
+int rst_launch_quant_rows_fp8(const unsigned short* w, unsigned char* q, float* scale, int N, int K, hipStream_t stream);

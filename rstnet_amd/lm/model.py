@@ -31,6 +31,20 @@ def _gating_hidden(dim: int, dim_feedforward: int) -> int:
     return (21 * dim) // 8 if dim_feedforward == 4 * dim else (2 * dim_feedforward) // 3
 
 
+def _w8(mod: nn.Module, name: str = "weight") -> Optional[tuple]:
+    """The ``(q, scale)`` fp8 copy of parameter ``name`` of ``mod`` (``LMModel.quantize_weights_``), or None.  The copy is dropped when
+    the bf16 parameter was replaced or written since: it then no longer holds the same values."""
+    q = getattr(mod, name + "_q8", None)
+    if q is None:
+        return None
+    w = getattr(mod, name)
+    if mod._w8_of.get(name) != (w.data_ptr(), w._version):
+        setattr(mod, name + "_q8", None)
+        setattr(mod, name + "_s8", None)
+        return None
+    return q, getattr(mod, name + "_s8")
+
+
 class _Weight(nn.Module):
     """Holder of a ``weight`` parameter (nn.Linear / nn.Embedding key layout); the arithmetic lives in the kernels."""
 
@@ -129,6 +143,7 @@ class StreamingTransformer(StreamingModule[_StepState]):
             raise NotImplementedError(f"positional_embedding={positional_embedding!r}")
         self.d_model, self.num_heads, self.context = d_model, num_heads, context
         self.rope, self.max_period, self.weights_per_step = positional_embedding == "rope", max_period, weights_per_step
+        self.weight_dtype = "bf16"        # "fp8": LMModel.quantize_weights_ left fp8 copies on the layers; the chain route streams them
         self.layers = nn.ModuleList([_Layer(d_model, dim_feedforward, weights_per_step, device=device, dtype=dtype)
                                      for _ in range(num_layers)])
 
@@ -191,6 +206,9 @@ class StreamingTransformer(StreamingModule[_StepState]):
                 gate = layer.gating[k_idx]
             else:
                 w_in, w_out, gate = att.in_proj_weight, att.out_proj.weight, layer.gating
+            # fp8 copies of a quantised model (never the depth transformer: its weights are not covered)
+            q8 = self.weight_dtype == "fp8" and not self.weights_per_step
+            w8_in = _w8(att, "in_proj_weight") if q8 else None
             if l == 0 and embed is not None:
                 add, table, tokens, col = embed
                 if B <= 2 and E <= 4096 and E % 8 == 0:
@@ -198,15 +216,16 @@ class StreamingTransformer(StreamingModule[_StepState]):
                 else:
                     x = ops.embed_sum(tokens, [table], [col], add=add)        # (a column block of h_all is read in place: no copy launch)
             if l > 0 or embed is None or not (B <= 2 and E <= 4096 and E % 8 == 0):
-                qkv = ops.lm_linear(x, w_in, prologue=ops.PROLOGUE_RMSNORM, alpha=layer.norm1.alpha_f32(), eps=layer.norm1.eps)
+                qkv = ops.lm_linear(x, w_in, prologue=ops.PROLOGUE_RMSNORM, alpha=layer.norm1.alpha_f32(), eps=layer.norm1.eps,
+                                    w8=w8_in)
             if fused_attn:
                 x = ops.gemv_attn(qkv, st.k[l], st.v[l], pos_t, w_out, context=self.context, res=x)
             else:
                 a = ops.lm_attn_decode(qkv, st.k[l], st.v[l], pos_t, rope=self.rope, context=self.context,
                                        max_period=self.max_period, scratch=st.scratch, packed=B > 2, rope_table=rope_table)
-                x = ops.lm_linear(a, w_out, res=x)
+                x = ops.lm_linear(a, w_out, res=x, w8=_w8(att.out_proj) if q8 else None)
             x = ops.lm_gated_pair(x, gate.linear_in.weight, gate.linear_out.weight, alpha=layer.norm2.alpha_f32(), eps=layer.norm2.eps,
-                                  res=x)
+                                  res=x, w8_in=_w8(gate.linear_in) if q8 else None, w8_out=_w8(gate.linear_out) if q8 else None)
         if pos is None:
             st.pos.add_(1)
             st.offset_cpu += 1
@@ -215,7 +234,10 @@ class StreamingTransformer(StreamingModule[_StepState]):
 
     def _persistent_step(self, st: _StepState, x: torch.Tensor, pos_t: torch.Tensor, cap: int) -> Optional[torch.Tensor]:
         """All layers of a batch-1 step as ONE persistent launch (csrc/lm_temporal.hip) when the library serves the shape and the
-        device's persistent launches are healthy; None -> the launch-per-op chain below."""
+        device's persistent launches are healthy; None -> the launch-per-op chain below.  Never for a quantised model: the persistent
+        launch reads the bf16 weights and would stream twice the bytes of the chain."""
+        if self.weight_dtype != "bf16":
+            return None
         E, H = self.d_model, self.num_heads
         Hd = self.layers[0].gating.linear_out.weight.shape[1]
         w0 = self.layers[0].self_attn.in_proj_weight
@@ -283,7 +305,9 @@ class LMModel(StreamingContainer):
         self.linears = nn.ModuleList([_Weight(card, depformer_dim, **fk) for _ in range(dep_q)])
         self.config = ModelConfig(model_type="lora")
         self._in_cat = _PackedCache()
+        self._in_cat8 = _PackedCache()
         self._depth_tables = _PackedCache()
+        self.weight_dtype = "bf16"
 
     def depth_frame_tables(self):
         """Pointer tables of the persistent depth-frame launch (``lm.depth_frame.DepthFrameTables``), rebuilt when a weight changes."""
@@ -301,6 +325,79 @@ class LMModel(StreamingContainer):
         version): all of a frame's ``depformer_in[k](transformer_out)`` products are ONE weight-streaming launch."""
         ws = [m.weight for m in self.depformer_in]
         return self._in_cat.get(tuple(ws), lambda: torch.cat([w.detach() for w in ws], 0).contiguous())
+
+    def depformer_in_all_w8(self) -> Optional[tuple]:
+        """The ``(q, scale)`` fp8 copy of ``depformer_in_all()`` of a quantised model (rows quantise independently, so stacking the
+        per-matrix copies IS the copy of the stacked matrix), or None."""
+        if self.weight_dtype != "fp8":
+            return None
+        pairs = [_w8(m) for m in self.depformer_in]
+        if any(c is None for c in pairs):
+            return None
+        return self._in_cat8.get(tuple(c[0] for c in pairs), lambda: (torch.cat([c[0] for c in pairs], 0).contiguous(),
+                                                                     torch.cat([c[1] for c in pairs], 0).contiguous()))
+
+    def _covered_weights(self):
+        """(module, parameter name) of every matrix ``quantize_weights_`` covers."""
+        for layer in self.transformer.layers:
+            yield layer.self_attn, "in_proj_weight"
+            yield layer.self_attn.out_proj, "weight"
+            yield layer.gating.linear_in, "weight"
+            yield layer.gating.linear_out, "weight"
+        yield self.text_linear, "weight"
+        for m in self.depformer_in:
+            yield m, "weight"
+
+    @torch.no_grad()
+    def quantize_weights_(self, weight_dtype: str = "fp8") -> "LMModel":
+        """Weight-only fp8 storage for the batch <= 2 decode step, in place; returns ``self``.  Idempotent.
+
+        Every COVERED matrix -- the temporal transformer's ``in_proj_weight``, ``out_proj.weight``, ``gating.linear_in.weight``,
+        ``gating.linear_out.weight``, ``text_linear.weight`` and the ``depformer_in[k]`` (13.5 of the 14.76 GB a Moshi-7B frame
+        streams) -- is quantised to e4m3fn bytes with one power-of-two scale per row (``ops.quantize_rows_fp8``), its bf16 parameter is
+        OVERWRITTEN with the dequantised values (exact in bf16; also in the tensors of a state dict the model was built from
+        without copying), and ``(q, scale)`` stay on the module as non-persistent buffers.  ``state_dict()``, the batch > 2 routes and
+        anything else that reads ``.weight`` therefore see the same model as the batch <= 2 GEMVs, which stream the fp8 copy
+        (``ops.gemv_fp8w``).  The bf16 copies stay resident.
+
+        NOT covered, on purpose: embeddings (row lookups, not streams), the depth transformer and the audio heads (they live in
+        the persistent depth-frame launch's bf16 pointer tables: 1.27 GB per frame, a separate piece of work) and the norms.
+        A quantised model does not take the persistent temporal launch (it reads bf16).
+
+        Captured frame graphs embed weight pointers, so quantising while a streaming session of this model is live raises
+        ``RuntimeError``: quantise first, then open the session.  Speech quality under fp8 weights has not been evaluated."""
+        if weight_dtype == "bf16":
+            if self.weight_dtype != "bf16":
+                raise ValueError("a quantised model cannot return to bf16: the bf16 parameters already hold the rounded values")
+            return self
+        if weight_dtype != "fp8":
+            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
+        if self._streaming_state is not None or self.transformer._streaming_state is not None:
+            raise RuntimeError("quantize_weights_ inside a live streaming session: a captured frame graph would keep streaming the "
+                               "bf16 weights; quantise before `streaming()`")
+        covered = list(self._covered_weights())
+        for mod, name in covered:
+            w = getattr(mod, name)
+            if w.dtype != torch.bfloat16:
+                raise TypeError(f"quantize_weights_ needs bf16 weights, got {w.dtype}")
+            if not bool(torch.isfinite(w).all()):
+                raise ValueError(f"quantize_weights_: non-finite values in a {tuple(w.shape)} weight; nothing was quantised")
+        for mod, name in covered:
+            if _w8(mod, name) is not None:
+                continue
+            w = getattr(mod, name)
+            q, scale = ops.quantize_rows_fp8(w.detach())
+            w.copy_(ops.dequantize_rows_fp8(q, scale))
+            if not hasattr(mod, "_w8_of"):
+                mod._w8_of = {}
+            for suffix, t in (("_q8", q), ("_s8", scale)):
+                if hasattr(mod, name + suffix):
+                    setattr(mod, name + suffix, t)
+                else:
+                    mod.register_buffer(name + suffix, t, persistent=False)
+            mod._w8_of[name] = (w.data_ptr(), w._version)
+        self.weight_dtype = self.transformer.weight_dtype = "fp8"
+        return self
 
     # ---- token-id conventions (models/model.py:226-277)
     @property
@@ -362,7 +459,7 @@ class LMModel(StreamingContainer):
         x = ops.embed_sum(toks, tables, list(range(1, K)) + [0])     # ((e_0 + e_1) + ...) + text, as the reference
         x = self.transformer.step(x)
         out = ops.rmsnorm(x, self.out_norm.alpha_f32(), self.out_norm.eps)
-        logits = ops.lm_linear(out, self.text_linear.weight)
+        logits = ops.lm_linear(out, self.text_linear.weight, w8=_w8(self.text_linear) if self.weight_dtype == "fp8" else None)
         return out.view(B, 1, self.dim), logits.view(B, 1, 1, -1)
 
     def forward_depformer(self, depformer_cb_index: int, sequence: torch.Tensor, transformer_out: torch.Tensor) -> torch.Tensor:
@@ -380,15 +477,18 @@ class LMModel(StreamingContainer):
         """Depth step ``k``: previous token = ``tokens[:, col]`` (int64 ``[B, n]``), ``h_t`` fp32 ``[B, dim]`` -> logits ``[B, card]``.
         ``h_all`` (``[B, dep_q * depformer_dim]``, the stacked ``depformer_in`` products of the frame) replaces ``h_t``."""
         E = self.depformer.d_model
-        h = h_all[:, k * E:(k + 1) * E] if h_all is not None else ops.lm_linear(h_t, self.depformer_in[k].weight)
+        h = h_all[:, k * E:(k + 1) * E] if h_all is not None else ops.lm_linear(
+            h_t, self.depformer_in[k].weight, w8=_w8(self.depformer_in[k]) if self.weight_dtype == "fp8" else None)
         table = self.depformer_text_emb.weight if k == 0 else self.depformer_emb[k - 1].weight
         y = self.depformer.step(None, step_index=step_index, pos=pos, embed=(h, table, tokens, col))
         return ops.lm_linear(y, self.linears[k].weight)
 
     @classmethod
-    def from_state_dict(cls, sd: Dict[str, torch.Tensor], cfg: dict, kv_dtype: torch.dtype = torch.bfloat16) -> "LMModel":
+    def from_state_dict(cls, sd: Dict[str, torch.Tensor], cfg: dict, kv_dtype: torch.dtype = torch.bfloat16,
+                        weight_dtype: str = "bf16") -> "LMModel":
         """Model for ``cfg`` (keys of ``rstnet_amd.synth.LM_*``) with weights taken from ``sd`` WITHOUT copying them
-        (a 7.7 B-parameter state dict stays a single 15 GB allocation).  ``kv_dtype``: precision of the temporal KV rings."""
+        (a 7.7 B-parameter state dict stays a single 15 GB allocation).  ``kv_dtype``: precision of the temporal KV rings.
+        ``weight_dtype="fp8"``: ``quantize_weights_("fp8")`` on the loaded model (it rewrites the covered tensors of ``sd`` in place)."""
         model = cls(kv_dtype=kv_dtype, causal=True, layer_scale=None, gating="silu", norm="rms_norm_f32", positional_embedding="rope",
                     depformer_causal=True, depformer_layer_scale=None, depformer_multi_linear=True, depformer_context=8,
                     depformer_gating="silu", depformer_pos_emb="none", depformer_weights_per_step=True, device="meta", **cfg)
@@ -404,7 +504,7 @@ class LMModel(StreamingContainer):
                 mod = getattr(mod, part) if not part.isdigit() else mod[int(part)]
             assert tuple(getattr(mod, leaf).shape) == tuple(tensor.shape), name
             setattr(mod, leaf, nn.Parameter(tensor, requires_grad=False))
-        return model.eval()
+        return model.eval().quantize_weights_(weight_dtype)
 
 
 @dataclass
@@ -485,7 +585,7 @@ class LMGen(StreamingModule[_LMGenState]):
         # the rings belong to the session (so that a frame graph captured by another live session keeps valid pointers and
         # exiting `streaming()` releases them); a bare `depformer_step` call outside any session gets throw-away rings
         # depformer_in[k](transformer_out) for all dep_q steps at once: one 8 x larger launch instead of eight
-        h_all = ops.lm_linear(h_t, lm.depformer_in_all())
+        h_all = ops.lm_linear(h_t, lm.depformer_in_all(), w8=lm.depformer_in_all_w8())
         E, H = dep.d_model, dep.num_heads
         Hd = dep.layers[0].gating[0].linear_out.weight.shape[1]
         if ops.depth_frame_enabled(h_t.device) and h_t.is_cuda and ops.depth_frame_supported(B, E, H, Hd, lm.card, lm.dep_q, len(dep.layers), self.top_k, device=h_t.device):
@@ -534,7 +634,8 @@ class LMGen(StreamingModule[_LMGenState]):
             if state.temporal_base is None:
                 state.temporal_base = tst.offset_cpu - state.offset
             tst.offset_cpu = state.temporal_base + state.offset
-            want = B == 1 and ops.temporal_frame_wanted(tst.offset_cpu)
+            # (a quantised model never takes it -- _persistent_step -- so its frame is not re-captured when the rings pass that mark)
+            want = B == 1 and lm.weight_dtype == "bf16" and ops.temporal_frame_wanted(tst.offset_cpu)
             if state.temporal_choice is None:
                 state.temporal_choice = want
             elif want != state.temporal_choice:

@@ -838,6 +838,60 @@ def gemv_bf16(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE
     return out
 
 
+def quantize_rows_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """bf16 ``[N, K]`` -> (``q`` uint8 ``[N, K]``: OCP e4m3fn bytes, ``scale`` fp32 ``[N]``: one power of two per row, the smallest
+    with ``amax / scale <= 448``; rst_quant_rows_fp8).  ``q * scale`` is exactly a bf16 number.  Non-finite weights raise."""
+    _chk(w, "w", torch.bfloat16)
+    assert w.dim() == 2, tuple(w.shape)
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("rstnet_amd.ops.quantize_rows_fp8: the weight holds non-finite values")
+    N, K = w.shape
+    q = torch.empty(N, K, device=w.device, dtype=torch.uint8)
+    scale = torch.empty(N, device=w.device, dtype=torch.float32)
+    _lib.check(_lib.lib().rst_quant_rows_fp8(_ptr(w), _ptr(q), _ptr(scale), N, K, _stream()))
+    return q, scale
+
+
+def dequantize_rows_fp8(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The bf16 ``[N, K]`` matrix that ``(q, scale)`` of ``quantize_rows_fp8`` stands for (exact: 4 significant bits times a power of two)."""
+    return (q.view(torch.float8_e4m3fn).to(torch.float32) * scale[:, None]).to(torch.bfloat16)
+
+
+def gemv_fp8w_supported(B: int, N: int, K: int) -> bool:
+    """Shapes ``gemv_fp8w`` serves (``K % 16 == 0``, ``B <= 4``, ``B * roundup(K, 1024) <= 32768``); others take the bf16 weight."""
+    return bool(_lib.lib().rst_gemv_fp8w_supported(B, N, K))
+
+
+def gemv_fp8w(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Optional[torch.Tensor] = None,
+              eps: float = 1e-8, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None, gate_out: bool = False) -> torch.Tensor:
+    """``gemv_bf16`` on fp8 weight storage: ``y[B,N] = (res +) (bias +) scale * (P(x) @ q.T)`` with ``q`` e4m3fn bytes ``[N,K]`` and
+    one fp32 scale per row (``quantize_rows_fp8``; rst_gemv_fp8w_f32).  The scale multiplies the dot product only."""
+    _chk(x, "x")
+    _chk(q, "q", torch.uint8)
+    _chk(scale, "scale")
+    _chk(alpha, "alpha")
+    _chk(res, "res")
+    _chk(bias, "bias")
+    B = x.shape[0]
+    N, K = q.shape
+    assert scale.shape == (N,), (tuple(scale.shape), N)
+    assert x.shape[1] == (2 * K if prologue == PROLOGUE_SILU_GATE else K), (tuple(x.shape), N, K, prologue)
+    No = N // 2 if gate_out else N
+    if out is None:
+        out = torch.empty(B, No, device=x.device, dtype=torch.float32)
+    prof = PROFILE
+    if prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    _lib.check(_lib.lib().rst_gemv_fp8w_f32(_ptr(x), _ptr(alpha), _ptr(q), _ptr(scale), _ptr(res), _ptr(bias), _ptr(out), B, N, K, x.shape[1],
+                                           No, prologue, eps, int(gate_out), _stream()))
+    if prof is not None:
+        e1.record()
+        prof.append(("gemv_fp8w", e0, e1, 2.0 * B * N * K, N * K + 4 * N + 4 * (x.numel() + out.numel()), (B, N, K)))
+    return out
+
+
 # Measured on MI355X (tools/bench_depth.py, graph-replayed chains at the depth transformer's shape): the out-projection with the
 # attention as its prologue costs 8.8 us per launch against 4.0 us (plain out-projection) + 3.2 us (attn_small) for the two
 # launches it replaces -- the prologue's dependent chain (qkv row -> 16 K/V rows -> scores -> softmax -> LDS) is longer than a
@@ -1059,34 +1113,55 @@ def gemm_skinny_fp8(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGU
     return out
 
 
+def _gemv_route(B: int, K: int) -> bool:
+    """The weight-streaming GEMV serves this linear (else the matrix-core skinny GEMM)."""
+    return B <= 2 and B * K <= 32768
+
+
+def _w8_usable(w8, B: int, w: torch.Tensor) -> bool:
+    return w8 is not None and gemv_fp8w_supported(B, w.shape[0], w.shape[1])
+
+
 def lm_gated_pair(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, *, alpha: torch.Tensor, eps: float, res: torch.Tensor,
-                  bias_in: Optional[torch.Tensor] = None, bias_out: Optional[torch.Tensor] = None, fp8: bool = False) -> torch.Tensor:
+                  bias_in: Optional[torch.Tensor] = None, bias_out: Optional[torch.Tensor] = None, fp8: bool = False,
+                  w8_in: Optional[tuple] = None, w8_out: Optional[tuple] = None) -> torch.Tensor:
     """The gated MLP of a decode step: ``res + W_out (silu(u) * v)``, ``[u ; v] = W_in rmsnorm(x)`` (modules/gating.py:12-51,
     lit_model.py:399-403).  Batch <= 2: two GEMVs, the gate in the epilogue of the first (row pairs per wave).  Above: the first skinny GEMM applies
-    the gate in its epilogue and hands the packed operand straight to the second -- the gated activation never exists in fp32."""
+    the gate in its epilogue and hands the packed operand straight to the second -- the gated activation never exists in fp32.
+    ``w8_in`` / ``w8_out``: ``(q, scale)`` fp8 copies of the two weights (``quantize_rows_fp8``), read by the GEMV pair only."""
     B = x.shape[0]
     if not fp8 and B <= 2 and B * max(w_out.shape[1], w_in.shape[1]) <= 32768 and w_in.shape[0] % 2 == 0:
         # GEMV pair: every wave of the first owns a (u, v) row pair and writes silu(u) * v; the second is a plain GEMV
-        g = gemv_bf16(x, w_in, prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, gate_out=True)
+        if _w8_usable(w8_in, B, w_in):
+            g = gemv_fp8w(x, w8_in[0], w8_in[1], prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, gate_out=True)
+        else:
+            g = gemv_bf16(x, w_in, prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, gate_out=True)
+        if _w8_usable(w8_out, B, w_out):
+            return gemv_fp8w(g, w8_out[0], w8_out[1], res=res, bias=bias_out)
         return gemv_bf16(g, w_out, res=res, bias=bias_out)
     if fp8 or B <= 2 or B > 64 or w_in.shape[0] % 32:
-        u = lm_linear(x, w_in, prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, fp8=fp8)
-        return lm_linear(u, w_out, prologue=PROLOGUE_SILU_GATE, res=res, bias=bias_out, fp8=fp8)
+        u = lm_linear(x, w_in, prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, fp8=fp8, w8=w8_in)
+        return lm_linear(u, w_out, prologue=PROLOGUE_SILU_GATE, res=res, bias=bias_out, fp8=fp8, w8=w8_out)
     g = gemm_skinny(x, w_in, prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, gate_out=True)
     return gemm_skinny(g, w_out, res=res, bias=bias_out)
 
 
 def lm_linear(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Optional[torch.Tensor] = None,
-              eps: float = 1e-8, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, fp8: bool = False) -> torch.Tensor:
+              eps: float = 1e-8, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, fp8: bool = False,
+              w8: Optional[tuple] = None) -> torch.Tensor:
     """Batch-size dispatch of one decode-step linear: weight-streaming GEMV for B <= 2, bf16-MFMA skinny GEMM above (the
-    prologue then runs inside the activation-packing launch).  ``fp8``: the opt-in e4m3 path (any batch <= 64)."""
+    prologue then runs inside the activation-packing launch).  ``fp8``: the opt-in e4m3 path (any batch <= 64).
+    ``w8 = (q, scale)``: an fp8 copy of ``w`` holding the SAME values (``quantize_rows_fp8`` of a weight that was overwritten with its
+    dequantised form): the GEMV route streams it instead of ``w``; every other route reads ``w``."""
     if isinstance(x, PackedAct):
         return gemm_skinny(x, w, prologue=prologue, res=res, bias=bias)
     if fp8 and x.shape[0] <= 64 and w.shape[1] % 32 == 0 and w.shape[1] <= 16384:
         return gemm_skinny_fp8(x, w, prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
     # the GEMV stages B x K fp32 activations in LDS: beyond two rows that footprint costs occupancy (fewer weight loads in
     # flight) and the matrix-core path is as fast or faster (measured: 4096 x 4096 at B = 3: 16.4 vs 16.5 us, B = 4: 20.9 vs 16.5)
-    if x.shape[0] <= 2 and x.shape[0] * w.shape[1] <= 32768:
+    if _gemv_route(x.shape[0], w.shape[1]):
+        if _w8_usable(w8, x.shape[0], w):
+            return gemv_fp8w(x, w8[0], w8[1], prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
         return gemv_bf16(x, w, prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
     if x.shape[0] <= 64:
         return gemm_skinny(x, w, prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)

@@ -246,7 +246,7 @@ def build_state(args, log_fn: Callable[[str, str], None] = log) -> ServerState:
         from .lm.loaders import load_lm_state_dict
         mimi = get_mimi(args.mimi_weight, device=device)
         sd = load_lm_state_dict(args.moshi_weight, device=device)
-    lm = LMModel.from_state_dict(sd, cfg)
+    lm = LMModel.from_state_dict(sd, cfg, weight_dtype=getattr(args, "lm_weights", "bf16"))
     tok = None
     if args.tokenizer:
         import sentencepiece
@@ -267,6 +267,9 @@ def main(argv=None) -> None:
     p.add_argument("--synthetic", action="store_true", help="seeded random-init weights of the real shapes (no checkpoints needed)")
     p.add_argument("--lm-config", choices=["moshi7b", "tiny"], default="moshi7b")
     p.add_argument("--device", type=str, default="cuda")
+    p.add_argument("--lm-weights", choices=["bf16", "fp8"], default="bf16",
+                   help="storage of the LM's streamed weights: fp8 = e4m3 weight-only copies for the batch-1 step (LMModel.quantize_weights_; "
+                        "speech quality under fp8 weights has not been evaluated)")
     args = p.parse_args(argv)
     if not args.synthetic and not (args.moshi_weight and args.mimi_weight):
         p.error("give --moshi-weight and --mimi-weight, or --synthetic")
