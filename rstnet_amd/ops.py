@@ -31,8 +31,36 @@ PAD_ZERO, PAD_REPLICATE = 0, 1
 PROFILE = None
 
 
+class _profiled:
+    """``with _profiled(name, flops, nbytes, shape):`` around the launches of one profile row.  ``PROFILE`` is read once, on entry:
+    the row ``(name, start event, end event, flops, nbytes, shape)`` goes to the list it named then, and with ``PROFILE is None``
+    no event is created.  A block that raises appends nothing."""
+    __slots__ = ("row", "prof", "e0", "e1")
+
+    def __init__(self, name: str, flops: float, nbytes: int, shape: tuple):
+        self.row = (name, flops, nbytes, shape)
+
+    def __enter__(self):
+        self.prof = PROFILE
+        if self.prof is not None:
+            self.e0, self.e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            self.e0.record()
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.prof is not None and exc_type is None:
+            self.e1.record()
+            name, flops, nbytes, shape = self.row
+            self.prof.append((name, self.e0, self.e1, flops, nbytes, shape))
+        return False
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def _ctx(context: Optional[int]) -> int:
+    """Attention context as the library takes it: 0 = unlimited."""
+    return int(context) if context else 0
 
 
 def _first_tensor(args):
@@ -61,22 +89,24 @@ class _PackedWeights:
     """Cache of device-side re-packed copies of weight tensors, keyed by (device, address, shape).  An entry dies with the
     STORAGE of its source (weak reference): per-step slices of a parameter are fresh tensor objects on every call but share
     the parameter's storage, and an address that the allocator hands out again after a free can never hit a stale entry.
-    A changed ``_version`` (in-place update of the weights) re-packs."""
+    A changed ``_version`` (in-place update of the weights) re-packs; so does one of ``also``, the companion tensors (or None) that
+    ``build`` packs into the same copy."""
 
     def __init__(self):
         self._d: dict = {}
 
-    def get(self, w: torch.Tensor, build):
+    def get(self, w: torch.Tensor, build, also: tuple = ()):
         from torch.multiprocessing.reductions import StorageWeakRef
         key = (w.device, w.data_ptr(), tuple(w.shape), w.dtype)
+        versions = (w._version, *(None if t is None else t._version for t in also))
         hit = self._d.get(key)
-        if hit is not None and hit[1] == w._version and not hit[2].expired():
+        if hit is not None and hit[1] == versions and not hit[2].expired():
             return hit[0]
         if len(self._d) > 64:
             for k in [k for k, v in self._d.items() if v[2].expired()]:
                 del self._d[k]
         packed = build()
-        self._d[key] = (packed, w._version, StorageWeakRef(w.untyped_storage()))
+        self._d[key] = (packed, versions, StorageWeakRef(w.untyped_storage()))
         return packed
 
     def clear(self) -> None:
@@ -122,19 +152,26 @@ def _scratch(cache: dict, device, shape_key: tuple, build):
 GEMM_WIN_SPLIT = None
 
 
+def _split_scratch(device, shape_key: tuple, plan, rows: int, N: int, counters):
+    """Split-K plan + scratch of one GEMM shape, ``(split, partials [split, rows, N] fp32, arrival counters int32)`` or
+    ``(1, None, None)``, cached per (stream, shape); launches on one stream are ordered and the counters re-arm themselves (zero
+    once), so layers of equal shape share the buffers.  ``plan`` / ``counters``: callables, asked when the entry is built."""
+    def build():
+        sk = int(plan())
+        if sk > 1:
+            return (sk, torch.empty(sk, rows, N, device=device, dtype=torch.float32),
+                    torch.zeros(int(counters()), device=device, dtype=torch.int32))
+        return (1, None, None)
+    return _scratch(_gemm_scratch, device, shape_key, build)
+
+
 def _gemm_split_scratch(device, M: int, N: int, K: int):
-    """Split-K plan + scratch of the few- / medium-row (streaming step) GEMMs, cached per (stream, shape); launches on one stream
-    are ordered and the counters re-arm themselves, so layers of equal shape share the buffers."""
+    """The K split of the medium-row (streaming step) GEMMs."""
     if M > 4096 or M == 0:
         return 1, None, None
-
-    def build():
-        sk = int(_lib.lib().rst_gemm_win_split_plan(M, N, K)) if GEMM_WIN_SPLIT is None else int(GEMM_WIN_SPLIT)
-        if sk > 1:
-            return (sk, torch.empty(sk, M, N, device=device, dtype=torch.float32),
-                    torch.zeros(int(_lib.lib().rst_gemm_win_split_tiles(M, N)), device=device, dtype=torch.int32))
-        return (1, None, None)
-    return _scratch(_gemm_scratch, device, ("gemm_win", M, N, K, GEMM_WIN_SPLIT), build)
+    return _split_scratch(device, ("gemm_win", M, N, K, GEMM_WIN_SPLIT),
+                          lambda: _lib.lib().rst_gemm_win_split_plan(M, N, K) if GEMM_WIN_SPLIT is None else GEMM_WIN_SPLIT, M, N,
+                          lambda: _lib.lib().rst_gemm_win_split_tiles(M, N))
 
 
 _skinny_f32_weights = _PackedWeights()
@@ -150,6 +187,7 @@ PIPELINE_FUSE = True
 _b3_weights = _PackedWeights()
 
 
+@_on_tensor_device
 def gemm_win_b3_pack_weight(w: torch.Tensor) -> torch.Tensor:
     """fp32 ``[N, K]`` -> its three bf16 planes in the operand order of the large-M kernel (rst_gemm_win_b3_pack_weight), cached per
     storage / version like the other packed copies."""
@@ -186,6 +224,7 @@ def _b3_route(x, hist, w, B: int, T_in: int, T_out: int, C_: int, K: int, N: int
     return _b3_supported(B, T_in, T_out, C_, K, N, S, P, pad_mode, T_in * C_, hist is not None)
 
 
+@_on_tensor_device
 def skinny_f32_pack_weight(w: torch.Tensor) -> torch.Tensor:
     """fp32 ``[N, K]`` -> MFMA-ordered copy ``[ceil(N/32)*32, ceil(K/8)*8]`` (rst_skinny_f32_pack_weight), cached per storage."""
     _chk(w, "w")
@@ -223,6 +262,11 @@ class PackedRows:
         return self
 
 
+def _packed_row_count(M: int) -> int:
+    """Rows of the packed operand of ``M <= 128`` logical rows: every producer and consumer of a ``PackedRows`` pads alike."""
+    return 32 if M <= 32 else (64 if M <= 64 else 128)
+
+
 # linear1 -> GELU -> linear2 of a streamed transformer layer (few-row route): linear1 writes the operand of linear2 in packed order,
 # no packing launch between them.  False: row-major result + pack (the A/B switch of tools/ab.py).
 SKINNY_F32_CHAIN = True
@@ -243,36 +287,31 @@ def _gemm_few_rows(x, hist, w, bias, res, scale, out, B, T_in, T_out, C_, K, N, 
     ``PackedRows`` (no packing at all); ``out_packed``: ``out`` is the ``xp`` of a ``PackedRows``."""
     M = B * T_out
     wp = skinny_f32_pack_weight(w)
-    dev = x.xp.device if isinstance(x, PackedRows) else x.device
-
-    def build():
-        sk = int(_lib.lib().rst_skinny_f32_split_plan(M, N, K)) if SKINNY_F32_SPLIT is None else int(SKINNY_F32_SPLIT)
-        return (sk, torch.empty(sk, M, N, device=dev, dtype=torch.float32),
-                torch.zeros(((M + 31) // 32) * ((N + 31) // 32), device=dev, dtype=torch.int32)) if sk > 1 else (1, None, None)
-    sc = _scratch(_gemm_scratch, dev, ("skinny", M, N, K, SKINNY_F32_SPLIT), build)
+    packed_in = isinstance(x, PackedRows)
+    sc = _split_scratch(x.xp.device if packed_in else x.device, ("skinny", M, N, K, SKINNY_F32_SPLIT),
+                        lambda: _lib.lib().rst_skinny_f32_split_plan(M, N, K) if SKINNY_F32_SPLIT is None else SKINNY_F32_SPLIT, M, N,
+                        lambda: ((M + 31) // 32) * ((N + 31) // 32))
     plain = hist is None and S == 1 and P == 0 and T_in == T_out and C_ == K and act_in == ACT_NONE
-    if SKINNY_F32_ROWS and plain and ln is None and not isinstance(x, PackedRows) and K % 8 == 0 and x.data_ptr() % 16 == 0:
+    if SKINNY_F32_ROWS and plain and ln is None and not packed_in and K % 8 == 0 and x.data_ptr() % 16 == 0:
         # the rows as they are: one launch
         _lib.check(_lib.lib().rst_linear_few_rows_f32(_ptr(x), K, _ptr(wp), _ptr(bias), _ptr(res), _ptr(scale), _ptr(out), M, N, K, N, act_out,
                                                      sc[0], _ptr(sc[1]), _ptr(sc[2]), int(out_packed), _stream()))
         return
-    if isinstance(x, PackedRows):
+    if packed_in:
         xp = x.xp
         if not (xp.shape[1] == wp.shape[1] and ln is None and hist is None):
             raise ValueError(f"rstnet_amd.ops: a PackedRows operand of {tuple(xp.shape)} does not fit packed weights {tuple(wp.shape)} / takes no LayerNorm or history")
     else:
-        xp = torch.empty(32 if M <= 32 else (64 if M <= 64 else 128), wp.shape[1], device=x.device, dtype=torch.float32)
-    if isinstance(x, PackedRows):
-        pass
-    elif ln is not None:
-        if not (hist is None and S == 1 and P == 0 and T_in == T_out and C_ == K and act_in == ACT_NONE):
-            raise ValueError("rstnet_amd.ops: a LayerNorm can only be folded into the packing launch of a plain linear")
-        _chk(ln[0], "ln gamma")
-        _chk(ln[1], "ln beta")
-        _lib.check(_lib.lib().rst_skinny_f32_pack_ln(_ptr(x), _ptr(ln[0]), _ptr(ln[1]), float(ln[2]), _ptr(xp), M, K, _stream()))
-    else:
-        _lib.check(_lib.lib().rst_skinny_f32_pack_win(_ptr(x), _ptr(hist), _ptr(xp), B, T_in, T_out, C_, K, S, P, pad_mode, T_in * C_, act_in,
-                                                     _stream()))
+        xp = torch.empty(_packed_row_count(M), wp.shape[1], device=x.device, dtype=torch.float32)
+        if ln is not None:
+            if not plain:
+                raise ValueError("rstnet_amd.ops: a LayerNorm can only be folded into the packing launch of a plain linear")
+            _chk(ln[0], "ln gamma")
+            _chk(ln[1], "ln beta")
+            _lib.check(_lib.lib().rst_skinny_f32_pack_ln(_ptr(x), _ptr(ln[0]), _ptr(ln[1]), float(ln[2]), _ptr(xp), M, K, _stream()))
+        else:
+            _lib.check(_lib.lib().rst_skinny_f32_pack_win(_ptr(x), _ptr(hist), _ptr(xp), B, T_in, T_out, C_, K, S, P, pad_mode, T_in * C_, act_in,
+                                                         _stream()))
     _lib.check(_lib.lib().rst_gemm_skinny_f32(_ptr(xp), _ptr(wp), _ptr(bias), _ptr(res), _ptr(scale), _ptr(out), M, N, K, N, act_out,
                                              sc[0], _ptr(sc[1]), _ptr(sc[2]), int(out_packed), _stream()))
 
@@ -282,6 +321,37 @@ def _few_rows(M: int, N: int, K: int) -> bool:
     return 1 <= M <= SKINNY_F32_MAX_ROWS and N * K >= 65536
 
 
+def _gemm(x, hist, w, bias, res, scale, out, B, T_in, T_out, C_, K, N, S, P, pad_mode, act_in, act_out, *, ln=None,
+          out_packed: bool = False, plain_linear: bool = False) -> None:
+    """The one ladder of the dense fp32 GEMMs, ``out [B*T_out, N] = epi(windows(x, hist) @ w.T)``: few rows (``_gemm_few_rows``;
+    ``ln`` / ``out_packed`` / a ``PackedRows`` ``x`` exist on this rung only) -> K split over workgroups -> three-plane bf16 ->
+    the f32 matrix instruction (``plain_linear``: rst_linear_f32 where nothing is split)."""
+    M = B * T_out
+    flops = 2.0 * B * T_out * N * K
+    if _few_rows(M, N, K):        # the same route with and without instrumentation: profiles describe the shipped path
+        x_elems = M * K if isinstance(x, PackedRows) else x.numel()
+        with _profiled("gemm_skinny_f32", flops, 4 * (w.numel() + x_elems + M * N), (M, N, K)):
+            _gemm_few_rows(x, hist, w, bias, res, scale, out, B, T_in, T_out, C_, K, N, S, P, pad_mode, act_in, act_out, ln=ln,
+                           out_packed=out_packed)
+        return
+    split_k, ws, cnt = _gemm_split_scratch(x.device, M, N, K)
+    # (zero padding only: a history buffer / replicate padding keeps the launch on the f32 instruction)
+    b3 = split_k <= 1 and _b3_route(x, hist, w, B, T_in, T_out, C_, K, N, S, P, pad_mode)
+    nbytes = 4 * (x.numel() + w.numel() + out.numel() + (res.numel() if res is not None else 0))
+    with _profiled("gemm_win_b3" if b3 else "gemm_win", flops, nbytes, (M, N, K)):
+        if b3:
+            _lib.check(_lib.lib().rst_gemm_win_b3_f32(_ptr(x), _ptr(hist), _ptr(w), _ptr(gemm_win_b3_pack_weight(w)), _ptr(bias), _ptr(res),
+                                                      _ptr(scale), _ptr(out), B, T_in, T_out, C_, K, N, S, P, pad_mode, T_in * C_, N, act_in,
+                                                      act_out, _stream()))
+        elif plain_linear and split_k <= 1:
+            _lib.check(_lib.lib().rst_linear_f32(_ptr(x), _ptr(w), _ptr(bias), _ptr(res), _ptr(scale), _ptr(out), M, K, N, act_out, _stream()))
+        else:
+            _lib.check(_lib.lib().rst_gemm_win_f32(_ptr(x), _ptr(hist), _ptr(w), _ptr(bias), _ptr(res), _ptr(scale), _ptr(out),
+                                                   B, T_in, T_out, C_, K, N, S, P, pad_mode, T_in * C_, N, act_in, act_out,
+                                                   split_k, _ptr(ws), _ptr(cnt), _stream()))
+
+
+@_on_tensor_device
 def gemm_win(x: torch.Tensor, w: torch.Tensor, *, B: int, T_in: int, T_out: int, C_: int, S: int, P: int, N: int,
              hist: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
              res: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None, pad_mode: int = PAD_ZERO,
@@ -301,80 +371,34 @@ def gemm_win(x: torch.Tensor, w: torch.Tensor, *, B: int, T_in: int, T_out: int,
         assert res.numel() == out.numel()
     if hist is not None:
         assert hist.numel() == B * P * C_, (tuple(hist.shape), B, P, C_)
-    prof = PROFILE
-    if _few_rows(B * T_out, N, K):        # the same route with and without instrumentation: profiles describe the shipped path
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _gemm_few_rows(x, hist, w, bias, res, scale, out, B, T_in, T_out, C_, K, N, S, P, pad_mode, act_in, act_out)
-        if prof is not None:
-            e1.record()
-            prof.append(("gemm_skinny_f32", e0, e1, 2.0 * B * T_out * N * K, 4 * (w.numel() + x.numel() + out.numel()), (B * T_out, N, K)))
-        return out
-    split_k, ws, cnt = _gemm_split_scratch(x.device, B * T_out, N, K)
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    # (zero padding only: a history buffer / replicate padding keeps the launch on the f32 instruction)
-    b3 = split_k <= 1 and _b3_route(x, hist, w, B, T_in, T_out, C_, K, N, S, P, pad_mode)
-    if b3:
-        _lib.check(_lib.lib().rst_gemm_win_b3_f32(_ptr(x), _ptr(hist), _ptr(w), _ptr(gemm_win_b3_pack_weight(w)), _ptr(bias), _ptr(res),
-                                                  _ptr(scale), _ptr(out), B, T_in, T_out, C_, K, N, S, P, pad_mode, T_in * C_, N, act_in,
-                                                  act_out, _stream()))
-    else:
-        _lib.check(_lib.lib().rst_gemm_win_f32(_ptr(x), _ptr(hist), _ptr(w), _ptr(bias), _ptr(res), _ptr(scale), _ptr(out),
-                                               B, T_in, T_out, C_, K, N, S, P, pad_mode, T_in * C_, N, act_in, act_out,
-                                               split_k, _ptr(ws), _ptr(cnt), _stream()))
-    if prof is not None:
-        e1.record()
-        nbytes = 4 * (x.numel() + w.numel() + out.numel() + (res.numel() if res is not None else 0))
-        prof.append(("gemm_win_b3" if b3 else "gemm_win", e0, e1, 2.0 * B * T_out * N * K, nbytes, (B * T_out, N, K)))
+    _gemm(x, hist, w, bias, res, scale, out, B, T_in, T_out, C_, K, N, S, P, pad_mode, act_in, act_out)
     return out
 
 
+@_on_tensor_device
 def linear(x, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, res: Optional[torch.Tensor] = None,
            scale: Optional[torch.Tensor] = None, act_out: int = ACT_NONE,
            ln: Optional[Tuple[torch.Tensor, torch.Tensor, float]] = None, out_packed: bool = False):
-    """``y = epi(LN(x) @ w.T + bias)`` over the last dim of ``x`` (rst_linear_f32).  ``ln = (gamma, beta, eps)``: the LayerNorm in
-    front of the linear; it is the prologue of the launch on the one/two-position GEMV route, part of the packing launch on the
-    few-row route and a separate launch otherwise.  ``out_packed`` (only where ``linear_chains`` says so): returns a ``PackedRows`` --
-    the operand of the next few-row linear in its packed order; ``x`` may be one."""
+    """``y = epi(LN(x) @ w.T + bias)`` over the last dim of ``x`` (rst_linear_f32): the windowed GEMM with one window per row.
+    ``ln = (gamma, beta, eps)``: the LayerNorm in front of the linear; it is the prologue of the launch on the one/two-position
+    GEMV route, part of the packing launch on the few-row route and a separate launch otherwise.  ``out_packed`` (only where
+    ``linear_chains`` says so): returns a ``PackedRows`` -- the operand of the next few-row linear in its packed order; ``x`` may be one."""
     for t, n in ((w, "w"), (bias, "bias"), (res, "res"), (scale, "scale")):
         _chk(t, n)
-    N = w.shape[0]
-    if isinstance(x, PackedRows) or out_packed:
-        K = x.shape[-1]
-        M = 1
-        for d in x.shape[:-1]:
-            M *= d
-        assert w.shape[1] == K and M > 4 and _few_rows(M, N, K), "packed rows travel between few-row linears only"
-        dev = x.xp.device if isinstance(x, PackedRows) else x.device
-        if not isinstance(x, PackedRows):
-            _chk(x, "x")
-        if out_packed:
-            assert res is None and N % 8 == 0
-            out = PackedRows(torch.empty(32 if M <= 32 else (64 if M <= 64 else 128), N, device=dev, dtype=torch.float32), (*x.shape[:-1], N))
-        else:
-            out = torch.empty(*x.shape[:-1], N, device=dev, dtype=torch.float32)
-        fold = ln is not None and SKINNY_F32_PACK_LN and K % 4 == 0
-        xin = x
-        if ln is not None and not fold:
-            xin = layernorm(x, ln[0], ln[1], ln[2])
-        prof = PROFILE
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _gemm_few_rows(xin, None, w, bias, res, scale, out.xp if out_packed else out, 1, M, M, K, K, N, 1, 0, 0, ACT_NONE, act_out,
-                       ln=ln if fold else None, out_packed=out_packed)
-        if prof is not None:
-            e1.record()
-            prof.append(("gemm_skinny_f32", e0, e1, 2.0 * M * N * K, 4 * (w.numel() + M * K + M * N), (M, N, K)))
-        return out
-    _chk(x, "x")
-    K = x.shape[-1]
+    packed_in = isinstance(x, PackedRows)
+    if not packed_in:
+        _chk(x, "x")
+    N, K = w.shape[0], x.shape[-1]
     assert w.shape[1] == K
-    M = x.numel() // K if K else 0
-    out = torch.empty(*x.shape[:-1], N, device=x.device, dtype=torch.float32)
+    M = math.prod(x.shape[:-1]) if K else 0
+    dev = x.xp.device if packed_in else x.device
+    if packed_in or out_packed:
+        assert M > 4 and _few_rows(M, N, K), "packed rows travel between few-row linears only"
+    if out_packed:
+        assert res is None and N % 8 == 0
+        out = PackedRows(torch.empty(_packed_row_count(M), N, device=dev, dtype=torch.float32), (*x.shape[:-1], N))
+    else:
+        out = torch.empty(*x.shape[:-1], N, device=dev, dtype=torch.float32)
     if 1 <= M <= 4 and K % 8 == 0 and K * M <= 32768 and act_out in (ACT_NONE, ACT_GELU):
         # a streaming step of one or two positions: weight-streaming GEMV (every CU pulls rows of w; no split-K hand-off)
         g, b, eps = ln if ln is not None else (None, None, 0.0)
@@ -385,34 +409,8 @@ def linear(x, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, res: Opti
     fold_ln = ln is not None and SKINNY_F32_PACK_LN and _few_rows(M, N, K) and K % 4 == 0
     if ln is not None and not fold_ln:
         x = layernorm(x, ln[0], ln[1], ln[2])
-    prof = PROFILE
-    if _few_rows(M, N, K):
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _gemm_few_rows(x, None, w, bias, res, scale, out, 1, M, M, K, K, N, 1, 0, 0, ACT_NONE, act_out, ln=ln if fold_ln else None)
-        if prof is not None:
-            e1.record()
-            prof.append(("gemm_skinny_f32", e0, e1, 2.0 * M * N * K, 4 * (w.numel() + x.numel() + out.numel()), (M, N, K)))
-        return out
-    split_k, ws, cnt = _gemm_split_scratch(x.device, M, N, K)
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    b3 = split_k <= 1 and _b3_route(x, None, w, 1, M, M, K, K, N, 1, 0, PAD_ZERO)
-    if split_k > 1:
-        _lib.check(_lib.lib().rst_gemm_win_f32(_ptr(x), None, _ptr(w), _ptr(bias), _ptr(res), _ptr(scale), _ptr(out), 1, M, M, K, K, N,
-                                               1, 0, 0, M * K, N, 0, act_out, split_k, _ptr(ws), _ptr(cnt), _stream()))
-    elif b3:
-        _lib.check(_lib.lib().rst_gemm_win_b3_f32(_ptr(x), None, _ptr(w), _ptr(gemm_win_b3_pack_weight(w)), _ptr(bias), _ptr(res), _ptr(scale),
-                                                  _ptr(out), 1, M, M, K, K, N, 1, 0, 0, M * K, N, 0, act_out, _stream()))
-    else:
-        _lib.check(_lib.lib().rst_linear_f32(_ptr(x), _ptr(w), _ptr(bias), _ptr(res), _ptr(scale), _ptr(out), M, K, N,
-                                             act_out, _stream()))
-    if prof is not None:
-        e1.record()
-        nbytes = 4 * (x.numel() + w.numel() + out.numel() + (res.numel() if res is not None else 0))
-        prof.append(("gemm_win_b3" if b3 else "gemm_win", e0, e1, 2.0 * M * N * K, nbytes, (M, N, K)))
+    _gemm(x, None, w, bias, res, scale, out.xp if out_packed else out, 1, M, M, K, K, N, 1, 0, PAD_ZERO, ACT_NONE, act_out,
+          ln=ln if fold_ln else None, out_packed=out_packed, plain_linear=True)
     return out
 
 
@@ -420,6 +418,7 @@ def resblock_supported(C: int, H: int, Kw: int, pre: bool = False, post: bool = 
     return bool(_lib.lib().rst_seanet_resblock_supported(C, H, Kw, int(pre), int(post), K0, Kf))
 
 
+@_on_tensor_device
 def seanet_resblock(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, *, Kw: int,
                     hist: Optional[torch.Tensor] = None, pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                     post: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, elu_out: bool = False) -> torch.Tensor:
@@ -444,25 +443,19 @@ def seanet_resblock(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: tor
     for t, n in tensors:
         _chk(t, n)
     out = torch.empty(B, T, 1 if post is not None else C, device=x.device, dtype=torch.float32)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
     # whole-utterance launches (more than 4096 rows, no streaming history): the three-plane bf16 form, as the large GEMMs
     b3 = (GEMM_B3 and hist is None and B * T > 4096 and x.data_ptr() % 16 == 0
           and _resblock_b3_supported(B, T, C, H, Kw, pre is not None, post is not None, K0, Kf))
-    if b3:
-        wp = resblock_b3_pack_weights(w0, w1, w2, Kw)
-        _lib.check(_lib.lib().rst_seanet_resblock_b3_f32(_ptr(x), _ptr(wp), _ptr(b0), _ptr(b1), _ptr(b2), _ptr(wf), _ptr(bf), _ptr(out),
-                                                         B, T, C, H, Kw, K0, Kf, int(elu_out), _stream()))
-    else:
-        _lib.check(_lib.lib().rst_seanet_resblock_f32(_ptr(x), _ptr(hist), _ptr(w0), _ptr(b0), _ptr(w1), _ptr(b1), _ptr(w2),
-                                                      _ptr(b2), _ptr(wf), _ptr(bf), _ptr(out), B, T, C, H, Kw, K0, Kf, int(elu_out),
-                                                      _stream()))
-    if prof is not None:
-        e1.record()
-        flops = 2.0 * B * T * (Kw * C * H + H * C) + (2.0 * B * T * C * K0) + (2.0 * B * T * C * Kf)
-        prof.append(("resblock_b3" if b3 else "resblock", e0, e1, flops, 4 * (x.numel() + out.numel()), (B * T, C, Kw * C)))
+    flops = 2.0 * B * T * (Kw * C * H + H * C) + (2.0 * B * T * C * K0) + (2.0 * B * T * C * Kf)
+    with _profiled("resblock_b3" if b3 else "resblock", flops, 4 * (x.numel() + out.numel()), (B * T, C, Kw * C)):
+        if b3:
+            wp = resblock_b3_pack_weights(w0, w1, w2, Kw)
+            _lib.check(_lib.lib().rst_seanet_resblock_b3_f32(_ptr(x), _ptr(wp), _ptr(b0), _ptr(b1), _ptr(b2), _ptr(wf), _ptr(bf), _ptr(out),
+                                                             B, T, C, H, Kw, K0, Kf, int(elu_out), _stream()))
+        else:
+            _lib.check(_lib.lib().rst_seanet_resblock_f32(_ptr(x), _ptr(hist), _ptr(w0), _ptr(b0), _ptr(w1), _ptr(b1), _ptr(w2),
+                                                          _ptr(b2), _ptr(wf), _ptr(bf), _ptr(out), B, T, C, H, Kw, K0, Kf, int(elu_out),
+                                                          _stream()))
     return out
 
 
@@ -474,9 +467,10 @@ def _resblock_b3_supported(B: int, T: int, C: int, H: int, Kw: int, pre: bool, p
 _rb3_weights = _PackedWeights()
 
 
+@_on_tensor_device
 def resblock_b3_pack_weights(w0: Optional[torch.Tensor], w1: torch.Tensor, w2: torch.Tensor, Kw: int) -> torch.Tensor:
     """The block's matrices as three bf16 planes in matrix-instruction operand order (rst_seanet_resblock_b3_pack), cached per
-    storage / version of ``w1`` (a block's three weights change together: they are re-packed from one state dict)."""
+    storage of ``w1`` and version of all three."""
     C, H = w2.shape
 
     def build():
@@ -486,14 +480,11 @@ def resblock_b3_pack_weights(w0: Optional[torch.Tensor], w1: torch.Tensor, w2: t
         wp = torch.empty(n, device=w1.device, dtype=torch.int16)
         _lib.check(_lib.lib().rst_seanet_resblock_b3_pack(_ptr(w0), _ptr(w1), _ptr(w2), _ptr(wp), C, H, Kw, w0.shape[1] if w0 is not None else 0,
                                                           _stream()))
-        return (wp, w2._version, None if w0 is None else w0._version)
-    hit = _rb3_weights.get(w1, build)
-    if hit[1] != w2._version or hit[2] != (None if w0 is None else w0._version):       # the companions changed in place: re-pack
-        _rb3_weights._d.pop((w1.device, w1.data_ptr(), tuple(w1.shape), w1.dtype), None)
-        hit = _rb3_weights.get(w1, build)
-    return hit[0]
+        return wp
+    return _rb3_weights.get(w1, build, also=(w2, w0))
 
 
+@_on_tensor_device
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float) -> torch.Tensor:
     for t, n in ((x, "x"), (gamma, "gamma"), (beta, "beta")):
         _chk(t, n)
@@ -508,6 +499,7 @@ def rope_coef(max_period: float, D: int) -> float:
     return float(torch.tensor(-math.log(max_period) * 2 / D, dtype=torch.float32))
 
 
+@_on_tensor_device
 def rope_split(qkv: torch.Tensor, H: int, *, q: Optional[torch.Tensor] = None, k: Optional[torch.Tensor] = None,
                v: Optional[torch.Tensor] = None, pos0: int = 0, pos_dev: Optional[torch.Tensor] = None, ring: bool = False,
                rope: bool = True, max_period: float = 10000.0):
@@ -534,6 +526,7 @@ def rope_split(qkv: torch.Tensor, H: int, *, q: Optional[torch.Tensor] = None, k
 _attn_scratch: dict = {}
 
 
+@_on_tensor_device
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, pos0: int = 0, pos_dev: Optional[torch.Tensor] = None,
               ring: bool = False, context: Optional[int] = None) -> torch.Tensor:
     """q ``[B,H,T,D]``, k/v ``[B,G,cap,D]`` (G = H, or fewer key/value heads on the few-query ring path) -> ``[B,T,H*D]``."""
@@ -555,10 +548,10 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, pos0: int = 
                       lambda: (torch.empty(B * T, H, splits, D + 2, device=q.device, dtype=torch.float32),
                                torch.zeros(B * T, H, device=q.device, dtype=torch.int32)))
         _lib.check(_lib.lib().rst_attn_decode_multi_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(sc[0]), _ptr(sc[1]), _ptr(out), _ptr(pos_dev),
-                                                       B, T, H, D, cap, int(context) if context else 0, splits, G, _stream()))
+                                                       B, T, H, D, cap, _ctx(context), splits, G, _stream()))
         return out
     _lib.check(_lib.lib().rst_attention_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(pos_dev), pos0, B, T, H, D, cap,
-                                            int(ring), int(context) if context else 0, _stream()))
+                                            int(ring), _ctx(context), _stream()))
     return out
 
 
@@ -574,6 +567,7 @@ def attention_step_supported(qkv: torch.Tensor, H: int, cap: int) -> bool:
                 _lib.lib().rst_attention_step_supported(T, E3 // (3 * H), cap))
 
 
+@_on_tensor_device
 def attention_step(qkv: torch.Tensor, H: int, k: torch.Tensor, v: torch.Tensor, pos_dev: torch.Tensor, *, context: Optional[int] = None,
                    rope: bool = True, max_period: float = 10000.0, out_packed: bool = False):
     """qkv ``[B,T,3*H*D]`` (the in-projection of the T new steps) -> ``[B,T,H*D]``; k / v ``[B,H,cap,D]`` rings, appended in place at
@@ -586,12 +580,12 @@ def attention_step(qkv: torch.Tensor, H: int, k: torch.Tensor, v: torch.Tensor, 
     if k.shape != v.shape or k.shape[0] != B or k.shape[1] != H or k.shape[3] != D:
         raise ValueError(f"rstnet_amd.ops: rings {tuple(k.shape)} / {tuple(v.shape)} do not belong to qkv {tuple(qkv.shape)} with {H} heads")
     M = B * T
-    rows = (32 if M <= 32 else (64 if M <= 64 else 128)) if out_packed else 0
+    rows = _packed_row_count(M) if out_packed else 0
     if out_packed and (M > SKINNY_F32_MAX_ROWS or (H * D) % 8):
         raise ValueError(f"rstnet_amd.ops: a packed attention result needs <= {SKINNY_F32_MAX_ROWS} rows and H * D % 8 == 0 (rows {M}, H * D {H * D})")
     out = torch.empty((rows, H * D) if out_packed else (B, T, H * D), device=qkv.device, dtype=torch.float32)
     _lib.check(_lib.lib().rst_attention_step_f32(_ptr(qkv), _ptr(k), _ptr(v), _ptr(out), _ptr(pos_dev), B, T, H, D, k.shape[2],
-                                                 int(context) if context else 0, int(rope), rope_coef(max_period, D), rows, _stream()))
+                                                 _ctx(context), int(rope), rope_coef(max_period, D), rows, _stream()))
     return PackedRows(out, (B, T, H * D)) if out_packed else out
 
 
@@ -624,6 +618,7 @@ def rope_table(T: int, D: int, max_period: float, device) -> torch.Tensor:
     return tab[:T]
 
 
+@_on_tensor_device
 def attention_qkv(qkv: torch.Tensor, H: int, *, rope: bool = True, max_period: float = 10000.0, context: Optional[int] = None) -> torch.Tensor:
     """qkv ``[B, T, 3*H*D]`` (the in-projection's output, "b t (p h d)") -> ``[B, T, H*D]``: causal (+ ``context``) attention over
     positions 0 .. T-1 with interleaved RoPE applied as q / k are loaded -- the whole-utterance pass of
@@ -633,10 +628,11 @@ def attention_qkv(qkv: torch.Tensor, H: int, *, rope: bool = True, max_period: f
     D = E3 // (3 * H)
     out = torch.empty(B, T, H * D, device=qkv.device, dtype=torch.float32)
     tab = rope_table(T, D, max_period, qkv.device) if rope else None
-    _lib.check(_lib.lib().rst_attention_qkv_f32(_ptr(qkv), _ptr(tab), _ptr(out), B, T, H, D, int(context) if context else 0, _stream()))
+    _lib.check(_lib.lib().rst_attention_qkv_f32(_ptr(qkv), _ptr(tab), _ptr(out), B, T, H, D, _ctx(context), _stream()))
     return out
 
 
+@_on_tensor_device
 def rvq_pack(emb: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """emb ``[L, n_codes, D]`` -> (packed ``[L, D/8, n_codes, 2, 4]``, e2 ``[L, n_codes]``)."""
     _chk(emb, "emb")
@@ -650,6 +646,11 @@ def rvq_pack(emb: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
 
 def _int_array(vals: Sequence[int]):
     return (C.c_int * len(vals))(*vals)
+
+
+def _group_arrays(groups: Sequence[Tuple[int, int]]):
+    """(first level, number of levels) of every RVQ group as the two int arrays the library takes."""
+    return _int_array([g[0] for g in groups]), _int_array([g[1] for g in groups])
 
 
 _rvq_keys: dict = {}
@@ -668,6 +669,7 @@ def _rvq_chain_supported(dev: int, M: int, n_codes: int, L: int, D: int, n_group
         return bool(_lib.lib().rst_rvq_chain_supported(M, n_codes, L, D, n_groups))
 
 
+@_on_tensor_device
 def rvq_search(x: torch.Tensor, emb: torch.Tensor, packed: torch.Tensor, e2: torch.Tensor, B: int, F: int,
                groups: Sequence[Tuple[int, int]], return_dist: bool = False):
     """x ``[B*F, n_groups*D]`` projected latents -> codes ``[B, L, F]`` int64 (levels outside ``groups`` untouched)."""
@@ -688,17 +690,17 @@ def rvq_search(x: torch.Tensor, emb: torch.Tensor, packed: torch.Tensor, e2: tor
         sc = _scratch(_rvq_slots, x.device, (L, M, n_codes),
                       lambda: (torch.full((n_slots,), -1, device=x.device, dtype=torch.int64), new_persistent_status(x.device)))
         _lib.check(_lib.lib().rst_rvq_search_chain_f32(_ptr(x), _ptr(emb), _ptr(packed), _ptr(e2), _ptr(codes), _ptr(dist), _ptr(sc[0]), _ptr(sc[1]),
-                                                       M, max(F, 1), x.shape[1], D, n_codes, L, len(groups), _int_array([g[0] for g in groups]),
-                                                       _int_array([g[1] for g in groups]), _stream()))
+                                                       M, max(F, 1), x.shape[1], D, n_codes, L, len(groups), *_group_arrays(groups),
+                                                       _stream()))
         return (codes, dist) if return_dist else codes
     if 0 < M <= 64:     # streaming step: the few-frame form (codes spread over workgroups)
         keys = _scratch(_rvq_keys, x.device, (L, M), lambda: torch.full((L, M), -1, device=x.device, dtype=torch.int64))
     _lib.check(_lib.lib().rst_rvq_search_f32(_ptr(x), _ptr(emb), _ptr(packed), _ptr(e2), _ptr(codes), _ptr(dist), _ptr(keys), M, max(F, 1),
-                                             x.shape[1], D, n_codes, L, len(groups), _int_array([g[0] for g in groups]),
-                                             _int_array([g[1] for g in groups]), _stream()))
+                                             x.shape[1], D, n_codes, L, len(groups), *_group_arrays(groups), _stream()))
     return (codes, dist) if return_dist else codes
 
 
+@_on_tensor_device
 def rvq_gather(codes: torch.Tensor, emb: torch.Tensor, groups: Sequence[Tuple[int, int]]) -> torch.Tensor:
     """codes ``[B, L, F]`` int64 -> ``[B*F, n_groups*D]`` sums of codebook rows per group."""
     _chk(codes, "codes", torch.int64)
@@ -707,11 +709,11 @@ def rvq_gather(codes: torch.Tensor, emb: torch.Tensor, groups: Sequence[Tuple[in
     _, n_codes, D = emb.shape
     out = torch.empty(B * F, len(groups) * D, device=codes.device, dtype=torch.float32)
     _lib.check(_lib.lib().rst_rvq_gather_f32(_ptr(codes), _ptr(emb), _ptr(out), B * F, max(F, 1), D, n_codes, L, len(groups),
-                                             _int_array([g[0] for g in groups]), _int_array([g[1] for g in groups]),
-                                             _stream()))
+                                             *_group_arrays(groups), _stream()))
     return out
 
 
+@_on_tensor_device
 def convtr_depthwise(x: torch.Tensor, w: torch.Tensor, stride: int, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x ``[B,T,C]``, w ``[C,Kw]`` -> ``[B,T*stride,C]``."""
     for t, n in ((x, "x"), (w, "w"), (hist, "hist")):
@@ -723,6 +725,7 @@ def convtr_depthwise(x: torch.Tensor, w: torch.Tensor, stride: int, hist: Option
     return out
 
 
+@_on_tensor_device
 def activation(x: torch.Tensor, act: str) -> torch.Tensor:
     """Stand-alone ELU / GELU (only used when an activation module is called outside a fused container)."""
     _chk(x, "x")
@@ -731,6 +734,7 @@ def activation(x: torch.Tensor, act: str) -> torch.Tensor:
     return out
 
 
+@_on_tensor_device
 def transpose12(x: torch.Tensor) -> torch.Tensor:
     """``[B, R, C] -> [B, C, R]`` (layout adapter between the reference's [B,C,T] and channels-last)."""
     _chk(x, "x")
@@ -742,6 +746,7 @@ def transpose12(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+@_on_tensor_device
 def mask_tail(x: torch.Tensor, lengths: torch.Tensor, replicate: bool = False) -> torch.Tensor:
     """In place: rows ``t >= lengths[b]`` of ``x [B,T,C]`` become zeros (or copies of the last valid row)."""
     _chk(x, "x")
@@ -785,6 +790,7 @@ def flush_hist_updates(pending: list) -> None:
             _lib.check(_lib.lib().rst_hist_update_batch_f32(xs, hs, ti, pp, cc, n, B, _stream()))
 
 
+@_on_tensor_device
 def hist_update(x: torch.Tensor, hist_in: Optional[torch.Tensor], P_out: int) -> torch.Tensor:
     """Last ``P_out`` steps of concat(hist_in, x) along time; x ``[B,T,C]``, hist ``[B,P,C]``.  In steady state (same history
     length, at most 16384 elements per stream) the roll happens IN PLACE and ``hist_in`` itself is returned: the state keeps
@@ -810,6 +816,7 @@ def hist_update(x: torch.Tensor, hist_in: Optional[torch.Tensor], P_out: int) ->
 PROLOGUE_NONE, PROLOGUE_RMSNORM, PROLOGUE_SILU_GATE = 0, 1, 2
 
 
+@_on_tensor_device
 def gemv_bf16(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Optional[torch.Tensor] = None,
               eps: float = 1e-8, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
               out: Optional[torch.Tensor] = None, gate_out: bool = False) -> torch.Tensor:
@@ -826,18 +833,13 @@ def gemv_bf16(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE
     No = N // 2 if gate_out else N
     if out is None:
         out = torch.empty(B, No, device=x.device, dtype=torch.float32)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.lib().rst_gemv_bf16_f32(_ptr(x), _ptr(alpha), _ptr(w), _ptr(res), _ptr(bias), _ptr(out), B, N, K, x.shape[1], No,
-                                           prologue, eps, int(gate_out), _stream()))
-    if prof is not None:
-        e1.record()
-        prof.append(("gemv_bf16", e0, e1, 2.0 * B * N * K, 2 * N * K + 4 * (x.numel() + out.numel()), (B, N, K)))
+    with _profiled("gemv_bf16", 2.0 * B * N * K, 2 * N * K + 4 * (x.numel() + out.numel()), (B, N, K)):
+        _lib.check(_lib.lib().rst_gemv_bf16_f32(_ptr(x), _ptr(alpha), _ptr(w), _ptr(res), _ptr(bias), _ptr(out), B, N, K, x.shape[1], No,
+                                               prologue, eps, int(gate_out), _stream()))
     return out
 
 
+@_on_tensor_device
 def quantize_rows_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """bf16 ``[N, K]`` -> (``q`` uint8 ``[N, K]``: OCP e4m3fn bytes, ``scale`` fp32 ``[N]``: one power of two per row, the smallest
     with ``amax / scale <= 448``; rst_quant_rows_fp8).  ``q * scale`` is exactly a bf16 number.  Non-finite weights raise."""
@@ -862,6 +864,7 @@ def gemv_fp8w_supported(B: int, N: int, K: int) -> bool:
     return bool(_lib.lib().rst_gemv_fp8w_supported(B, N, K))
 
 
+@_on_tensor_device
 def gemv_fp8w(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Optional[torch.Tensor] = None,
               eps: float = 1e-8, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
               out: Optional[torch.Tensor] = None, gate_out: bool = False) -> torch.Tensor:
@@ -880,15 +883,9 @@ def gemv_fp8w(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, *, prologue
     No = N // 2 if gate_out else N
     if out is None:
         out = torch.empty(B, No, device=x.device, dtype=torch.float32)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.lib().rst_gemv_fp8w_f32(_ptr(x), _ptr(alpha), _ptr(q), _ptr(scale), _ptr(res), _ptr(bias), _ptr(out), B, N, K, x.shape[1],
-                                           No, prologue, eps, int(gate_out), _stream()))
-    if prof is not None:
-        e1.record()
-        prof.append(("gemv_fp8w", e0, e1, 2.0 * B * N * K, N * K + 4 * N + 4 * (x.numel() + out.numel()), (B, N, K)))
+    with _profiled("gemv_fp8w", 2.0 * B * N * K, N * K + 4 * N + 4 * (x.numel() + out.numel()), (B, N, K)):
+        _lib.check(_lib.lib().rst_gemv_fp8w_f32(_ptr(x), _ptr(alpha), _ptr(q), _ptr(scale), _ptr(res), _ptr(bias), _ptr(out), B, N, K, x.shape[1],
+                                               No, prologue, eps, int(gate_out), _stream()))
     return out
 
 
@@ -905,6 +902,7 @@ def gemv_attn_supported(B: int, H: int, D: int, cap: int, rope: bool, G: Optiona
     return FUSE_SHORT_RING_ATTENTION and B <= 2 and 1 <= cap <= 8 and not rope and (G is None or G == H) and 4 <= D <= 256 and D & (D - 1) == 0 and B * H * D <= 32768
 
 
+@_on_tensor_device
 def gemv_attn(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos_dev: torch.Tensor, w: torch.Tensor, *,
               context: Optional[int] = None, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``res + W_out attention(qkv)`` in ONE launch (rst_gemv_attn_bf16_f32): ``qkv [B, 3*H*D]`` un-rotated, the ring
@@ -916,18 +914,13 @@ def gemv_attn(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, p
     N = w.shape[0]
     assert qkv.shape == (B, 3 * H * D) and w.shape[1] == H * D, (tuple(qkv.shape), tuple(w.shape), H, D)
     out = torch.empty(B, N, device=qkv.device, dtype=torch.float32)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.lib().rst_gemv_attn_bf16_f32(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(pos_dev), _ptr(w), _ptr(res), _ptr(bias),
-                                                _ptr(out), B, N, H, D, cap, int(context) if context else 0, qkv.shape[1], N, _stream()))
-    if prof is not None:
-        e1.record()
-        prof.append(("gemv_bf16", e0, e1, 2.0 * B * N * H * D, 2 * N * H * D + 4 * (qkv.numel() + out.numel()), (B, N, H * D)))
+    with _profiled("gemv_bf16", 2.0 * B * N * H * D, 2 * N * H * D + 4 * (qkv.numel() + out.numel()), (B, N, H * D)):
+        _lib.check(_lib.lib().rst_gemv_attn_bf16_f32(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(pos_dev), _ptr(w), _ptr(res), _ptr(bias),
+                                                    _ptr(out), B, N, H, D, cap, _ctx(context), qkv.shape[1], N, _stream()))
     return out
 
 
+@_on_tensor_device
 def gemv_embed(add: torch.Tensor, table: torch.Tensor, tokens: torch.Tensor, col: int, w: torch.Tensor, *, alpha: torch.Tensor,
                eps: float = 1e-8, bias: Optional[torch.Tensor] = None):
     """First GEMV of a depth step (rst_gemv_embed_bf16_f32): ``x = add + table[tokens[:, col]]`` (``add`` fp32 ``[B, K]``, possibly a
@@ -943,16 +936,10 @@ def gemv_embed(add: torch.Tensor, table: torch.Tensor, tokens: torch.Tensor, col
     assert w.shape[1] == K and table.shape[1] == K and tokens.shape[0] == B and 0 <= col < tokens.shape[1]
     y = torch.empty(B, N, device=add.device, dtype=torch.float32)
     x = torch.empty(B, K, device=add.device, dtype=torch.float32)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.lib().rst_gemv_embed_bf16_f32(_ptr(add), _ptr(table), _ptr(tokens), _ptr(x), _ptr(alpha), _ptr(w), _ptr(bias), _ptr(y),
-                                                 B, N, K, add.stride(0) if B > 1 else K, N, tokens.shape[1], col, table.shape[0], float(eps),
-                                                 _stream()))
-    if prof is not None:
-        e1.record()
-        prof.append(("gemv_bf16", e0, e1, 2.0 * B * N * K, 2 * N * K + 4 * (2 * B * K + y.numel()), (B, N, K)))
+    with _profiled("gemv_bf16", 2.0 * B * N * K, 2 * N * K + 4 * (2 * B * K + y.numel()), (B, N, K)):
+        _lib.check(_lib.lib().rst_gemv_embed_bf16_f32(_ptr(add), _ptr(table), _ptr(tokens), _ptr(x), _ptr(alpha), _ptr(w), _ptr(bias), _ptr(y),
+                                                     B, N, K, add.stride(0) if B > 1 else K, N, tokens.shape[1], col, table.shape[0], float(eps),
+                                                     _stream()))
     return y, x
 
 
@@ -960,6 +947,7 @@ _skinny_weights = _PackedWeights()
 _skinny_weights_gated = _PackedWeights()
 
 
+@_on_tensor_device
 def skinny_pack_weight(w: torch.Tensor, interleave_halves: bool = False) -> torch.Tensor:
     """bf16 ``[N, K]`` -> the MFMA-ordered copy ``[ceil(N/32)*32, K]`` of rst_skinny_pack_weight_bf16, cached per weight
     storage (the row-major original stays: the batch <= 2 GEMV streams that one).  ``interleave_halves``: the layout of gated
@@ -974,6 +962,7 @@ def skinny_pack_weight(w: torch.Tensor, interleave_halves: bool = False) -> torc
     return (_skinny_weights_gated if interleave_halves else _skinny_weights).get(w, build)
 
 
+@_on_tensor_device
 def skinny_pack_act(x: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Optional[torch.Tensor] = None,
                     eps: float = 1e-8) -> torch.Tensor:
     """fp32 ``[B, K]`` (``[B, 2K]`` for the SiLU gate) -> packed bf16 hi / lo planes ``[2, ceil(B/32)*32, K]`` of P(x)."""
@@ -1009,6 +998,7 @@ def _packed_buffer(device, B: int, K: int, role: str = "in") -> torch.Tensor:
 SKINNY_X32_MAX_K = 2048
 
 
+@_on_tensor_device
 def gemm_skinny(x, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Optional[torch.Tensor] = None,
                 eps: float = 1e-8, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, gate_out: bool = False):
     """``y[B,N] = (res +) (bias +) P(x) @ w.T`` for 2 < B <= 64 on the bf16 matrix cores: prologue + hi/lo split + packing of
@@ -1029,16 +1019,10 @@ def gemm_skinny(x, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Opt
         B = x.shape[0]
         out = None if gate_out else torch.empty(B, N, device=x.device, dtype=torch.float32)
         gp = _packed_buffer(x.device, B, N // 2, "gate") if gate_out else None
-        prof = PROFILE
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.check(_lib.lib().rst_gemm_skinny_x32_bf16_f32(_ptr(x), _ptr(alpha) if prologue == PROLOGUE_RMSNORM else None, float(eps),
-                                                          1 if prologue == PROLOGUE_RMSNORM else 0, x.stride(0) if B > 1 else K, _ptr(wp), _ptr(res),
-                                                          _ptr(bias), _ptr(out), B, N, K, N, _ptr(gp), _stream()))
-        if prof is not None:
-            e1.record()
-            prof.append(("gemm_skinny", e0, e1, 2.0 * B * N * K, 2 * N * K + 4 * (x.numel() + B * N), (B, N, K)))
+        with _profiled("gemm_skinny", 2.0 * B * N * K, 2 * N * K + 4 * (x.numel() + B * N), (B, N, K)):
+            _lib.check(_lib.lib().rst_gemm_skinny_x32_bf16_f32(_ptr(x), _ptr(alpha) if prologue == PROLOGUE_RMSNORM else None, float(eps),
+                                                              1 if prologue == PROLOGUE_RMSNORM else 0, x.stride(0) if B > 1 else K, _ptr(wp),
+                                                              _ptr(res), _ptr(bias), _ptr(out), B, N, K, N, _ptr(gp), _stream()))
         return PackedAct(gp, B, N // 2) if gate_out else out
     if isinstance(x, PackedAct):
         assert prologue == PROLOGUE_NONE and x.K == K
@@ -1051,26 +1035,18 @@ def gemm_skinny(x, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Opt
     # gate_out: w is a stacked [W_u ; W_v]; the epilogue emits silu(u) * v as the packed operand of the next GEMM
     out = None if gate_out else torch.empty(B, N, device=x.device, dtype=torch.float32)
     gp = _packed_buffer(x.device, B, N // 2, "gate") if gate_out else None
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    def build():         # split-K scratch of this shape: partial tiles + arrival counters (zero once, the kernel re-arms them)
-        sk = int(_lib.lib().rst_skinny_bf16_split_plan(B, N, K))
-        return (sk, torch.empty(sk, (B + 31) // 32 * 32, N, device=xp.device, dtype=torch.float32),
-                torch.zeros((N + 31) // 32, device=xp.device, dtype=torch.int32)) if sk > 1 else (1, None, None)
-    sc = _scratch(_gemm_scratch, xp.device, ("skinny_bf16", B, N, K), build)
-    _lib.check(_lib.lib().rst_gemm_skinny_bf16_f32(_ptr(xp), _ptr(wp), _ptr(res), _ptr(bias), _ptr(out), B, N, K, N, _ptr(gp),
-                                                  sc[0], _ptr(sc[1]), _ptr(sc[2]), _stream()))
-    if prof is not None:
-        e1.record()
-        prof.append(("gemm_skinny", e0, e1, 2.0 * B * N * K, 2 * N * K + 4 * (x.numel() + B * N), (B, N, K)))
+    with _profiled("gemm_skinny", 2.0 * B * N * K, 2 * N * K + 4 * (x.numel() + B * N), (B, N, K)):
+        sc = _split_scratch(xp.device, ("skinny_bf16", B, N, K), lambda: _lib.lib().rst_skinny_bf16_split_plan(B, N, K),
+                            (B + 31) // 32 * 32, N, lambda: (N + 31) // 32)
+        _lib.check(_lib.lib().rst_gemm_skinny_bf16_f32(_ptr(xp), _ptr(wp), _ptr(res), _ptr(bias), _ptr(out), B, N, K, N, _ptr(gp),
+                                                      sc[0], _ptr(sc[1]), _ptr(sc[2]), _stream()))
     return PackedAct(gp, B, N // 2) if gate_out else out
 
 
 _skinny_weights_fp8 = _PackedWeights()
 
 
+@_on_tensor_device
 def skinny_pack_weight_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """bf16 ``[N, K]`` -> (fp8 e4m3 copy in MFMA order ``[ceil(N/32)*32, K]`` uint8, per-row scales fp32), cached per weight."""
     _chk(w, "w", torch.bfloat16)
@@ -1085,6 +1061,7 @@ def skinny_pack_weight_fp8(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]
     return _skinny_weights_fp8.get(w, build)
 
 
+@_on_tensor_device
 def gemm_skinny_fp8(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Optional[torch.Tensor] = None,
                     eps: float = 1e-8, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The fp8 (e4m3, per-row scales) form of ``gemm_skinny``: ``y = (res +) (bias +) Q(P(x)) @ Q(w).T`` for 1 <= B <= 64."""
@@ -1101,15 +1078,9 @@ def gemm_skinny_fp8(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGU
     xsc = torch.empty(b32, device=x.device, dtype=torch.float32)
     _lib.check(_lib.lib().rst_skinny_pack_act_fp8(_ptr(x), _ptr(alpha), _ptr(xp), _ptr(xsc), B, K, x.shape[1], prologue, eps, _stream()))
     out = torch.empty(B, N, device=x.device, dtype=torch.float32)
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.lib().rst_gemm_skinny_fp8_f32(_ptr(xp), _ptr(xsc), _ptr(wp), _ptr(wsc), _ptr(res), _ptr(bias), _ptr(out), B, N, K, N,
-                                                 _stream()))
-    if prof is not None:
-        e1.record()
-        prof.append(("gemm_skinny_fp8", e0, e1, 2.0 * B * N * K, N * K + 4 * (x.numel() + out.numel()), (B, N, K)))
+    with _profiled("gemm_skinny_fp8", 2.0 * B * N * K, N * K + 4 * (x.numel() + out.numel()), (B, N, K)):
+        _lib.check(_lib.lib().rst_gemm_skinny_fp8_f32(_ptr(xp), _ptr(xsc), _ptr(wp), _ptr(wsc), _ptr(res), _ptr(bias), _ptr(out), B, N, K, N,
+                                                     _stream()))
     return out
 
 
@@ -1122,6 +1093,7 @@ def _w8_usable(w8, B: int, w: torch.Tensor) -> bool:
     return w8 is not None and gemv_fp8w_supported(B, w.shape[0], w.shape[1])
 
 
+@_on_tensor_device
 def lm_gated_pair(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, *, alpha: torch.Tensor, eps: float, res: torch.Tensor,
                   bias_in: Optional[torch.Tensor] = None, bias_out: Optional[torch.Tensor] = None, fp8: bool = False,
                   w8_in: Optional[tuple] = None, w8_out: Optional[tuple] = None) -> torch.Tensor:
@@ -1146,6 +1118,7 @@ def lm_gated_pair(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, *, a
     return gemm_skinny(g, w_out, res=res, bias=bias_out)
 
 
+@_on_tensor_device
 def lm_linear(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Optional[torch.Tensor] = None,
               eps: float = 1e-8, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, fp8: bool = False,
               w8: Optional[tuple] = None) -> torch.Tensor:
@@ -1170,6 +1143,7 @@ def lm_linear(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE
                                   res=None if res is None else res[i:i + 64], bias=bias) for i in range(0, x.shape[0], 64)])
 
 
+@_on_tensor_device
 def embed_sum(tokens: torch.Tensor, tables: Sequence[torch.Tensor], tok_index: Sequence[int],
               add: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``out[b] = (add[b] +) sum_i tables[i][tokens[b, tok_index[i]]]``; tokens int64 ``[B, n]`` (rows contiguous, any row stride), tables
@@ -1190,6 +1164,7 @@ def embed_sum(tokens: torch.Tensor, tables: Sequence[torch.Tensor], tok_index: S
     return out
 
 
+@_on_tensor_device
 def rmsnorm(x: torch.Tensor, alpha: torch.Tensor, eps: float = 1e-8) -> torch.Tensor:
     _chk(x, "x")
     _chk(alpha, "alpha")
@@ -1207,6 +1182,7 @@ def lm_attn_splits(cap: int, pairs: int) -> int:
     return max(1, min(int(LM_ATTN_MAX_SPLITS), cap // 128, 1024 // max(1, pairs)))
 
 
+@_on_tensor_device
 def lm_rope_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos_dev: torch.Tensor, *, heads: int, rope: bool,
                    max_period: float = 10000.0, rope_dims: int = 0) -> torch.Tensor:
     """qkv ``[B, T, (H+2G)*D]`` (T new steps) -> rotated q ``[B, H, T, D]``; k/v appended to ring slots ``(pos+t) % cap`` of
@@ -1223,6 +1199,7 @@ def lm_rope_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     return q
 
 
+@_on_tensor_device
 def lm_rope_table(pos_dev: torch.Tensor, D: int, *, max_period: float = 10000.0, rope_dims: int = 0) -> torch.Tensor:
     """The rotation of ONE decode step as ``[D/2, 2]`` (cos, sin) pairs (rst_lm_rope_table_f32; identity beyond ``rope_dims / 2``): computed
     once per frame and handed to every layer's ``lm_attn_decode(rope_table=...)`` -- the values the attention launch would compute itself."""
@@ -1232,6 +1209,7 @@ def lm_rope_table(pos_dev: torch.Tensor, D: int, *, max_period: float = 10000.0,
     return out
 
 
+@_on_tensor_device
 def lm_attn_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos_dev: torch.Tensor, *, rope: bool,
                    context: Optional[int], max_period: float = 10000.0, splits: Optional[int] = None,
                    scratch: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, heads: Optional[int] = None,
@@ -1267,7 +1245,7 @@ def lm_attn_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     out = None if packed else torch.empty(B, H * D, device=qkv.device, dtype=torch.float32)
     xp = _packed_buffer(qkv.device, B, H * D) if packed else None
     _lib.check(_lib.lib().rst_lm_attn_decode_f32(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(ws), _ptr(counters), _ptr(out),
-                                                _ptr(pos_dev), B, H, D, cap, int(context) if context else 0, splits, qkv.shape[1],
+                                                _ptr(pos_dev), B, H, D, cap, _ctx(context), splits, qkv.shape[1],
                                                 int(rope), rope_coef(max_period, rope_dims or D), G, rope_dims, _ptr(xp), int(kv16),
                                                 _ptr(rope_table) if rope else None, _stream()))
     return PackedAct(xp, B, H * D) if packed else out
@@ -1276,6 +1254,7 @@ def lm_attn_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
 _sample_ws: dict = {}
 
 
+@_on_tensor_device
 def lm_sample(logits: torch.Tensor, *, use_sampling: bool, temp: float, top_k: int, noise: Optional[torch.Tensor] = None,
               out: Optional[torch.Tensor] = None, limit: int = 0, limit_dev: Optional[torch.Tensor] = None, top_p: float = 0.0,
               two_level: bool = True) -> torch.Tensor:
@@ -1308,6 +1287,7 @@ def lm_sample(logits: torch.Tensor, *, use_sampling: bool, temp: float, top_k: i
     return out
 
 
+@_on_tensor_device
 def lm_ring_begin(cache: torch.Tensor, user_tokens: torch.Tensor, initial: torch.Tensor, delays: torch.Tensor,
                   offset_dev: torch.Tensor, first_user_k: int) -> torch.Tensor:
     """Start of an ``LMGen.step`` frame on the device (models/model.py:506-521): user streams into the token ring
@@ -1324,6 +1304,7 @@ def lm_ring_begin(cache: torch.Tensor, user_tokens: torch.Tensor, initial: torch
     return out
 
 
+@_on_tensor_device
 def lm_ring_commit(cache: torch.Tensor, tokens: torch.Tensor, delays: torch.Tensor, offset_dev: torch.Tensor, max_delay: int) -> torch.Tensor:
     """End of the frame (models/model.py:545-562): ``offset_dev += 1``, generated ``tokens [B, n]`` into the ring, returns the
     delay-aligned gather ``[B, n]`` (meaningful once ``offset > max_delay``)."""
@@ -1490,6 +1471,7 @@ def depth_frame_supported(B: int, E: int, H: int, Hd: int, card: int, dep_q: int
     return _depth_frame_grid(_device_index(device), B, E, H, Hd, card, dep_q, L, top_k if 0 < top_k < card else card) > 0
 
 
+@_on_tensor_device
 def depth_decode_frame(tables, h_all: torch.Tensor, tokens: torch.Tensor, noise: Optional[torch.Tensor], *, use_sampling: bool,
                        temp: float, top_k: int, eps: float, context: Optional[int] = None, limits: Optional[torch.Tensor] = None,
                        ring_cap: Optional[int] = None) -> None:
@@ -1512,20 +1494,14 @@ def depth_decode_frame(tables, h_all: torch.Tensor, tokens: torch.Tensor, noise:
     ws = _scratch(_depth_ws, h_all.device, (B, t.E, t.Hd, t.card),
                   lambda: torch.zeros(int(_lib.lib().rst_depth_frame_workspace_bytes(B, t.E, t.Hd, t.card)) // 8, device=h_all.device,
                                       dtype=torch.int64))
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.lib().rst_depth_decode_frame(
-        t.in_proj, t.out_proj, t.norm1, t.norm2, t.gate_in, t.gate_out, t.heads, t.head_bias, t.emb, t.emb_rows,
-        _ptr(h_all), _ptr(tokens), _ptr(noise) if sampling else None, _ptr(limits), _ptr(ws), _ptr(t.status),
-        B, t.E, t.H, t.Hd, t.card, t.dep_q, t.L, h_all.stride(0) if B > 1 else h_all.shape[1], tokens.stride(0) if B > 1 else tokens.shape[1],
-        noise.stride(0) if (sampling and B > 1) else (noise.shape[1] if sampling else 0), int(top_k), int(sampling), float(temp), float(eps),
-        int(context) if context else 0, int(ring_cap) if ring_cap else t.dep_q, _stream()))
-    if prof is not None:
-        e1.record()
-        n_w = t.dep_q * (t.L * (3 * t.E * t.E + t.E * t.E + 3 * t.Hd * t.E) + t.card * t.E)      # weight elements read once per frame
-        prof.append(("depth_frame", e0, e1, 2.0 * B * n_w, 2 * n_w + 4 * h_all.numel(), (B, t.dep_q, t.L)))
+    n_w = t.dep_q * (t.L * (3 * t.E * t.E + t.E * t.E + 3 * t.Hd * t.E) + t.card * t.E)      # weight elements read once per frame
+    with _profiled("depth_frame", 2.0 * B * n_w, 2 * n_w + 4 * h_all.numel(), (B, t.dep_q, t.L)):
+        _lib.check(_lib.lib().rst_depth_decode_frame(
+            t.in_proj, t.out_proj, t.norm1, t.norm2, t.gate_in, t.gate_out, t.heads, t.head_bias, t.emb, t.emb_rows,
+            _ptr(h_all), _ptr(tokens), _ptr(noise) if sampling else None, _ptr(limits), _ptr(ws), _ptr(t.status),
+            B, t.E, t.H, t.Hd, t.card, t.dep_q, t.L, h_all.stride(0) if B > 1 else h_all.shape[1], tokens.stride(0) if B > 1 else tokens.shape[1],
+            noise.stride(0) if (sampling and B > 1) else (noise.shape[1] if sampling else 0), int(top_k), int(sampling), float(temp), float(eps),
+            _ctx(context), int(ring_cap) if ring_cap else t.dep_q, _stream()))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1602,6 +1578,7 @@ class TemporalFrameTables:
         self._keep = keep
 
 
+@_on_tensor_device
 def temporal_decode_frame(tables: "TemporalFrameTables", x: torch.Tensor, pos_dev: torch.Tensor, rope_table: Optional[torch.Tensor]) -> torch.Tensor:
     """x fp32 ``[1, E]`` -> ``[1, E]`` through every layer of ``tables`` (one new step at position ``*pos_dev``, appended to the rings);
     ``rope_table``: fp32 ``[D/2, 2]`` of `lm_rope_table` or None (no rotation)."""
@@ -1613,17 +1590,11 @@ def temporal_decode_frame(tables: "TemporalFrameTables", x: torch.Tensor, pos_de
     y = torch.empty_like(x)
     ws = _scratch(_temporal_ws, x.device, (t.E, t.Hd, t.H),
                   lambda: torch.zeros(int(_lib.lib().rst_temporal_frame_workspace_bytes(t.E, t.Hd, t.H)) // 8, device=x.device, dtype=torch.int64))
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(_lib.lib().rst_temporal_decode_frame(
-        _ptr(t.dev_tables), _ptr(x), _ptr(y), _ptr(pos_dev), _ptr(rope_table), _ptr(ws), _ptr(t.status), t.E, t.H, t.Hd, t.L, t.cap,
-        int(t.context) if t.context else 0, int(t.kv_bf16), t.eps, _stream()))
-    if prof is not None:
-        e1.record()
-        n_w = t.L * (4 * t.E * t.E + 3 * t.Hd * t.E)
-        prof.append(("temporal_frame", e0, e1, 2.0 * n_w, 2 * n_w, (1, t.L, t.E)))
+    n_w = t.L * (4 * t.E * t.E + 3 * t.Hd * t.E)
+    with _profiled("temporal_frame", 2.0 * n_w, 2 * n_w, (1, t.L, t.E)):
+        _lib.check(_lib.lib().rst_temporal_decode_frame(
+            _ptr(t.dev_tables), _ptr(x), _ptr(y), _ptr(pos_dev), _ptr(rope_table), _ptr(ws), _ptr(t.status), t.E, t.H, t.Hd, t.L, t.cap,
+            _ctx(t.context), int(t.kv_bf16), t.eps, _stream()))
     return y
 
 
@@ -1659,6 +1630,7 @@ def codec_transformer_status(device) -> torch.Tensor:
     return st
 
 
+@_on_tensor_device
 def codec_transformer_frame(x: torch.Tensor, layers: Sequence[dict], pos_dev: torch.Tensor, *, H: int, context: Optional[int], rope: bool,
                             max_period: float, eps: float) -> torch.Tensor:
     """x fp32 ``[B, T, E]`` (the new positions of every stream) -> ``[B, T, E]`` through all ``layers``: each a dict of fp32 device
@@ -1686,16 +1658,5 @@ def codec_transformer_frame(x: torch.Tensor, layers: Sequence[dict], pos_dev: to
         table("in_proj"), table("out_proj"), table("linear1"), table("linear2"), table("norm1_w"), table("norm1_b"), table("norm2_w"),
         table("norm2_b"), table("scale1") if has_scale else None, table("scale2") if has_scale else None, table("k_cache"), table("v_cache"),
         _ptr(x), _ptr(y), _ptr(pos_dev), _ptr(ws), _ptr(codec_transformer_status(x.device)), B, T, E, H, F_, L, cap,
-        int(context) if context else 0, int(rope), rope_coef(max_period, D), float(eps), _stream()))
+        _ctx(context), int(rope), rope_coef(max_period, D), float(eps), _stream()))
     return y
-
-
-# every public entry point runs under the device guard of its first tensor argument
-for _name in ("skinny_f32_pack_weight", "gemm_win", "linear", "seanet_resblock", "layernorm", "rope_split", "attention", "rvq_pack",
-              "rvq_search", "rvq_gather", "convtr_depthwise", "activation", "transpose12", "mask_tail", "hist_update", "gemv_bf16",
-              "gemv_attn", "gemv_embed", "skinny_pack_weight", "skinny_pack_act", "gemm_skinny", "skinny_pack_weight_fp8", "gemm_skinny_fp8", "lm_gated_pair",
-              "lm_linear", "embed_sum", "rmsnorm", "lm_rope_append", "lm_rope_table", "lm_attn_decode", "lm_sample", "lm_ring_begin", "lm_ring_commit",
-              "depth_decode_frame", "temporal_decode_frame", "codec_transformer_frame"):
-    globals()[_name] = _on_tensor_device(globals()[_name])
-del _name
-
