@@ -9,6 +9,8 @@ from typing import Any, List, Optional
 
 import torch
 
+from . import ops
+
 _in_graph = False      # a Graphed call is on the stack: nothing below it captures a graph of its own (compile.py:145-165)
 
 
@@ -112,6 +114,25 @@ class Graphed:
         self._refresh_inputs(args)
         self.graph.replay()
         return self.static_out
+
+
+class RecaptureGate:
+    """When the holder of a captured frame graph has to capture again because the device's persistent launches were retired or given
+    back (``ops.persistent_epoch`` moved: the frame now takes other launches).  ``moved(frame)``, asked once per frame BEFORE the
+    replay and never inside a capture, looks at the repair counters every 64th frame (``ops.persistent_poll``: no synchronisation) and
+    answers whether the epoch changed since the last question -- on the polling frames only, or on ``every_frame`` (the pipeline, whose
+    LM session may have polled for it).  What is rebuilt, and after how many eager frames, is the caller's."""
+
+    def __init__(self, device, every_frame: bool = False):
+        self.device, self.every_frame, self.epoch = device, every_frame, ops.persistent_epoch(device)
+
+    def moved(self, frame: int) -> bool:
+        if frame % 64 == 0:
+            ops.persistent_poll(self.device)
+        elif not self.every_frame:
+            return False
+        was, self.epoch = self.epoch, ops.persistent_epoch(self.device)
+        return was != self.epoch
 
 
 CUDAGraphed = Graphed       # the reference's name

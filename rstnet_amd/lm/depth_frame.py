@@ -1,12 +1,16 @@
-"""Pointer tables of ``rst_depth_decode_frame`` (the depth phase of a frame as one persistent launch, csrc/lm_depth.hip) for a
-depth transformer with per-step weights -- ``LMModel.depformer`` (models/model.py:188-225) or ``GPT.codecformer``
-(models/llama_streaming.py:560-590): host arrays of device pointers, built once per weight version."""
+"""The depth phase of a frame for a depth transformer with per-step weights -- ``LMModel.depformer`` (models/model.py:188-225) or
+``GPT.codecformer`` (models/llama_streaming.py:560-590): ``DepthDecoder`` runs it (both front ends delegate to the one their model
+owns), ``DepthFrameTables`` are the pointer tables of ``rst_depth_decode_frame`` (the phase as one persistent launch,
+csrc/lm_depth.hip): host arrays of device pointers, built once per weight version."""
 from __future__ import annotations
 
 import ctypes as C
 from typing import List, Optional, Sequence
 
 import torch
+
+from .. import ops
+from ..packed import _PackedCache
 
 
 class DepthFrameTables:
@@ -51,7 +55,6 @@ class DepthFrameTables:
         self.eps = float(dep.layers[0].norm1.eps)
         self.context = dep.context
         dev = heads[0].device
-        from .. import ops
         # 4 words (csrc/persist.h): time-out codes of the frame in flight | frames repaired by the one-workgroup launch | OR of the
         # repaired frames' codes | reserved; registered with ops.persistent_poll
         self.status = ops.new_persistent_status(dev)
@@ -68,3 +71,87 @@ class DepthFrameTables:
         if st[0] or st[1]:
             raise RuntimeError(f"rst_depth_decode_frame: hand-offs timed out ({st[1]} frame(s) repaired by the one-workgroup launch, codes "
                                f"{st[2]:#x}, in flight {st[0]:#x}); the device was shared with other work or the launch was not fully resident")
+
+
+class DepthDecoder:
+    """The depth phase of a frame, once for ``LMGen`` and ``GPTGen``: step ``k`` of ``dep_q`` = in-projection ``k`` of the temporal output +
+    embedding of the previous token -> the per-step-weights transformer ``dep`` -> head ``k`` -> sampler.  Owned by the model; holds
+    REFERENCES to its modules (``dep_q`` each; ``emb[0]`` is the text table, a head may carry a ``bias``), never copies of their weights."""
+
+    def __init__(self, dep, in_proj: Sequence, emb: Sequence, heads: Sequence):
+        assert len(in_proj) == len(emb) == len(heads) == dep.weights_per_step
+        self.dep, self.in_proj, self.emb, self.heads = dep, in_proj, emb, heads
+        self._in_cat, self._tables = _PackedCache(), _PackedCache()
+
+    def _head_bias(self, k: int) -> Optional[torch.Tensor]:
+        return self.heads[k].bias_f32() if getattr(self.heads[k], "bias", None) is not None else None
+
+    def in_all(self) -> torch.Tensor:
+        """``[dep_q * E, dim]``: the in-projections stacked (a second copy per weight version): ONE weight-streaming launch per frame."""
+        ws = [m.weight for m in self.in_proj]
+        return self._in_cat.get(tuple(ws), lambda: torch.cat([w.detach() for w in ws], 0).contiguous())
+
+    def tables(self) -> DepthFrameTables:
+        """Pointer tables of the persistent depth-frame launch, rebuilt when any weight they point at changes."""
+        dep = self.dep
+        params = [p for l in dep.layers for p in (l.self_attn.in_proj_weight, l.self_attn.out_proj.weight, l.norm1.alpha, l.norm2.alpha)]
+        params += [g.linear_in.weight for l in dep.layers for g in l.gating] + [g.linear_out.weight for l in dep.layers for g in l.gating]
+        params += [m.weight for m in self.heads] + [getattr(m, "bias", None) for m in self.heads] + [m.weight for m in self.emb]
+        return self._tables.get(tuple(params), lambda: DepthFrameTables(
+            dep, [m.weight for m in self.heads], [self._head_bias(k) for k in range(len(self.heads))], [m.weight for m in self.emb]))
+
+    def check(self) -> None:      # ``DepthFrameTables.check`` of the tables built so far, if any
+        if self._tables._val is not None:
+            self._tables._val.check()
+
+    def step_hidden(self, k: int, tokens: torch.Tensor, col: int, h: Optional[torch.Tensor], *, h_all: Optional[torch.Tensor] = None,
+                    w8: Optional[tuple] = None, pos: Optional[torch.Tensor] = None, step_index: Optional[int] = None) -> torch.Tensor:
+        """Depth step ``k`` up to its head: previous token ``tokens[:, col]`` (int64 ``[B, n]``), ``h`` fp32 ``[B, dim]`` -> ``[B, E]``.  ``h_all``
+        (``h @ in_all().T``) replaces ``h``; ``w8``: fp8 copy of in-projection ``k``; ``pos`` / ``step_index``: as ``StreamingTransformer.step``."""
+        E = self.dep.d_model
+        add = h_all[:, k * E:(k + 1) * E] if h_all is not None else ops.lm_linear(h, self.in_proj[k].weight, w8=w8)
+        return self.dep.step(None, step_index=step_index, pos=pos, embed=(add, self.emb[k].weight, tokens, col))
+
+    def step_logits(self, k: int, tokens: torch.Tensor, col: int, h: Optional[torch.Tensor], **step) -> torch.Tensor:
+        """``step_hidden`` + head ``k`` -> logits fp32 ``[B, card]``."""
+        return ops.lm_linear(self.step_hidden(k, tokens, col, h, **step), self.heads[k].weight, bias=self._head_bias(k))
+
+    def decode_frame(self, tokens: torch.Tensor, h: torch.Tensor, noise: Optional[torch.Tensor], pos: torch.Tensor, *, use_sampling: bool,
+                     temp: float, top_k: int, limits: Optional[torch.Tensor] = None, rings=None, w8: Optional[tuple] = None, keep=None,
+                     persistent: bool = True) -> None:
+        """The whole phase IN PLACE on ``tokens`` (int64 ``[B, >= dep_q + 1]``, any row stride): column 0 holds the text token, step k embeds
+        column k and samples column k + 1.  ``h`` fp32 ``[B, dim]``; ``noise``: Exp(1) draws ``[B, dep_q * top_k]`` or None (greedy); ``pos``:
+        int64 ``arange(dep_q)`` on the device (the steps are positions 0 .. dep_q - 1 of a ring that restarts every frame, as constant device
+        scalars: no counter to zero and bump); ``limits`` int32 ``[dep_q]``: per-step id blanking; ``w8``: the fp8 copy of ``in_all()``.
+        ``rings``, the KV rings of the launch-per-op chain -- None: those installed on the transformer; a state: swapped in for the call; a
+        callable ``B -> state``: called only if the chain runs.  ``keep``: the object whose ``tables`` attribute keeps the pointer tables
+        alive (a captured frame embeds their device pointers).  ``persistent=False`` keeps the call off the one-launch route."""
+        dep, Q = self.dep, len(self.heads)
+        B, dev = tokens.shape[0], h.device
+        h_all = ops.lm_linear(h, self.in_all(), w8=w8)      # the in-projections of all dep_q steps: one 8 x larger launch instead of eight
+        Hd, card = dep.layers[0].gating[0].linear_out.weight.shape[1], self.heads[0].weight.shape[0]
+        if ops.depth_frame_enabled(dev) and persistent and \
+                ops.depth_frame_supported(B, dep.d_model, dep.num_heads, Hd, card, Q, len(dep.layers), top_k, device=dev):
+            # batch 1 / 2: the whole phase (dep_q x (L layers + head + sampler)) is ONE persistent launch whose ops hand their vectors
+            # over in-kernel, on a dense [B, dep_q + 1] buffer; the slot -> position map follows the capacity of the rings in use
+            dense = tokens if tokens.shape[1] == Q + 1 and tokens.is_contiguous() else tokens[:, :Q + 1].contiguous()
+            st = dep._streaming_state if rings is None else rings
+            tables = self.tables()
+            if keep is not None:
+                keep.tables = tables
+            ops.depth_decode_frame(tables, h_all, dense, noise, use_sampling=use_sampling, temp=temp, top_k=top_k, eps=dep.layers[0].norm1.eps,
+                                   context=dep.context, limits=limits, ring_cap=None if st is None or callable(st) else st.k[0].shape[2])
+            if dense is not tokens:
+                tokens[:, 1:Q + 1] = dense[:, 1:]
+            return
+        saved = dep._streaming_state
+        if rings is not None:
+            dep._streaming_state = rings(B) if callable(rings) else rings
+        try:
+            for k in range(Q):
+                logits = self.step_logits(k, tokens, k, None, h_all=h_all, pos=pos[k:k + 1], step_index=k)
+                ops.lm_sample(logits, use_sampling=use_sampling, temp=temp, top_k=top_k, out=tokens[:, k + 1],
+                              noise=None if noise is None else noise[:, k * top_k:(k + 1) * top_k],
+                              limit_dev=None if limits is None else limits[k:k + 1])
+        finally:
+            dep._streaming_state = saved

@@ -19,7 +19,7 @@ from typing import Callable, Dict, Optional
 import torch
 
 from .. import ops
-from ..graphs import Graphed as _Graphed
+from ..graphs import Graphed as _Graphed, RecaptureGate
 from .gpt import GPT, _GPTState
 
 
@@ -59,6 +59,7 @@ class GPTGen:
         self.n_audio_codes = n_audio_codes
         self.noise = noise           # test hook: Exp(1) draws (kind, g_idx, l_idx) -> [B, k]; disables graph capture
         self._saved = None
+        self.tables = None           # the DepthFrameTables a captured frame points at (kept alive with the graph)
         self._limits: Optional[torch.Tensor] = None
         self._depth: Optional[_Graphed] = None
         self._fused: Optional[_Graphed] = None       # `step`: the whole frame as one graph on the session's token column `_col`
@@ -78,7 +79,7 @@ class GPTGen:
         self._depth_pos = torch.arange(cfg.dep_q, device=dev, dtype=torch.long)
         self._depth = _Graphed(self._depth_frame, disable=eager)
         self._regime, self.B, self._eager = None, batch_size, eager
-        self._frames, self._persist_epoch = 0, ops.persistent_epoch(dev)
+        self._frames, self._gate = 0, RecaptureGate(dev)      # (`frame` and `step` share the frame counter and the gate)
 
     def end(self) -> None:
         m = self.model
@@ -111,33 +112,9 @@ class GPTGen:
         token in column 0; step l embeds column l and samples column l + 1 (the layout of ``LMGen._depth``).  ``noise``: Exp(1)
         draws ``[B, dep_q * k]`` or None (greedy)."""
         m = self.model
-        dep, cfg = m.codecformer, m.config
-        B = tokens.shape[0]
-        k_eff = min(self.top_k, cfg.audio_card)
-        h_all = ops.lm_linear(h, m.codecformer_in_all())      # codecformer_in[k](h) of all dep_q steps in one launch
-        E, H = dep.d_model, dep.num_heads
-        Hd = dep.layers[0].gating[0].linear_out.weight.shape[1]
-        if ops.depth_frame_enabled(tokens.device) and ops.depth_frame_supported(B, E, H, Hd, cfg.audio_card, cfg.dep_q, len(dep.layers), k_eff, device=tokens.device):
-            # batch 1 / 2: the dep_q steps with their samplers are one persistent launch (csrc/lm_depth.hip), on a dense [B, dep_q + 1] buffer
-            dense = tokens if tokens.shape[1] == cfg.dep_q + 1 and tokens.is_contiguous() else tokens[:, :cfg.dep_q + 1].contiguous()
-            self._tables = m.depth_frame_tables()      # a captured frame embeds the tables' device pointers: kept alive with the graph
-            ops.depth_decode_frame(self._tables, h_all, dense, noise, use_sampling=self.use_sampling, temp=self.temp, top_k=k_eff,
-                                   eps=dep.layers[0].norm1.eps, context=dep.context, limits=self._limits,
-                                   ring_cap=dep._streaming_state.k[0].shape[2])
-            if dense is not tokens:
-                tokens[:, 1:cfg.dep_q + 1] = dense[:, 1:]
-            return
-        for l_idx in range(cfg.dep_q):
-            add = h_all[:, l_idx * E:(l_idx + 1) * E]
-            table = m.codecformer_text_emb.weight if l_idx == 0 else m.codecformer_emb[l_idx - 1].weight
-            # positions 0 .. dep_q - 1 of a ring that restarts every frame, as constant device scalars (no counter to zero and bump:
-            # nine glue launches per frame); the step's input is formed inside its first launch
-            y = dep.step(None, step_index=l_idx, pos=self._depth_pos[l_idx:l_idx + 1], embed=(add, table, tokens, l_idx))
-            head = m.audio_linears[l_idx]
-            logits = ops.lm_linear(y, head.weight, bias=head.bias_f32())
-            ops.lm_sample(logits, use_sampling=self.use_sampling, temp=self.temp, top_k=k_eff,
-                          noise=None if noise is None else noise[:, l_idx * k_eff:(l_idx + 1) * k_eff],
-                          limit_dev=self._limits[l_idx:l_idx + 1], out=tokens[:, l_idx + 1])
+        # on the rings `begin` installed on the codecformer (capacity dep_q + 1, see the module docstring); this generator keeps the tables
+        m.depth_decoder.decode_frame(tokens, h, noise, self._depth_pos, use_sampling=self.use_sampling, temp=self.temp,
+                                     top_k=min(self.top_k, m.config.audio_card), limits=self._limits, keep=self)
 
     def _depth_frame(self, text_token: torch.Tensor, h: torch.Tensor, g_idx: int = 0) -> torch.Tensor:
         """dep_q depth-transformer steps + sampling: text_token int64 [B], h fp32 [B, n_embd] -> tokens int64 [B, dep_q]."""
@@ -178,11 +155,8 @@ class GPTGen:
         """``advance`` of the previous frame + ``frame`` of the next one as ONE graph replay with no host-side tensor traffic: returns
         (text [B], audio [B, dep_q]) as VIEWS of the session's token column (valid until the next ``step``; clone to keep)."""
         col, cfg = self._col, self.model.config
-        if self._frames % 64 == 0 and col.is_cuda and not self._eager:
-            ops.persistent_poll(col.device)
-            if self._persist_epoch != ops.persistent_epoch(col.device):
-                self._persist_epoch = ops.persistent_epoch(col.device)
-                self._fused = _Graphed(self._step_fn)
+        if col.is_cuda and not self._eager and self._gate.moved(self._frames):
+            self._fused = _Graphed(self._step_fn)
         self._frames += 1
         self._g_idx += 1
         self.last_h, self.last_logits = self._fused()
@@ -202,12 +176,9 @@ class GPTGen:
     def frame(self, h: torch.Tensor, logits: torch.Tensor, g_idx: int = 0):
         """(h, logits) of the last position -> (text token [B], audio tokens [B, dep_q]) of the next frame."""
         B = h.shape[0]
-        if self._frames % 64 == 0 and h.is_cuda and not self._eager:
-            # health of the persistent depth launch (csrc/persist.h): a device that had to repair frames moves to the launch-per-op chain
-            ops.persistent_poll(h.device)
-            if self._persist_epoch != ops.persistent_epoch(h.device):
-                self._persist_epoch = ops.persistent_epoch(h.device)
-                self._depth = _Graphed(self._depth_frame)
+        if h.is_cuda and not self._eager and self._gate.moved(self._frames):
+            # a device that had to repair frames of the persistent depth launch (csrc/persist.h) moves to the launch-per-op chain
+            self._depth = _Graphed(self._depth_frame)
         self._frames += 1
         k_text = min(self.top_k_text, self.model.config.padded_vocab_size)
         text = ops.lm_sample(logits, use_sampling=self.use_sampling, temp=self.temp_text, top_k=k_text,

@@ -30,11 +30,12 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..codec.conv import _PackedCache
 from ..codec.streaming import StreamingModule
 from ..graphs import Graphed as _Graphed
+from ..packed import _PackedCache
+from .depth_frame import DepthDecoder
 from .model import RMSNorm as _AlphaNorm  # noqa: F401  (key layout of the codecformer norms)
-from .model import ScaledEmbedding, StreamingTransformer, _StepState, _Weight
+from .model import ScaledEmbedding, StreamingTransformer, _StepState, _Weight, adopt_state_dict
 
 
 @dataclass
@@ -347,7 +348,10 @@ class CausalSelfAttention(nn.Module):
         fk = {"device": device, "dtype": dtype}
         self.attn = _Linear(config.n_embd, (config.n_head + 2 * config.n_query_groups) * config.head_size, config.bias, **fk)
         self.proj = _Linear(config.head_size * config.n_head, config.n_embd, config.bias, **fk)
-        self._packed = _PackedCache()
+        self._packed, self._packed_ad = _PackedCache(), _PackedCache()
+
+    def adapters_changed(self) -> None:      # new adapter tensors on `attn`: drop the kernel-side form built from the old ones
+        self._packed_ad.clear()
 
     def packed_qkv(self) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """(weight, bias) with rows in [Q | K | V] order and interleaved rotary pairs (see the module docstring)."""
@@ -366,8 +370,6 @@ class CausalSelfAttention(nn.Module):
         lin, c = self.attn, self.config
         if lin.lora_A is None:
             return None
-        if not hasattr(self, "_packed_ad"):
-            self._packed_ad = _PackedCache()
 
         def build():
             enable = (c.lora_query, c.lora_key, c.lora_value)
@@ -395,7 +397,10 @@ class LLaMAMLP(nn.Module):
         self.fc_1 = _Linear(config.n_embd, config.intermediate_size, config.bias, **fk)
         self.fc_2 = _Linear(config.n_embd, config.intermediate_size, config.bias, **fk)
         self.proj = _Linear(config.intermediate_size, config.n_embd, config.bias, **fk)
-        self._packed = _PackedCache()
+        self._packed, self._packed_ad = _PackedCache(), _PackedCache()
+
+    def adapters_changed(self) -> None:      # new adapter tensors on `fc_1` / `fc_2`: drop the kernel-side form built from the old ones
+        self._packed_ad.clear()
 
     def packed_fc(self) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         w1, w2, b1, b2 = self.fc_1.linear.weight, self.fc_2.linear.weight, self.fc_1.linear.bias, self.fc_2.linear.bias
@@ -410,8 +415,6 @@ class LLaMAMLP(nn.Module):
         l1, l2 = self.fc_1, self.fc_2
         if l1.lora_A is None and l2.lora_A is None:
             return None
-        if not hasattr(self, "_packed_ad"):
-            self._packed_ad = _PackedCache()
         present = [l for l in (l1, l2) if l.lora_A is not None]
 
         def build():
@@ -539,6 +542,9 @@ class GPT(StreamingModule[_GPTState]):
         self.codecformer.set_streaming_propagate(False)
         self.audio_linears = nn.ModuleList([_PlainLinear(config.audio_card, config.codecformer_dim, config.codecformer_bias_proj, **fk)
                                             for _ in range(config.dep_q)])
+        # the depth phase of a frame (lm.depth_frame.DepthDecoder; GPTGen._depth_into and the codecformer methods below delegate to it)
+        self.depth_decoder = DepthDecoder(self.codecformer, self.codecformer_in, [self.codecformer_text_emb, *self.codecformer_emb],
+                                          self.audio_linears)
 
     def use_fp8(self, enabled: bool = True) -> "GPT":
         """Opt into the fp8 matrix-core path for the linears of the global transformer blocks (BASELINE.json configs[4]);
@@ -627,36 +633,16 @@ class GPT(StreamingModule[_GPTState]):
 
     # ---- local (depth) transformer
     def codecformer_in_all(self) -> torch.Tensor:
-        """``[dep_q * codecformer_dim, n_embd]``: the dep_q ``codecformer_in[k]`` matrices stacked (built once per weight version),
-        so that a frame's dep_q products with ``transformer_out`` are one weight-streaming launch."""
-        if not hasattr(self, "_in_cat"):
-            from ..codec.conv import _PackedCache
-            self._in_cat = _PackedCache()
-        ws = [m.weight for m in self.codecformer_in]
-        return self._in_cat.get(tuple(ws), lambda: torch.cat([w.detach() for w in ws], 0).contiguous())
+        """``[dep_q * codecformer_dim, n_embd]``: the dep_q ``codecformer_in[k]`` matrices stacked."""
+        return self.depth_decoder.in_all()
 
     def depth_frame_tables(self):
         """Pointer tables of the persistent depth-frame launch (``lm.depth_frame.DepthFrameTables``), rebuilt when a weight changes."""
-        from ..codec.conv import _PackedCache
-        from .depth_frame import DepthFrameTables
-        if not hasattr(self, "_depth_tables"):
-            self._depth_tables = _PackedCache()
-        dep = self.codecformer
-        params = [p for l in dep.layers for p in (l.self_attn.in_proj_weight, l.self_attn.out_proj.weight, l.norm1.alpha, l.norm2.alpha)]
-        params += [g.linear_in.weight for l in dep.layers for g in l.gating] + [g.linear_out.weight for l in dep.layers for g in l.gating]
-        params += [m.weight for m in self.audio_linears] + [m.bias for m in self.audio_linears]
-        params += [self.codecformer_text_emb.weight] + [m.weight for m in self.codecformer_emb]
-        return self._depth_tables.get(tuple(params), lambda: DepthFrameTables(
-            dep, [m.weight for m in self.audio_linears], [m.bias_f32() for m in self.audio_linears],
-            [self.codecformer_text_emb.weight] + [m.weight for m in self.codecformer_emb][:self.config.dep_q - 1]))
+        return self.depth_decoder.tables()
 
     def _codec_step(self, k: int, prev: torch.Tensor, h: Optional[torch.Tensor], h_all: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One depth step: (codecformer_in[k](h) + embedding of the previous token ``prev`` int64 [N]) through the codecformer ->
-        ``[N, codecformer_dim]``; the sum is formed inside the first launch of the step.  ``h_all``: ``h @ codecformer_in_all().T``."""
-        E = self.config.codecformer_dim
-        add = h_all[:, k * E:(k + 1) * E] if h_all is not None else ops.lm_linear(h, self.codecformer_in[k].weight)
-        table = self.codecformer_text_emb.weight if k == 0 else self.codecformer_emb[k - 1].weight
-        return self.codecformer.step(None, embed=(add, table, prev.reshape(-1, 1).contiguous(), 0))
+        """One depth step up to its head: ``prev`` int64 ``[N]``, ``h`` fp32 ``[N, n_embd]`` (or ``h_all = h @ codecformer_in_all().T``) -> ``[N, codecformer_dim]``."""
+        return self.depth_decoder.step_hidden(k, prev.reshape(-1, 1).contiguous(), 0, h, h_all=h_all)
 
     def _codec_in(self, k: int, prev: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
         """codecformer_in[k](h) + embedding of the previous token (text embedding for k = 0): prev int64 [N], h fp32 [N, n_embd]."""
@@ -672,10 +658,9 @@ class GPT(StreamingModule[_GPTState]):
         assert K == 1, f"Codebooks for Depformer streaming should be passed 1 by 1, got {K}."
         assert S == 1, f"Steps for Depformer streaming should be passed 1 by 1, got {S}."
         assert transformer_out.shape[1] == 1, "Transformer out should be a for a single step."
-        k = codecformer_cb_index
-        y = self._codec_step(k, sequence.reshape(B), transformer_out.reshape(B, -1).float().contiguous())
-        head = self.audio_linears[k]
-        return ops.lm_linear(y, head.weight, bias=head.bias_f32()).view(B, 1, 1, -1)
+        logits = self.depth_decoder.step_logits(codecformer_cb_index, sequence.reshape(B, 1).contiguous(), 0,
+                                                transformer_out.reshape(B, -1).float().contiguous())
+        return logits.view(B, 1, 1, -1)
 
     @torch.no_grad()
     def forward_local(self, local_start_token: torch.Tensor, sequence: torch.Tensor, transformer_out: torch.Tensor) -> torch.Tensor:
@@ -814,22 +799,11 @@ class GPT(StreamingModule[_GPTState]):
                 raise RuntimeError(f"{name}: adapter shapes {tuple(A.shape)} / {tuple(Bm.shape)} do not fit r={c.lora_r}")
             m.set_adapter(A.to(dev), Bm.to(dev), c.lora_alpha / c.lora_r)
         for blk in self.transformer.h:      # kernel-side forms are rebuilt from the new tensors
-            blk.attn._packed_ad = _PackedCache()
-            blk.mlp._packed_ad = _PackedCache()
+            blk.attn.adapters_changed()
+            blk.mlp.adapters_changed()
 
     @classmethod
     def _from_merged(cls, sd: Dict[str, torch.Tensor], config: Config) -> "GPT":
         model = cls(config, device="meta")
-        params = dict(model.named_parameters())
-        missing = [k for k in params if k not in sd]
-        unexpected = [k for k in sd if k not in params]
-        if missing or unexpected:
-            raise RuntimeError(f"state_dict mismatch: missing={missing[:5]} unexpected={unexpected[:5]}")
-        for name, tensor in sd.items():
-            mod = model
-            *path, leaf = name.split(".")
-            for part in path:
-                mod = getattr(mod, part) if not part.isdigit() else mod[int(part)]
-            assert tuple(getattr(mod, leaf).shape) == tuple(tensor.shape), name
-            setattr(mod, leaf, nn.Parameter(tensor, requires_grad=False))
+        adopt_state_dict(model, sd)
         return model.eval()

@@ -21,9 +21,10 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..codec.conv import _PackedCache
 from ..codec.streaming import StreamingContainer, StreamingModule
-from ..graphs import Graphed as _Graphed
+from ..graphs import Graphed as _Graphed, RecaptureGate
+from ..packed import _PackedCache
+from .depth_frame import DepthDecoder
 
 
 def _gating_hidden(dim: int, dim_feedforward: int) -> int:
@@ -43,6 +44,22 @@ def _w8(mod: nn.Module, name: str = "weight") -> Optional[tuple]:
         setattr(mod, name + "_s8", None)
         return None
     return q, getattr(mod, name + "_s8")
+
+
+def adopt_state_dict(model: nn.Module, sd: Dict[str, torch.Tensor]) -> None:
+    """The tensors of ``sd`` become the parameters of ``model`` (built on the meta device) WITHOUT being copied."""
+    params = dict(model.named_parameters())
+    missing = [k for k in params if k not in sd]
+    unexpected = [k for k in sd if k not in params]
+    if missing or unexpected:
+        raise RuntimeError(f"state_dict mismatch: missing={missing[:5]} unexpected={unexpected[:5]}")
+    for name, tensor in sd.items():
+        mod = model
+        *path, leaf = name.split(".")
+        for part in path:
+            mod = getattr(mod, part) if not part.isdigit() else mod[int(part)]
+        assert tuple(getattr(mod, leaf).shape) == tuple(tensor.shape), name
+        setattr(mod, leaf, nn.Parameter(tensor, requires_grad=False))
 
 
 class _Weight(nn.Module):
@@ -304,27 +321,18 @@ class LMModel(StreamingContainer):
         self.depformer.set_streaming_propagate(False)
         self.linears = nn.ModuleList([_Weight(card, depformer_dim, **fk) for _ in range(dep_q)])
         self.config = ModelConfig(model_type="lora")
-        self._in_cat = _PackedCache()
         self._in_cat8 = _PackedCache()
-        self._depth_tables = _PackedCache()
         self.weight_dtype = "bf16"
+        # the depth phase of a frame (lm.depth_frame.DepthDecoder; LMGen._depth and the methods below delegate to it)
+        self.depth_decoder = DepthDecoder(self.depformer, self.depformer_in, [self.depformer_text_emb, *self.depformer_emb], self.linears)
 
     def depth_frame_tables(self):
         """Pointer tables of the persistent depth-frame launch (``lm.depth_frame.DepthFrameTables``), rebuilt when a weight changes."""
-        from .depth_frame import DepthFrameTables
-        dep = self.depformer
-        params = [p for l in dep.layers for p in (l.self_attn.in_proj_weight, l.self_attn.out_proj.weight, l.norm1.alpha, l.norm2.alpha)]
-        params += [g.linear_in.weight for l in dep.layers for g in l.gating] + [g.linear_out.weight for l in dep.layers for g in l.gating]
-        params += [m.weight for m in self.linears] + [self.depformer_text_emb.weight] + [m.weight for m in self.depformer_emb]
-        return self._depth_tables.get(tuple(params), lambda: DepthFrameTables(
-            dep, [m.weight for m in self.linears], [None] * self.dep_q,
-            [self.depformer_text_emb.weight] + [m.weight for m in self.depformer_emb]))
+        return self.depth_decoder.tables()
 
     def depformer_in_all(self) -> torch.Tensor:
-        """``[dep_q * depformer_dim, dim]``: the dep_q ``depformer_in[k]`` matrices stacked (a second copy, built once per weight
-        version): all of a frame's ``depformer_in[k](transformer_out)`` products are ONE weight-streaming launch."""
-        ws = [m.weight for m in self.depformer_in]
-        return self._in_cat.get(tuple(ws), lambda: torch.cat([w.detach() for w in ws], 0).contiguous())
+        """``[dep_q * depformer_dim, dim]``: the dep_q ``depformer_in[k]`` matrices stacked."""
+        return self.depth_decoder.in_all()
 
     def depformer_in_all_w8(self) -> Optional[tuple]:
         """The ``(q, scale)`` fp8 copy of ``depformer_in_all()`` of a quantised model (rows quantise independently, so stacking the
@@ -476,12 +484,8 @@ class LMModel(StreamingContainer):
                           step_index: Optional[int] = None, h_all: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Depth step ``k``: previous token = ``tokens[:, col]`` (int64 ``[B, n]``), ``h_t`` fp32 ``[B, dim]`` -> logits ``[B, card]``.
         ``h_all`` (``[B, dep_q * depformer_dim]``, the stacked ``depformer_in`` products of the frame) replaces ``h_t``."""
-        E = self.depformer.d_model
-        h = h_all[:, k * E:(k + 1) * E] if h_all is not None else ops.lm_linear(
-            h_t, self.depformer_in[k].weight, w8=_w8(self.depformer_in[k]) if self.weight_dtype == "fp8" else None)
-        table = self.depformer_text_emb.weight if k == 0 else self.depformer_emb[k - 1].weight
-        y = self.depformer.step(None, step_index=step_index, pos=pos, embed=(h, table, tokens, col))
-        return ops.lm_linear(y, self.linears[k].weight)
+        w8 = _w8(self.depformer_in[k]) if h_all is None and self.weight_dtype == "fp8" else None
+        return self.depth_decoder.step_logits(k, tokens, col, h_t, h_all=h_all, w8=w8, pos=pos, step_index=step_index)
 
     @classmethod
     def from_state_dict(cls, sd: Dict[str, torch.Tensor], cfg: dict, kv_dtype: torch.dtype = torch.bfloat16,
@@ -492,18 +496,7 @@ class LMModel(StreamingContainer):
         model = cls(kv_dtype=kv_dtype, causal=True, layer_scale=None, gating="silu", norm="rms_norm_f32", positional_embedding="rope",
                     depformer_causal=True, depformer_layer_scale=None, depformer_multi_linear=True, depformer_context=8,
                     depformer_gating="silu", depformer_pos_emb="none", depformer_weights_per_step=True, device="meta", **cfg)
-        params = dict(model.named_parameters())
-        missing = [k for k in params if k not in sd]
-        unexpected = [k for k in sd if k not in params]
-        if missing or unexpected:
-            raise RuntimeError(f"state_dict mismatch: missing={missing[:5]} unexpected={unexpected[:5]}")
-        for name, tensor in sd.items():
-            mod = model
-            *path, leaf = name.split(".")
-            for part in path:
-                mod = getattr(mod, part) if not part.isdigit() else mod[int(part)]
-            assert tuple(getattr(mod, leaf).shape) == tuple(tensor.shape), name
-            setattr(mod, leaf, nn.Parameter(tensor, requires_grad=False))
+        adopt_state_dict(model, sd)
         return model.eval().quantize_weights_(weight_dtype)
 
 
@@ -513,9 +506,9 @@ class _LMGenState:
     initial: torch.Tensor          # int64 [1, K, 1]
     offset_dev: torch.Tensor       # int64 [1]: the frame counter as the ring kernels see it
     graphed_frame: _Graphed
+    gate: RecaptureGate                    # whether the device's persistent launches were retired since the frame graph was captured
     depth: Optional[_StepState] = None     # the depth transformer's KV rings of THIS session (a captured frame points at them)
     offset: int = 0
-    persist_epoch: int = 0                 # ops.persistent_epoch(device) when the frame graph was captured
     tables: object = None                  # the DepthFrameTables the captured frame points at (kept alive with the graph)
     temporal_base: Optional[int] = None    # host-side position of the temporal rings at frame 0 of this session
     temporal_choice: Optional[bool] = None  # whether the captured frame takes the persistent temporal launch
@@ -549,8 +542,8 @@ class LMGen(StreamingModule[_LMGenState]):
                            dtype=torch.long)
         disable = lm.device.type != "cuda"
         return _LMGenState(cache, lm._get_initial_token(), torch.zeros(1, device=lm.device, dtype=torch.long),
-                           _Graphed(self._frame, disable=disable), depth=lm.depformer._init_streaming_state(batch_size),
-                           persist_epoch=ops.persistent_epoch(lm.device))
+                           _Graphed(self._frame, disable=disable), RecaptureGate(lm.device),
+                           depth=lm.depformer._init_streaming_state(batch_size))
 
     def _noise(self, B: int, k: int) -> Optional[torch.Tensor]:
         if not self.use_sampling:
@@ -579,35 +572,13 @@ class LMGen(StreamingModule[_LMGenState]):
         step ``cb`` embeds ``tokens[:, cb]`` and samples ``tokens[:, cb + 1]`` in place.  The depth KV rings are persistent
         buffers; the steps are positions 0 .. dep_q - 1 of a ring that restarts every frame (= the reference's fresh
         ``with depformer.streaming(B)`` context), supplied as constant device scalars instead of a counter to reset and bump."""
-        B = tokens.shape[0]
-        lm = self.lm_model
-        dep = lm.depformer
-        # the rings belong to the session (so that a frame graph captured by another live session keeps valid pointers and
+        B, lm, state = tokens.shape[0], self.lm_model, self._streaming_state
+        # the chain's rings belong to the session (so that a frame graph captured by another live session keeps valid pointers and
         # exiting `streaming()` releases them); a bare `depformer_step` call outside any session gets throw-away rings
-        # depformer_in[k](transformer_out) for all dep_q steps at once: one 8 x larger launch instead of eight
-        h_all = ops.lm_linear(h_t, lm.depformer_in_all(), w8=lm.depformer_in_all_w8())
-        E, H = dep.d_model, dep.num_heads
-        Hd = dep.layers[0].gating[0].linear_out.weight.shape[1]
-        if ops.depth_frame_enabled(h_t.device) and h_t.is_cuda and ops.depth_frame_supported(B, E, H, Hd, lm.card, lm.dep_q, len(dep.layers), self.top_k, device=h_t.device):
-            # batch 1 / 2: the whole phase (dep_q x (L layers + head + sampler)) is ONE persistent launch whose ops hand their
-            # vectors over in-kernel; the depth KV ring lives in its LDS
-            tables = lm.depth_frame_tables()
-            if self._streaming_state is not None:
-                self._streaming_state.tables = tables       # a captured frame embeds the tables' device pointers: they live as long as it does
-            ops.depth_decode_frame(tables, h_all, tokens, noise, use_sampling=self.use_sampling, temp=self.temp,
-                                   top_k=self.top_k, eps=dep.layers[0].norm1.eps, context=dep.context)
-            return
-        state = self._streaming_state
-        rings = state.depth if state is not None and state.depth is not None and state.depth.k[0].shape[0] == B \
-            else dep._init_streaming_state(B)
-        saved, dep._streaming_state = dep._streaming_state, rings
-        try:
-            for cb in range(lm.dep_q):
-                logits = lm._depformer_logits(cb, tokens, cb, None, pos=self._depth_pos[cb:cb + 1], step_index=cb, h_all=h_all)
-                ops.lm_sample(logits, use_sampling=self.use_sampling, temp=self.temp, top_k=self.top_k,
-                              noise=None if noise is None else noise[:, cb * self.top_k:(cb + 1) * self.top_k], out=tokens[:, cb + 1])
-        finally:
-            dep._streaming_state = saved
+        mine = state is not None and state.depth is not None and state.depth.k[0].shape[0] == B
+        lm.depth_decoder.decode_frame(
+            tokens, h_t, noise, self._depth_pos, use_sampling=self.use_sampling, temp=self.temp, top_k=self.top_k, keep=state,
+            rings=state.depth if mine else lm.depformer._init_streaming_state, w8=lm.depformer_in_all_w8(), persistent=h_t.is_cuda)
 
     @torch.no_grad()
     def step(self, input_tokens: torch.Tensor) -> Optional[torch.Tensor]:
@@ -620,13 +591,9 @@ class LMGen(StreamingModule[_LMGenState]):
         assert S == 1, "Only support being given steps one by one."
         needed = lm.num_codebooks - lm.dep_q - 1
         assert Ki == needed, f"We expect {needed} tokens from the user stream, got {Ki}."
-        if state.offset % 64 == 0 and lm.device.type == "cuda":
-            # health of the persistent depth launch (no synchronisation): a device that had to repair frames moves to the
-            # launch-per-op chain, which needs a fresh capture
-            ops.persistent_poll(lm.device)
-            if state.persist_epoch != ops.persistent_epoch(lm.device):
-                state.persist_epoch = ops.persistent_epoch(lm.device)
-                state.graphed_frame = _Graphed(self._frame)
+        if lm.device.type == "cuda" and state.gate.moved(state.offset):
+            # a device that had to repair frames moves to the launch-per-op chain, which needs a fresh capture
+            state.graphed_frame = _Graphed(self._frame)
         tst = lm.transformer._streaming_state
         if tst is not None:
             # the temporal rings' fill as the host knows it (graph replays do not run the Python that counts steps): the persistent
@@ -645,8 +612,7 @@ class LMGen(StreamingModule[_LMGenState]):
         if tst is not None:
             tst.offset_cpu = state.temporal_base + state.offset + 1
         if self.check:
-            if lm._depth_tables._val is not None:
-                lm._depth_tables._val.check()       # a timed-out hand-off of the persistent depth launch
+            lm.depth_decoder.check()       # a timed-out hand-off of the persistent depth launch
             assert not (input_ == lm.ungenerated_token_id).any(), (state.offset, input_)
             assert (input_[:, lm.audio_offset:] <= lm.card).all(), input_
             assert (input_[:, :1] <= lm.text_card).all()

@@ -12,6 +12,7 @@ from typing import Optional
 import torch
 
 from .codec.mimi import MimiCodec
+from .graphs import Graphed, RecaptureGate
 from .lm.model import LMGen
 
 
@@ -24,7 +25,7 @@ class StreamingPipeline:
         self._dec = None
         from . import ops
         self.fuse = bool(ops.PIPELINE_FUSE)     # one graph per frame once the delay line is full (False: the three module calls, as the reference loops)
-        self._fused, self._fused_epoch = None, -1
+        self._fused, self._gate = None, None
         self.last_codes: Optional[torch.Tensor] = None      # what the encoder emitted for the last frame, [B, K, 1] (valid until the next step)
 
     def __enter__(self):
@@ -33,7 +34,8 @@ class StreamingPipeline:
         self._mimi_ctx.__enter__()
         self._lm_ctx = self.lm_gen.streaming(self.batch_size)
         self._lm_ctx.__enter__()
-        self._fused, self._fused_epoch, self.last_codes = None, -1, None     # a graph of an earlier session points at that session's states
+        self._fused, self.last_codes = None, None     # a graph of an earlier session points at that session's states
+        self._gate = RecaptureGate(self.lm_gen.lm_model.device, every_frame=True)
         return self
 
     def __exit__(self, *exc):
@@ -66,16 +68,11 @@ class StreamingPipeline:
         fused_ok = (self.fuse and pcm.is_cuda and state is not None and state.offset >= gen.max_delay + 2 and not gen.check
                     and self.mimi.code_layout == "bkt")
         if fused_ok:
-            from . import ops
-            from .graphs import Graphed
-            if state.offset % 64 == 0:
-                ops.persistent_poll(pcm.device)
-            epoch = ops.persistent_epoch(pcm.device)
-            if self._fused is None or self._fused_epoch != epoch:
+            if self._gate.moved(state.offset) or self._fused is None:
                 # the first capture follows the modules' own eager frames (the delay line: max_delay + 2 of them).  A RE-capture after the
                 # device's persistent launches were retired takes launch-per-op paths that have not run in this session yet: one eager
                 # frame first, so that their lazily created state and scratch exist before the capture
-                self._fused, self._fused_epoch = Graphed(self._frame_fn, warmup=0 if self._fused is None else 1), epoch
+                self._fused = Graphed(self._frame_fn, warmup=0 if self._fused is None else 1)
             if not self._fused.disable:
                 wav = self._fused(pcm.contiguous())
                 state.offset += 1
