@@ -498,6 +498,28 @@ int rst_lm_attn_decode_f32(const float* qkv, void* k, void* v, float* ws, uint32
                            float rope_coef, int kv_heads, int rope_dims, uint16_t* out_packed, int kv_bf16, const float* rope_table,
                            rst_stream_t stream);
 
+/* Multi-position (prefill) attention of the LM temporal transformer: Tc new positions of B streams against the ring plus the chunk
+ * itself, BEFORE anything is appended.  qkv [B][Tc][ldqkv] = [q | k | v] (H heads each, un-rotated in-projection output); rings k, v
+ * [B][H][cap][D] fp32, or bf16 when kv_bf16; *pos_dev = position of the chunk's first row.  The query at position p sees the keys j with
+ * max(0, p - window + 1) <= j <= p: positions < *pos_dev from ring slot j % cap, positions >= *pos_dev from qkv, rotated (interleaved
+ * RoPE, angle_i = exp(i * rope_coef) * position, rope_dims 0 -> D) and ROUNDED TO THE RING'S DTYPE, i.e. the bytes rst_lm_ring_append
+ * stores.  rope_freqs (device, may be NULL): the rope_dims / 2 fp32 frequencies exp(i * rope_coef) as the caller's reference evaluates them --
+ * a frequency one ulp off moves a key at position 3000 by 2e-4 of its magnitude; NULL: the correctly rounded fp32 value, evaluated by the
+ * kernel.  out [B*Tc][H*D].  D in {64, 128}, Tc <= cap, 1 <= window <= cap, any *pos_dev (empty, partly filled, wrapped ring).
+ * bf16 rings run on v_mfma_f32_32x32x16_bf16 (online softmax over 32-key tiles; rotated queries and probabilities enter as bf16 hi + lo
+ * pairs, ring keys / values exactly; fp32 accumulation and softmax); fp32 rings on plain fp32 FMAs.
+ * workspace: rst_lm_attn_prefill_workspace_bytes(B, Tc, H, D, kv_bf16) bytes (-1: too large), 16-byte aligned (rotated queries and the
+ * chunk's keys / values in the ring's dtype).
+ * rst_lm_ring_append runs AFTER it in stream order: rotates the chunk's keys as above and writes k, v to slots (*pos_dev + t) % cap in
+ * the ring's dtype.  (Slot (pos + t) % cap holds position pos + t - cap, which the chunk's first queries still read once the ring has
+ * wrapped: appending inside the attention launch would race.) */
+int rst_lm_attn_prefill_workspace_bytes(int B, int Tc, int H, int D, int kv_bf16);
+int rst_lm_attn_prefill_f32(const float* qkv, const void* k, const void* v, void* workspace, int64_t workspace_bytes, float* out,
+                            const int64_t* pos_dev, int B, int Tc, int H, int D, int cap, int window, int ldqkv, int rope,
+                            float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream);
+int rst_lm_ring_append(const float* qkv, void* k, void* v, const int64_t* pos_dev, int B, int Tc, int H, int D, int cap, int ldqkv, int rope,
+                       float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream);
+
 /* The few-query form of rst_attention_f32(ring = 1) for streaming steps of the codec transformers (T <= a few new steps per
  * call): q [B][H][T][D] already rotated and k / v already appended by rst_rope_split_f32; every (b, t, h) query is split
  * over the occupied ring slots like rst_lm_attn_decode_f32 (same mask / slot map with end_offset = *pos_dev + T).

@@ -3,11 +3,11 @@ RQ-Transformer: a temporal transformer over 17 token streams + a per-codebook de
 
 Same constructor keywords, ``state_dict`` keys (``emb.{i}.weight``, ``transformer.layers.{l}.self_attn.in_proj_weight``,
 ``...gating.linear_in.weight``, ``depformer.layers.{l}.gating.{k}.linear_out.weight``, ``linears.{k}.weight`` ...),
-``forward_text`` / ``forward_depformer`` signatures and ``LMGen.step`` semantics (delayed token ring cache, ``None`` for
-the first ``max_delay`` steps).  Training ``forward`` is out of scope.
+``forward`` / ``forward_local`` / ``forward_text`` / ``forward_depformer`` signatures and ``LMGen.step`` semantics (delayed token ring
+cache, ``None`` for the first ``max_delay`` steps); ``LMGen.prefill`` takes in frames that already exist.  Inference only: no autograd.
 
 Execution: weights bf16 in HBM, activations fp32, one decode step (T = 1) per call through the kernels of
-``csrc/lm_*.hip``; a whole ``LMGen`` frame (token-ring update, ``forward_text``, the depth steps with their samplers, ring
+``csrc/lm_*.hip`` -- or T positions per call through ``StreamingTransformer.run`` (``csrc/lm_prefill.hip``); a whole ``LMGen`` frame (token-ring update, ``forward_text``, the depth steps with their samplers, ring
 commit) is captured into ONE HIP graph after a warm-up -- the reference wraps ``forward_text`` and ``depformer_step`` in two
 ``CUDAGraphed`` wrappers (``MLLM_v2/utils/compile.py:189-277``) and does the ring arithmetic on the host in between -- and the
 environment flag ``NO_CUDA_GRAPH`` disables that (``compile.py:168-174``).
@@ -25,6 +25,10 @@ from ..codec.streaming import StreamingContainer, StreamingModule
 from ..graphs import Graphed as _Graphed, RecaptureGate
 from ..packed import _PackedCache
 from .depth_frame import DepthDecoder
+
+
+# positions per launch chain of the multi-position pass (StreamingTransformer.run); a chunk is also never longer than the ring
+PREFILL_CHUNK = 256
 
 
 def _gating_hidden(dim: int, dim_feedforward: int) -> int:
@@ -248,6 +252,47 @@ class StreamingTransformer(StreamingModule[_StepState]):
             st.offset_cpu += 1
         return x
 
+    def window(self, cap: int) -> int:
+        """Keys a query sees on a ring of ``cap`` slots, itself included: the context, and never more than ``cap - 1`` because
+        ``RingKVCache.complete`` hides the oldest slot of a full ring -- exactly what single steps see."""
+        return min(self.context, cap - 1) if self.context else cap - 1
+
+    def run(self, x: torch.Tensor, B: int, T: int) -> torch.Tensor:
+        """x fp32 ``[B*T, d_model]`` (row ``b*T + t``) -> ``[B*T, d_model]``: ``T`` new positions per stream through every layer, equal to
+        the same positions fed to ``step`` one at a time.  Per chunk of ``PREFILL_CHUNK`` positions and layer: in-projection with the
+        RMSNorm prologue | prefill attention against the ring plus the chunk | ring append | out-projection | gated MLP; the linears
+        stream their weights once per 64 rows.  Advances the position counters by ``T``.  ``T == 1`` is ``step``."""
+        st = self._streaming_state
+        if st is None:
+            raise RuntimeError("the decode-step transformer only runs in streaming mode")
+        if self.weights_per_step:
+            raise NotImplementedError("run() serves the temporal transformer; per-step-weights (depth) transformers advance by `step`")
+        if T == 1:
+            return self.step(x)
+        E = self.d_model
+        assert x.shape == (B * T, E), (tuple(x.shape), B, T, E)
+        cap = st.k[0].shape[2]
+        window = self.window(cap)
+        q8 = self.weight_dtype == "fp8"
+        xv = x.view(B, T, E)
+        y = torch.empty_like(xv)
+        for t0 in range(0, T, min(PREFILL_CHUNK, cap)):
+            Tc = min(PREFILL_CHUNK, cap, T - t0)
+            h = xv[:, t0:t0 + Tc].reshape(B * Tc, E)
+            for l, layer in enumerate(self.layers):
+                att, gate = layer.self_attn, layer.gating
+                qkv = ops.lm_linear(h, att.in_proj_weight, prologue=ops.PROLOGUE_RMSNORM, alpha=layer.norm1.alpha_f32(), eps=layer.norm1.eps,
+                                    w8=_w8(att, "in_proj_weight") if q8 else None).view(B, Tc, 3 * E)
+                a = ops.lm_attn_prefill(qkv, st.k[l], st.v[l], st.pos, window=window, rope=self.rope, max_period=self.max_period)
+                # after the attention, in stream order: the slot of position pos + t still held position pos + t - cap
+                ops.lm_ring_append(qkv, st.k[l], st.v[l], st.pos, rope=self.rope, max_period=self.max_period)
+                h = ops.lm_linear(a, att.out_proj.weight, res=h, w8=_w8(att.out_proj) if q8 else None)
+                h = ops.lm_gated_pair(h, gate.linear_in.weight, gate.linear_out.weight, alpha=layer.norm2.alpha_f32(), eps=layer.norm2.eps,
+                                      res=h, w8_in=_w8(gate.linear_in) if q8 else None, w8_out=_w8(gate.linear_out) if q8 else None)
+            y[:, t0:t0 + Tc] = h.view(B, Tc, E)
+            st.pos.add_(Tc)
+            st.offset_cpu += Tc
+        return y.view(B * T, E)
 
     def _persistent_step(self, st: _StepState, x: torch.Tensor, pos_t: torch.Tensor, cap: int) -> Optional[torch.Tensor]:
         """All layers of a batch-1 step as ONE persistent launch (csrc/lm_temporal.hip) when the library serves the shape and the
@@ -453,22 +498,75 @@ class LMModel(StreamingContainer):
         tok[:, 0] = self.text_initial_token_id
         return tok
 
+    @torch.no_grad()
     def forward(self, sequence: torch.Tensor, masks: Optional[torch.Tensor] = None):
-        raise NotImplementedError("teacher-forced training forward is out of scope; use forward_text / forward_depformer")
+        """models/model.py:297-319 (inference only; ``masks`` is unused there too): sequence int64 ``[B, n_q+1, S]`` -> (audio_logits fp32
+        ``[B,S,dep_q,card]``, text_logits fp32 ``[B,S,V]``).  The global input is the sequence shifted right behind the initial frame;
+        its text ids give the local start token and its first ``dep_q`` audio rows the local sequence."""
+        B, K, S = sequence.shape
+        shifted = torch.cat([self._get_initial_token().repeat(B, 1, 1), sequence[:, :, :-1]], dim=2)
+        transformer_out, text_logits = self.forward_text(shifted)
+        audio_logits = self.forward_local(shifted[:, 0, :], shifted[:, 1:self.dep_q + 1, :], transformer_out)
+        return audio_logits, text_logits.squeeze(1)
 
-    # ---- decode step
+    @torch.no_grad()
+    def forward_local(self, local_start_token: torch.Tensor, sequence: torch.Tensor, transformer_out: torch.Tensor) -> torch.Tensor:
+        """Teacher-forced depth logits (models/model.py:321-362).  ``local_start_token``: the ``depformer_text_emb`` embedding of the
+        text ids, float ``[B,T,depformer_dim]`` as in the reference, or the int64 ids ``[B,T]`` themselves; ``sequence`` int64
+        ``[B,dep_q,T]``, ``transformer_out`` fp32 ``[B,T,dim]`` -> ``[B,T,dep_q,card]``.  ``dep_q`` depth steps over ``B*T`` rows on a
+        ring of capacity ``dep_q + 1`` (the non-streaming reference path has no ring, hence no Q1 slot quirk at the last codebook)."""
+        B, K, T = sequence.shape
+        assert K == self.dep_q, f"Sequence shape {sequence.shape} must match the moshi stream output."
+        dep, N = self.depformer, B * T
+        saved = dep._streaming_state
+        dep._streaming_state = dep._init_streaming_state(N, capacity=self.dep_q + 1)
+        try:
+            h = transformer_out.reshape(N, -1).float().contiguous()
+            outs = []
+            for k in range(K):
+                w = self.depformer_in[k].weight
+                if k == 0 and local_start_token.dtype != torch.long:
+                    x = ops.lm_linear(h, w, res=local_start_token.reshape(N, -1).float().contiguous())
+                else:
+                    prev = local_start_token if k == 0 else sequence[:, k - 1]
+                    table = self.depformer_text_emb.weight if k == 0 else self.depformer_emb[k - 1].weight
+                    x = ops.embed_sum(prev.reshape(N, 1).contiguous(), [table], [0], add=ops.lm_linear(h, w))
+                y = dep.step(x)
+                outs.append(ops.lm_linear(y, self.linears[k].weight).view(B, T, 1, -1))
+        finally:
+            dep._streaming_state = saved
+        return torch.cat(outs, dim=2)
+
+    # ---- decode step / multi-position pass
     def forward_text(self, sequence: torch.Tensor, masks: Optional[torch.Tensor] = None):
-        """sequence int64 ``[B, n_q+1, 1]`` -> (transformer_out fp32 ``[B,1,dim]``, text_logits fp32 ``[B,1,1,V]``)."""
+        """sequence int64 ``[B, n_q+1, S]`` -> (transformer_out fp32 ``[B,S,dim]``, text_logits fp32 ``[B,1,S,V]``).  ``S == 1``: one
+        decode step.  ``S > 1`` inside ``streaming()``: the S positions that follow the ones already streamed, equal to S single steps
+        (window ``min(context, capacity - 1)``); outside it: positions 0 .. S-1 under the plain causal + context mask of the
+        reference's non-streaming pass (models/model.py:364-389), on throw-away rings of capacity ``S + 1``."""
         B, K, S = sequence.shape
         assert K == self.num_codebooks, f"Sequence shape {sequence.shape} must match the number of codebooks."
-        assert S == 1, "the streaming decode path takes one step at a time"
-        toks = sequence.reshape(B, K).contiguous()
         tables = [e.weight for e in self.emb] + [self.text_emb.weight]
-        x = ops.embed_sum(toks, tables, list(range(1, K)) + [0])     # ((e_0 + e_1) + ...) + text, as the reference
-        x = self.transformer.step(x)
+        w8 = _w8(self.text_linear) if self.weight_dtype == "fp8" else None
+        if S == 1:
+            toks = sequence.reshape(B, K).contiguous()
+            x = ops.embed_sum(toks, tables, list(range(1, K)) + [0])     # ((e_0 + e_1) + ...) + text, as the reference
+            x = self.transformer.step(x)
+            out = ops.rmsnorm(x, self.out_norm.alpha_f32(), self.out_norm.eps)
+            logits = ops.lm_linear(out, self.text_linear.weight, w8=w8)
+            return out.view(B, 1, self.dim), logits.view(B, 1, 1, -1)
+        toks = sequence.permute(0, 2, 1).reshape(B * S, K).contiguous()
+        x = ops.embed_sum(toks, tables, list(range(1, K)) + [0])
+        tr = self.transformer
+        saved = tr._streaming_state
+        if saved is None:
+            tr._streaming_state = tr._init_streaming_state(B, capacity=S + 1)
+        try:
+            x = tr.run(x, B, S)
+        finally:
+            tr._streaming_state = saved
         out = ops.rmsnorm(x, self.out_norm.alpha_f32(), self.out_norm.eps)
-        logits = ops.lm_linear(out, self.text_linear.weight, w8=_w8(self.text_linear) if self.weight_dtype == "fp8" else None)
-        return out.view(B, 1, self.dim), logits.view(B, 1, 1, -1)
+        logits = ops.lm_linear(out, self.text_linear.weight, w8=w8)
+        return out.view(B, S, self.dim), logits.view(B, 1, S, -1)
 
     def forward_depformer(self, depformer_cb_index: int, sequence: torch.Tensor, transformer_out: torch.Tensor) -> torch.Tensor:
         """sequence int64 ``[B,1,1]`` (previous token), transformer_out fp32 ``[B,1,dim]`` -> logits fp32 ``[B,1,1,card]``."""
@@ -498,6 +596,39 @@ class LMModel(StreamingContainer):
                     depformer_gating="silu", depformer_pos_emb="none", depformer_weights_per_step=True, device="meta", **cfg)
         adopt_state_dict(model, sd)
         return model.eval().quantize_weights_(weight_dtype)
+
+
+def prefill_token_plan(cache: torch.Tensor, offset: int, user: torch.Tensor, own: torch.Tensor, delays: List[int], initial: torch.Tensor):
+    """The token bookkeeping of ``T`` teacher-forced ``LMGen.step`` frames at once (models/model.py:506-521, 545-562), as a pure function
+    built from torch indexing (CPU or device tensors): token ring ``cache`` int64 ``[B, K, CT]`` at frame ``offset``, ``user`` ``[B, Ki, T]``,
+    ``own`` ``[B, n_own, T]`` (the tokens frame t would have sampled), ``delays`` (K ints), ``initial`` int64 ``[K]`` -> (the model input
+    columns ``[B, K, T]``, the ring after the T frames).
+
+    Frame t (o = offset + t) writes user stream k at column o + delay_k, the initial token at column o while o <= delay_k, reads column
+    o, then writes ``own[:, :, t]`` at column o + 1.  A column is never more than ``max_delay + 1`` ahead of the frame that writes it, so
+    on the UNROLLED axis j = column - offset every write has its own place, later frames write later columns, and the ring ends up
+    holding, per stream and slot, the last written column that maps to the slot."""
+    B, K, CT = cache.shape
+    Ki, T, n_own = user.shape[1], user.shape[2], own.shape[1]
+    assert Ki + n_own == K and len(delays) == K and own.shape[2] == T and max(delays) + 2 <= CT
+    dev = cache.device
+    j = torch.arange(T + CT, device=dev)
+    line = cache[:, :, (offset + j) % CT]                    # columns offset .. offset + T + CT - 1 (j < CT: what the ring holds now)
+    line[:, :n_own, 1:T + 1] = own
+    for q in range(Ki):
+        k = n_own + q
+        line[:, k, delays[k]:delays[k] + T] = user[:, q]
+    for k, d in enumerate(delays):                           # the initial token wins: it is written by the frame that reads the column
+        n = min(T, d - offset + 1)
+        if n > 0:
+            line[:, k, :n] = initial[k]
+    # last written column per stream (own streams: offset + T; user streams: offset + T - 1 + delay), and from it the newest column
+    # of every slot; a slot whose newest column lies before `offset` was not written and keeps its entry
+    last = torch.tensor([T if k < n_own else T - 1 + d for k, d in enumerate(delays)], device=dev).view(K, 1)
+    slot = torch.arange(CT, device=dev).view(1, CT)
+    newest = last - (offset + last - slot) % CT
+    ring = torch.where((newest >= 0).unsqueeze(0), line.gather(2, newest.clamp(min=0).unsqueeze(0).expand(B, K, CT)), cache)
+    return line[:, :, :T], ring
 
 
 @dataclass
@@ -620,6 +751,54 @@ class LMGen(StreamingModule[_LMGenState]):
         if state.offset <= self.max_delay:
             return None
         return out.view(B, lm.dep_q + 1, 1).clone()
+
+    def model_time(self, outputs: torch.Tensor) -> torch.Tensor:
+        """The delay-aligned stream ``step`` returns, ``[B, dep_q + 1, A]`` (A consecutive frames from the first non-None one), as
+        model-time frames for ``prefill``: ``model[k][t] = aligned[k][t - delay_k]`` for ``t >= delay_k``; the earlier entries are never
+        read (``step`` overwrites their ring columns with the initial token) and hold the initial token."""
+        lm = self.lm_model
+        B, n, A = outputs.shape
+        assert n == lm.dep_q + 1, f"We expect {lm.dep_q + 1} generated streams, got {n}."
+        own = lm._get_initial_token().to(outputs.device)[:, :n].repeat(B, 1, A)
+        for k, d in enumerate(lm.delays[:n]):
+            if d < A:
+                own[:, k, d:] = outputs[:, k, :A - d]
+        return own
+
+    @torch.no_grad()
+    def prefill(self, user_tokens: torch.Tensor, own_tokens: torch.Tensor) -> None:
+        """Takes in ``T`` frames that already exist: equal to ``T`` calls of ``step(user_tokens[..., t:t+1])`` in which the tokens frame
+        ``t`` sampled (text, then ``dep_q`` audio, in model time: what ``step`` writes to the token ring at ``offset + 1``) are replaced
+        by ``own_tokens[..., t]``.  user_tokens int64 ``[B, Ki, T]``, own_tokens int64 ``[B, dep_q + 1, T]`` (``model_time`` builds it
+        from recorded ``step`` outputs).  The depth transformer, the output norm and the text head never run; the temporal pass is one
+        ``StreamingTransformer.run``.  Works at any session offset; a captured frame graph stays valid (it reads positions from device
+        scalars)."""
+        state = self._streaming_state
+        if state is None:
+            raise RuntimeError("You should wrap those calls with a `with lm_gen.streaming(): ...`.")
+        lm = self.lm_model
+        assert user_tokens.dim() == 3 and own_tokens.dim() == 3, "Shape should be [B, K, T]."
+        B, Ki, T = user_tokens.shape
+        needed = lm.num_codebooks - lm.dep_q - 1
+        assert Ki == needed, f"We expect {needed} tokens from the user stream, got {Ki}."
+        assert own_tokens.shape == (B, lm.dep_q + 1, T), f"We expect own tokens [{B}, {lm.dep_q + 1}, {T}], got {tuple(own_tokens.shape)}."
+        if T == 0:
+            return
+        tst = lm.transformer._streaming_state
+        if tst is None:
+            raise RuntimeError("LMGen.prefill needs the model's streaming state: open `lm_gen.streaming()` (it propagates to the model)")
+        if state.temporal_base is None:
+            state.temporal_base = tst.offset_cpu - state.offset
+        tst.offset_cpu = state.temporal_base + state.offset      # (graph replays of `step` do not run the Python that counts steps)
+        inputs, ring = prefill_token_plan(state.cache, state.offset, user_tokens.to(state.cache.device), own_tokens.to(state.cache.device),
+                                          lm.delays, state.initial.reshape(-1))
+        K = lm.num_codebooks
+        toks = inputs.permute(0, 2, 1).reshape(B * T, K).contiguous()
+        tables = [e.weight for e in lm.emb] + [lm.text_emb.weight]
+        lm.transformer.run(ops.embed_sum(toks, tables, list(range(1, K)) + [0]), B, T)      # advances pos / offset_cpu by T
+        state.cache.copy_(ring)
+        state.offset += T
+        state.offset_dev.add_(T)
 
     def depformer_step(self, text_token: torch.Tensor, transformer_out: torch.Tensor) -> torch.Tensor:
         """text_token int64 ``[B]``, transformer_out fp32 ``[B, 1, dim]`` -> the frame's ``dep_q`` audio tokens ``[B, dep_q]``

@@ -1251,6 +1251,65 @@ def lm_attn_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     return PackedAct(xp, B, H * D) if packed else out
 
 
+_prefill_ws: dict = {}
+_rope_freq_tables: dict = {}
+
+
+def _rope_freqs(device, max_period: float, n: int) -> torch.Tensor:
+    """The reference's frequency table ``exp(arange(n / 2) * (-ln(max_period) * 2 / n))`` (modules/rope.py:37-38) evaluated as the
+    reference writes it, by torch in fp32, once per (device, max_period, n).  The prefill kernels multiply it by positions in the
+    thousands, where one ulp of a frequency is 2e-4 rad: the table keeps the stored keys on the reference's angles."""
+    key = (device, float(max_period), n)
+    tab = _rope_freq_tables.get(key)
+    if tab is None:
+        ds = torch.arange(n // 2, dtype=torch.float32)
+        tab = _rope_freq_tables[key] = torch.exp(ds * (-math.log(max_period) * 2 / n)).to(device)
+    return tab
+
+
+def _prefill_args(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos_dev: torch.Tensor):
+    _chk(qkv, "qkv")
+    kv16 = k_cache.dtype == torch.bfloat16
+    _chk(k_cache, "k_cache", k_cache.dtype if kv16 else torch.float32)
+    _chk(v_cache, "v_cache", k_cache.dtype)
+    _chk(pos_dev, "pos_dev", torch.int64)
+    B, H, cap, D = k_cache.shape
+    assert qkv.dim() == 3 and qkv.shape[0] == B and qkv.shape[2] == 3 * H * D, (tuple(qkv.shape), B, H, D)
+    assert v_cache.shape == k_cache.shape
+    return B, qkv.shape[1], H, D, cap, kv16
+
+
+@_on_tensor_device
+def lm_attn_prefill(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos_dev: torch.Tensor, *, window: int,
+                    rope: bool, max_period: float = 10000.0, rope_dims: int = 0) -> torch.Tensor:
+    """Attention of ``Tc`` new positions given their in-projection ``qkv [B, Tc, 3*H*D]`` against the ring ``[B,H,cap,D]`` (bf16 or
+    fp32) plus the chunk itself, BEFORE anything is appended -> ``[B*Tc, H*D]``.  The query at position ``p`` (``pos_dev`` = position of
+    row 0) sees keys ``max(0, p - window + 1) .. p``; the chunk's own keys / values take part rounded to the ring's dtype.  Follow with
+    ``lm_ring_append`` (rst_lm_attn_prefill_f32; head dim 64 / 128, ``Tc <= cap``, ``1 <= window <= cap``)."""
+    B, Tc, H, D, cap, kv16 = _prefill_args(qkv, k_cache, v_cache, pos_dev)
+    nbytes = int(_lib.lib().rst_lm_attn_prefill_workspace_bytes(B, Tc, H, D, int(kv16)))
+    if nbytes <= 0:
+        raise ValueError(f"rstnet_amd.ops: lm_attn_prefill workspace for B={B} Tc={Tc} H={H} D={D} is not addressable")
+    ws = _scratch(_prefill_ws, qkv.device, ("prefill", nbytes), lambda: torch.empty((nbytes + 7) // 8, device=qkv.device, dtype=torch.int64))
+    out = torch.empty(B * Tc, H * D, device=qkv.device, dtype=torch.float32)
+    _lib.check(_lib.lib().rst_lm_attn_prefill_f32(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(ws), nbytes, _ptr(out), _ptr(pos_dev),
+                                                 B, Tc, H, D, cap, int(window), qkv.shape[2], int(rope),
+                                                 rope_coef(max_period, rope_dims or D), rope_dims, int(kv16),
+                                                 _ptr(_rope_freqs(qkv.device, max_period, rope_dims or D)) if rope else None, _stream()))
+    return out
+
+
+@_on_tensor_device
+def lm_ring_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos_dev: torch.Tensor, *, rope: bool,
+                   max_period: float = 10000.0, rope_dims: int = 0) -> None:
+    """The append that follows ``lm_attn_prefill`` in stream order: the ``Tc`` keys of ``qkv [B, Tc, 3*H*D]`` rotated at positions
+    ``pos_dev + t``, and the values, into ring slots ``(pos_dev + t) % cap`` in the ring's dtype (rst_lm_ring_append)."""
+    B, Tc, H, D, cap, kv16 = _prefill_args(qkv, k_cache, v_cache, pos_dev)
+    _lib.check(_lib.lib().rst_lm_ring_append(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(pos_dev), B, Tc, H, D, cap, qkv.shape[2],
+                                            int(rope), rope_coef(max_period, rope_dims or D), rope_dims, int(kv16),
+                                            _ptr(_rope_freqs(qkv.device, max_period, rope_dims or D)) if rope else None, _stream()))
+
+
 _sample_ws: dict = {}
 
 
