@@ -520,6 +520,17 @@ int rst_lm_attn_prefill_f32(const float* qkv, const void* k, const void* v, void
 int rst_lm_ring_append(const float* qkv, void* k, void* v, const int64_t* pos_dev, int B, int Tc, int H, int D, int cap, int ldqkv, int rope,
                        float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream);
 
+/* The same three calls with grouped key/value heads (the litgpt-style GPT): G = kv heads, H % G == 0.  The qkv row is
+ * [q: H*D | k: G*D | v: G*D] (ldqkv >= (H + 2G) * D, the layout of rst_lm_rope_append_f32), rings k, v are [B][G][cap][D], and query head h
+ * reads kv head h / (H / G).  Workspace: B*Tc*H*D*4 + 2*B*Tc*G*D*(2 | 4) bytes.  Everything else -- rotation, rounding of the chunk's
+ * keys / values to the ring's dtype, window rule, online softmax, refusals -- is as above; G == H runs the very same launches. */
+int rst_lm_attn_prefill_gqa_workspace_bytes(int B, int Tc, int H, int G, int D, int kv_bf16);
+int rst_lm_attn_prefill_gqa_f32(const float* qkv, const void* k, const void* v, void* workspace, int64_t workspace_bytes, float* out,
+                                const int64_t* pos_dev, int B, int Tc, int H, int G, int D, int cap, int window, int ldqkv, int rope,
+                                float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream);
+int rst_lm_ring_append_gqa(const float* qkv, void* k, void* v, const int64_t* pos_dev, int B, int Tc, int H, int G, int D, int cap, int ldqkv,
+                           int rope, float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream);
+
 /* The few-query form of rst_attention_f32(ring = 1) for streaming steps of the codec transformers (T <= a few new steps per
  * call): q [B][H][T][D] already rotated and k / v already appended by rst_rope_split_f32; every (b, t, h) query is split
  * over the occupied ring slots like rst_lm_attn_decode_f32 (same mask / slot map with end_offset = *pos_dev + T).

@@ -91,6 +91,9 @@ SIGNATURES = {
     "rst_lm_attn_prefill_workspace_bytes": [_i, _i, _i, _i, _i],
     "rst_lm_attn_prefill_f32": [_p, _p, _p, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _p],
     "rst_lm_ring_append": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _p],
+    "rst_lm_attn_prefill_gqa_workspace_bytes": [_i, _i, _i, _i, _i, _i],
+    "rst_lm_attn_prefill_gqa_f32": [_p, _p, _p, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _p],
+    "rst_lm_ring_append_gqa": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _p],
     "rst_attn_decode_multi_f32":[_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "rst_attention_step_supported": [_i, _i, _i],
     "rst_attention_step_f32": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p],

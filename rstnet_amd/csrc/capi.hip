@@ -574,40 +574,59 @@ int rst_lm_rope_table_f32(const int64_t* pos_dev, float* table, int D, int rope_
     return rst_launch_lm_rope_table((const long*)pos_dev, table, D, rope_dims > 0 ? rope_dims : D, rope_coef, (hipStream_t)stream);
 }
 
-int rst_lm_attn_prefill_workspace_bytes(int B, int Tc, int H, int D, int kv_bf16) {
-    const long n = rst_lm_attn_prefill_workspace_bytes_impl(B, Tc, H, D, kv_bf16);
+static int lm_prefill_ws_int(int B, int Tc, int H, int G, int D, int kv_bf16) {
+    const long n = rst_lm_attn_prefill_workspace_bytes_impl(B, Tc, H, G, D, kv_bf16);
     return n > 0x7fffffffL ? -1 : (int)n;
 }
 
-static LmPrefillParams lm_prefill_params(const float* qkv, void* k, void* v, const int64_t* pos_dev, int B, int Tc, int H, int D, int cap,
+int rst_lm_attn_prefill_workspace_bytes(int B, int Tc, int H, int D, int kv_bf16) { return lm_prefill_ws_int(B, Tc, H, H, D, kv_bf16); }
+
+int rst_lm_attn_prefill_gqa_workspace_bytes(int B, int Tc, int H, int G, int D, int kv_bf16) {
+    return lm_prefill_ws_int(B, Tc, H, G, D, kv_bf16);
+}
+
+static LmPrefillParams lm_prefill_params(const float* qkv, void* k, void* v, const int64_t* pos_dev, int B, int Tc, int H, int G, int D, int cap,
                                          int ldqkv, int rope, float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs) {
     LmPrefillParams p{};
-    p.qkv = qkv; p.k = k; p.v = v; p.kv_bf16 = kv_bf16; p.pos_dev = (const long*)pos_dev; p.B = B; p.T = Tc; p.H = H; p.D = D; p.cap = cap;
-    p.ldqkv = ldqkv; p.rope = rope; p.rope_coef = rope_coef; p.rope_dims = rope_dims > 0 ? rope_dims : D;
+    p.qkv = qkv; p.k = k; p.v = v; p.kv_bf16 = kv_bf16; p.pos_dev = (const long*)pos_dev; p.B = B; p.T = Tc; p.H = H; p.G = G; p.D = D;
+    p.cap = cap; p.ldqkv = ldqkv; p.rope = rope; p.rope_coef = rope_coef; p.rope_dims = rope_dims > 0 ? rope_dims : D;
     p.rope_freqs = rope ? rope_freqs : nullptr;
     return p;
+}
+
+int rst_lm_attn_prefill_gqa_f32(const float* qkv, const void* k, const void* v, void* workspace, int64_t workspace_bytes, float* out,
+                                const int64_t* pos_dev, int B, int Tc, int H, int G, int D, int cap, int window, int ldqkv, int rope,
+                                float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream) {
+    RST_REQUIRE(H >= 1 && G >= 1 && H % G == 0, "lm_attn_prefill: %d query heads are not a multiple of %d key/value heads", H, G);
+    LmPrefillParams p = lm_prefill_params(qkv, const_cast<void*>(k), const_cast<void*>(v), pos_dev, B, Tc, H, G, D, cap, ldqkv, rope, rope_coef,
+                                          rope_dims, kv_bf16, rope_freqs);
+    const long need = rst_lm_attn_prefill_workspace_bytes_impl(B, Tc, H, G, D, kv_bf16);
+    RST_REQUIRE(need > 0 && workspace && workspace_bytes >= need && (uintptr_t)workspace % 16 == 0,
+                "lm_attn_prefill: workspace of %ld bytes (16-byte aligned) needed, got %ld", need, (long)workspace_bytes);
+    const long nq = (long)B * Tc * H * D, nk = (long)B * Tc * G * D;
+    p.out = out; p.window = window;
+    p.q_rot = static_cast<float*>(workspace);
+    p.k_new = static_cast<char*>(workspace) + nq * 4;
+    p.v_new = static_cast<char*>(workspace) + nq * 4 + nk * (kv_bf16 ? 2 : 4);
+    return rst_launch_lm_attn_prefill(p, (hipStream_t)stream);
 }
 
 int rst_lm_attn_prefill_f32(const float* qkv, const void* k, const void* v, void* workspace, int64_t workspace_bytes, float* out,
                             const int64_t* pos_dev, int B, int Tc, int H, int D, int cap, int window, int ldqkv, int rope,
                             float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream) {
-    LmPrefillParams p = lm_prefill_params(qkv, const_cast<void*>(k), const_cast<void*>(v), pos_dev, B, Tc, H, D, cap, ldqkv, rope, rope_coef,
-                                          rope_dims, kv_bf16, rope_freqs);
-    const long need = rst_lm_attn_prefill_workspace_bytes_impl(B, Tc, H, D, kv_bf16);
-    RST_REQUIRE(need > 0 && workspace && workspace_bytes >= need && (uintptr_t)workspace % 16 == 0,
-                "lm_attn_prefill: workspace of %ld bytes (16-byte aligned) needed, got %ld", need, (long)workspace_bytes);
-    const long n = (long)B * Tc * H * D;
-    p.out = out; p.window = window;
-    p.q_rot = static_cast<float*>(workspace);
-    p.k_new = static_cast<char*>(workspace) + n * 4;
-    p.v_new = static_cast<char*>(workspace) + n * 4 + n * (kv_bf16 ? 2 : 4);
-    return rst_launch_lm_attn_prefill(p, (hipStream_t)stream);
+    return rst_lm_attn_prefill_gqa_f32(qkv, k, v, workspace, workspace_bytes, out, pos_dev, B, Tc, H, H, D, cap, window, ldqkv, rope, rope_coef,
+                                       rope_dims, kv_bf16, rope_freqs, stream);
+}
+
+int rst_lm_ring_append_gqa(const float* qkv, void* k, void* v, const int64_t* pos_dev, int B, int Tc, int H, int G, int D, int cap, int ldqkv,
+                           int rope, float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream) {
+    const LmPrefillParams p = lm_prefill_params(qkv, k, v, pos_dev, B, Tc, H, G, D, cap, ldqkv, rope, rope_coef, rope_dims, kv_bf16, rope_freqs);
+    return rst_launch_lm_ring_append(p, (hipStream_t)stream);
 }
 
 int rst_lm_ring_append(const float* qkv, void* k, void* v, const int64_t* pos_dev, int B, int Tc, int H, int D, int cap, int ldqkv, int rope,
                        float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream) {
-    const LmPrefillParams p = lm_prefill_params(qkv, k, v, pos_dev, B, Tc, H, D, cap, ldqkv, rope, rope_coef, rope_dims, kv_bf16, rope_freqs);
-    return rst_launch_lm_ring_append(p, (hipStream_t)stream);
+    return rst_lm_ring_append_gqa(qkv, k, v, pos_dev, B, Tc, H, H, D, cap, ldqkv, rope, rope_coef, rope_dims, kv_bf16, rope_freqs, stream);
 }
 
 int rst_attn_decode_multi_f32(const float* q, const float* k, const float* v, float* ws, uint32_t* counters, float* out,

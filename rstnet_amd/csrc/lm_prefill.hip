@@ -13,6 +13,9 @@
 //      (32 queries, head, stream), its four waves taking every fourth key tile and merging through LDS;
 //      fp32 rings (tiny models, kv_dtype=float32: the parity configuration): prefill_attn_f32_kernel, plain fp32 FMAs.
 // rst_launch_lm_ring_append is stage_kernel again with the ring as its destination: the same instructions produce the same bytes.
+//
+// Grouped KV heads (G < H, the litgpt-style GPT): the qkv row is [q: H*D | k: G*D | v: G*D], rings and the staged keys / values hold
+// G heads, and query head h reads KV head h / (H / G).  G == H is the Moshi layout, with the index arithmetic it always had.
 #include "lm_common.h"
 
 namespace {
@@ -42,11 +45,11 @@ template <> struct PfKv<true> {
 
 // One (real, imag) pair of one head of one new position per work item (the arithmetic of rope_append_kernel, lm_attn.hip:
 // angle = exp(i * rope_coef) * position as an fp32 product, cosf / sinf of it).  to_ring == 0: q heads -> q_rot [B][H][T][D] fp32, k / v heads -> k_new / v_new
-// [B][H][T][D] in the ring's dtype.  to_ring != 0: k / v heads only -> ring slots (pos + t) % cap of [B][H][cap][D].
+// [B][G][T][D] in the ring's dtype.  to_ring != 0: k / v heads only -> ring slots (pos + t) % cap of [B][G][cap][D].
 template <bool KV16>
 __global__ __launch_bounds__(256) void stage_kernel(const LmPrefillParams p, const int to_ring) {
     const int half = p.D / 2;
-    const int nh = to_ring ? p.H : 2 * p.H;
+    const int nh = to_ring ? p.G : p.H + p.G;
     const long total = (long)p.B * p.T * nh * half;
     const long pos0 = *p.pos_dev;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
@@ -73,9 +76,9 @@ __global__ __launch_bounds__(256) void stage_kernel(const LmPrefillParams p, con
         } else {
             const int g = hh - p.H;
             const float* ks = row + ((long)p.H + g) * p.D + 2 * i;
-            const float* vs = ks + (long)p.H * p.D;
-            const long at = to_ring ? ((b * p.H + g) * p.cap + (long)(pos % p.cap)) * p.D + 2 * i
-                                    : ((b * p.H + g) * p.T + t) * (long)p.D + 2 * i;
+            const float* vs = ks + (long)p.G * p.D;
+            const long at = to_ring ? ((b * p.G + g) * p.cap + (long)(pos % p.cap)) * p.D + 2 * i
+                                    : ((b * p.G + g) * p.T + t) * (long)p.D + 2 * i;
             PfKv<KV16>::store2(to_ring ? p.k : p.k_new, at, ks[0] * c - ks[1] * s, ks[0] * s + ks[1] * c);
             PfKv<KV16>::store2(to_ring ? p.v : p.v_new, at, vs[0], vs[1]);
         }
@@ -98,10 +101,11 @@ __global__ __launch_bounds__(64) void prefill_attn_f32_kernel(const LmPrefillPar
     const float* qrow = p.q_rot + ((b * p.H + h) * p.T + t) * (long)D;
     for (int i = lane; i < D; i += 64) sm_q[i] = qrow[i];
     __syncthreads();
-    const float* kring = static_cast<const float*>(p.k) + (b * p.H + h) * (long)p.cap * D;
-    const float* vring = static_cast<const float*>(p.v) + (b * p.H + h) * (long)p.cap * D;
-    const float* knew = static_cast<const float*>(p.k_new) + (b * p.H + h) * (long)p.T * D;
-    const float* vnew = static_cast<const float*>(p.v_new) + (b * p.H + h) * (long)p.T * D;
+    const long bg = b * p.G + h / (p.H / p.G);          // this query head's KV head
+    const float* kring = static_cast<const float*>(p.k) + bg * (long)p.cap * D;
+    const float* vring = static_cast<const float*>(p.v) + bg * (long)p.cap * D;
+    const float* knew = static_cast<const float*>(p.k_new) + bg * (long)p.T * D;
+    const float* vnew = static_cast<const float*>(p.v_new) + bg * (long)p.T * D;
     const float scale = 1.0f / sqrtf((float)D);
     float m_run = -INFINITY, l_run = 0.f;
     float o[D];
@@ -174,10 +178,11 @@ __global__ __launch_bounds__(256) void prefill_attn_bf16_kernel(const LmPrefillP
     const int tq = t0 + r;                               // this lane's query; rows past T are computed on a clamped row and dropped
     const int q_lo = max(tq - p.window + 1, u_min);      // its visible keys: q_lo <= u <= tq
 
-    const unsigned short* kring = static_cast<const unsigned short*>(p.k) + (b * p.H + h) * (long)p.cap * D;
-    const unsigned short* vring = static_cast<const unsigned short*>(p.v) + (b * p.H + h) * (long)p.cap * D;
-    const unsigned short* knew = static_cast<const unsigned short*>(p.k_new) + (b * p.H + h) * (long)p.T * D;
-    const unsigned short* vnew = static_cast<const unsigned short*>(p.v_new) + (b * p.H + h) * (long)p.T * D;
+    const long bg = b * p.G + h / (p.H / p.G);          // this query head's KV head (workgroup-uniform: scalar registers)
+    const unsigned short* kring = static_cast<const unsigned short*>(p.k) + bg * (long)p.cap * D;
+    const unsigned short* vring = static_cast<const unsigned short*>(p.v) + bg * (long)p.cap * D;
+    const unsigned short* knew = static_cast<const unsigned short*>(p.k_new) + bg * (long)p.T * D;
+    const unsigned short* vnew = static_cast<const unsigned short*>(p.v_new) + bg * (long)p.T * D;
     // row (in elements) of key u in its source, and whether that source is the staged chunk; u is clamped into [u_lo, t_last] (a
     // clamped key is masked by its score, its bytes are finite ring / chunk contents)
     auto row_of = [&](int u, bool& is_new) -> long {
@@ -321,7 +326,9 @@ int prefill_check(const LmPrefillParams& p, const char* what, bool attention) {
     RST_REQUIRE(p.qkv && p.k && p.v && p.pos_dev && p.B >= 1 && p.T >= 1 && p.H >= 1 && p.cap >= 1, "%s: bad arguments", what);
     RST_REQUIRE(p.D == 64 || p.D == 128, "%s: head dim %d unsupported (64, 128)", what, p.D);
     RST_REQUIRE(p.T <= p.cap, "%s: %d new positions for a ring of capacity %d", what, p.T, p.cap);
-    RST_REQUIRE(p.ldqkv >= 3 * p.H * p.D && p.ldqkv % 2 == 0, "%s: qkv row of %d floats for %d heads of dim %d", what, p.ldqkv, p.H, p.D);
+    RST_REQUIRE(p.G >= 1 && p.H % p.G == 0, "%s: %d query heads are not a multiple of %d key/value heads", what, p.H, p.G);
+    RST_REQUIRE(p.ldqkv >= (p.H + 2 * p.G) * p.D && p.ldqkv % 2 == 0, "%s: qkv row of %d floats for %d + 2 x %d heads of dim %d", what, p.ldqkv,
+                p.H, p.G, p.D);
     RST_REQUIRE(p.rope_dims >= 0 && p.rope_dims <= p.D && p.rope_dims % 2 == 0, "%s: bad rope_dims %d", what, p.rope_dims);
     if (attention) {
         RST_REQUIRE(p.out && p.q_rot && p.k_new && p.v_new, "%s: null output or workspace", what);
@@ -333,15 +340,14 @@ int prefill_check(const LmPrefillParams& p, const char* what, bool attention) {
 
 }  // namespace
 
-long rst_lm_attn_prefill_workspace_bytes_impl(int B, int T, int H, int D, int kv_bf16) {
-    if (B < 1 || T < 1 || H < 1 || D < 1) return -1;
-    const long n = (long)B * T * H * D;
-    return n * 4 + 2 * n * (kv_bf16 ? 2 : 4);
+long rst_lm_attn_prefill_workspace_bytes_impl(int B, int T, int H, int G, int D, int kv_bf16) {
+    if (B < 1 || T < 1 || H < 1 || G < 1 || D < 1) return -1;
+    return (long)B * T * H * D * 4 + 2 * (long)B * T * G * D * (kv_bf16 ? 2 : 4);
 }
 
 int rst_launch_lm_attn_prefill(const LmPrefillParams& p, hipStream_t stream) {
     if (const int rc = prefill_check(p, "lm_attn_prefill", true)) return rc;
-    const long total = (long)p.B * p.T * 2 * p.H * (p.D / 2);
+    const long total = (long)p.B * p.T * (p.H + p.G) * (p.D / 2);
     const dim3 sgrid(cap_grid((total + 255) / 256, 4096));
     if (p.kv_bf16) {
         hipLaunchKernelGGL(stage_kernel<true>, sgrid, dim3(256), 0, stream, p, 0);
@@ -359,7 +365,7 @@ int rst_launch_lm_attn_prefill(const LmPrefillParams& p, hipStream_t stream) {
 
 int rst_launch_lm_ring_append(const LmPrefillParams& p, hipStream_t stream) {
     if (const int rc = prefill_check(p, "lm_ring_append", false)) return rc;
-    const long total = (long)p.B * p.T * p.H * (p.D / 2);
+    const long total = (long)p.B * p.T * p.G * (p.D / 2);
     const dim3 sgrid(cap_grid((total + 255) / 256, 4096));
     if (p.kv_bf16) hipLaunchKernelGGL(stage_kernel<true>, sgrid, dim3(256), 0, stream, p, 1);
     else hipLaunchKernelGGL(stage_kernel<false>, sgrid, dim3(256), 0, stream, p, 1);

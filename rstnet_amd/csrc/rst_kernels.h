@@ -286,20 +286,21 @@ int rst_launch_lm_rope_table(const long* pos_dev, float* out, int D, int rope_di
 
 // Multi-position (prefill) attention and the append that follows it (lm_prefill.hip)
 struct LmPrefillParams {
-    const float* qkv;     // [B][T][ldqkv]: [q (H*D) | k (H*D) | v (H*D)] of the T new positions, un-rotated
-    void* k;              // [B][H][cap][D] ring: fp32, or bf16 when kv_bf16 (read by the attention, written by the append)
+    const float* qkv;     // [B][T][ldqkv]: [q (H*D) | k (G*D) | v (G*D)] of the T new positions, un-rotated
+    void* k;              // [B][G][cap][D] ring: fp32, or bf16 when kv_bf16 (read by the attention, written by the append)
     void* v;
     int kv_bf16;
     const long* pos_dev;  // position of the chunk's first row (== positions already appended)
     float* out;           // [B*T][H*D]
     float* q_rot;         // workspace: [B][H][T][D] rotated queries
-    void* k_new;          // workspace: [B][H][T][D] the chunk's rotated keys in the ring's dtype
+    void* k_new;          // workspace: [B][G][T][D] the chunk's rotated keys in the ring's dtype
     void* v_new;          // workspace: the chunk's values in the ring's dtype
     int B, T, H, D, cap, window, ldqkv, rope, rope_dims;
+    int G;                // key/value heads, H % G == 0: query head h reads kv head h / (H / G); G == H for MHA
     float rope_coef;
     const float* rope_freqs;   // [rope_dims / 2] frequencies exp(i * rope_coef), or nullptr: evaluated by the kernel
 };
-long rst_lm_attn_prefill_workspace_bytes_impl(int B, int T, int H, int D, int kv_bf16);
+long rst_lm_attn_prefill_workspace_bytes_impl(int B, int T, int H, int G, int D, int kv_bf16);
 int rst_launch_lm_attn_prefill(const LmPrefillParams& p, hipStream_t stream);
 int rst_launch_lm_ring_append(const LmPrefillParams& p, hipStream_t stream);
 

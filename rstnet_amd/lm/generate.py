@@ -20,7 +20,7 @@ import torch
 
 from .. import ops
 from ..graphs import Graphed as _Graphed, RecaptureGate
-from .gpt import GPT, _GPTState
+from .gpt import GPT, _GPTState, counted_step
 
 
 def reverse_delay(x: torch.Tensor) -> torch.Tensor:
@@ -67,12 +67,14 @@ class GPTGen:
         self._regime = None
         self.B = 0
 
-    def begin(self, batch_size: int) -> None:
+    def begin(self, batch_size: int, kv_dtype: Optional[torch.dtype] = None) -> None:
+        """Open a session of ``batch_size`` streams.  ``kv_dtype``: precision of the global KV rings (None = the model's ``kv_dtype``)."""
         m = self.model
         cfg, dev = m.config, m.device
         eager = self.noise is not None or dev.type != "cuda"
+        ring = m.transformer._make_state(batch_size, cfg.context + 1, kv_dtype)      # (refuses an unserved kv_dtype before anything changes)
         self._saved = (m.transformer._streaming_state, m._streaming_state, m.codecformer._streaming_state)
-        m.transformer._streaming_state = m.transformer._make_state(batch_size, cfg.context + 1)
+        m.transformer._streaming_state = ring
         m._streaming_state = _GPTState(_Graphed(m._global_step, disable=eager))
         m.codecformer._streaming_state = m.codecformer._init_streaming_state(batch_size, capacity=cfg.dep_q + 1)
         self._limits = torch.full((cfg.dep_q,), self.n_audio_codes + 1, device=dev, dtype=torch.int32)
@@ -159,7 +161,8 @@ class GPTGen:
             self._fused = _Graphed(self._step_fn)
         self._frames += 1
         self._g_idx += 1
-        self.last_h, self.last_logits = self._fused()
+        # (a graph replay advances the device counter only; `prefill` decides its route from the host mirror: lm.gpt.counted_step)
+        self.last_h, self.last_logits = counted_step(self.model.transformer._streaming_state, self._fused)
         return col[:, 0], col[:, 1:cfg.dep_q + 1]
 
     def set_blanking(self, wide: list) -> None:
@@ -169,7 +172,9 @@ class GPTGen:
         self._limits.copy_(torch.tensor([n + 1 if w else n for w in wide], dtype=torch.int32))
 
     def prefill(self, tokens: torch.Tensor):
-        """tokens int64 [B, K, T] -> (h [B, n_embd], logits [B, V]) of the LAST position."""
+        """tokens int64 [B, K, T] -> (h [B, n_embd], logits [B, V]) of the LAST position, from which ``frame`` / ``start`` continue.
+        Valid at any point of a live session: the T positions are appended behind whatever the session holds (a second turn, a wrapped
+        ring included); the captured step graphs stay valid, positions being device scalars."""
         h, logits = self.model.forward_global(tokens)
         return h[:, -1].contiguous(), logits[:, -1].contiguous()
 

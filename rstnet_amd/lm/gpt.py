@@ -34,8 +34,62 @@ from ..codec.streaming import StreamingModule
 from ..graphs import Graphed as _Graphed
 from ..packed import _PackedCache
 from .depth_frame import DepthDecoder
+from . import model as _lm_model       # PREFILL_CHUNK is read at call time
 from .model import RMSNorm as _AlphaNorm  # noqa: F401  (key layout of the codecformer norms)
 from .model import ScaledEmbedding, StreamingTransformer, _StepState, _Weight, adopt_state_dict
+
+KV_DTYPES = (torch.float32, torch.bfloat16)
+ROUTE_APPEND_FIRST = "append_first"      # lm_rope_append, then attention over the ring: fp32 rings that the chunk does not fill
+ROUTE_PREFILL = "prefill"                # lm_attn_prefill against ring + chunk, then lm_ring_append (csrc/lm_prefill.hip)
+
+
+def prefill_window(context: Optional[int], cap: int) -> int:
+    """Keys a query of a multi-position pass sees on a ring of ``cap`` slots, itself included: what ``T`` single steps see there --
+    the context, and never more than ``cap - 1`` because the step kernels hide the oldest slot of a full ring (the rule of
+    ``StreamingTransformer.window``).  ``GPTGen``'s rings of ``context + 1`` slots give the plain context."""
+    return min(context, cap - 1) if context else cap - 1
+
+
+def prefill_route(cap: int, pos: int, T: int, kv_dtype: torch.dtype) -> str:
+    """Route of ``T`` new positions behind ``pos`` appended ones on a ring of ``cap`` slots.  Appending first is only right while the
+    ring is not full after the chunk, ``pos + T < cap``, and its kernels read fp32 rings only.  (``pos + T > cap`` rewrites slots the
+    chunk's earlier queries still see; at ``pos + T == cap`` nothing is rewritten, but those kernels apply the slot -> position map of
+    the ring as it is AFTER the chunk to every query, and on a ring that is exactly full that map hides the oldest slot, SURVEY Q1:
+    position 0 is lost to queries that single steps let see it.)  Everything else attends before it appends."""
+    if kv_dtype == torch.float32 and pos + T < cap:
+        return ROUTE_APPEND_FIRST
+    return ROUTE_PREFILL
+
+
+def prefill_chunks(cap: int, pos: int, T: int, kv_dtype: torch.dtype, chunk: int) -> list:
+    """``[(t0, Tc, route)]`` of a ``T``-position call: a call that appends first as a whole stays ONE pass (the launches it always
+    took); otherwise position chunks of ``min(chunk, cap)``, each with its own route."""
+    if prefill_route(cap, pos, T, kv_dtype) == ROUTE_APPEND_FIRST:
+        return [(0, T, ROUTE_APPEND_FIRST)]
+    step = min(chunk, cap)
+    return [(t0, min(step, T - t0), prefill_route(cap, pos + t0, min(step, T - t0), kv_dtype)) for t0 in range(0, T, step)]
+
+
+def counted_step(st: _StepState, step, *args):
+    """Run ONE T = 1 step of the global transformer through ``step`` -- a ``Graphed`` callable or a plain one -- and leave the host
+    mirror ``st.offset_cpu`` one further, whether Python ran (warm-up, capture, eager: ``_blocks`` counted already) or a graph was
+    replayed (the device counter ``st.pos`` moved, no Python ran).  ``prefill_chunks`` decides the route of a later ``T > 1`` call from
+    that mirror without a device synchronisation, and a mirror that lags sends a chunk across the wrap down the append-first route:
+    wrong values, no error.  So EVERY caller that may replay a captured step goes through here, and code that moves ``st.pos`` by hand
+    (a benchmark that seeds a full ring) sets ``st.offset_cpu`` with it."""
+    at = st.offset_cpu
+    out = step(*args)
+    st.offset_cpu = at + 1
+    return out
+
+
+def check_kv_dtype(kv_dtype: torch.dtype, capacity: Optional[int] = None) -> None:
+    """The one place that says which ring dtypes exist, and (given a capacity) which rings can hold them."""
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype {kv_dtype}: the KV rings are torch.float32 or torch.bfloat16")
+    if kv_dtype == torch.bfloat16 and capacity is not None and capacity <= 64:
+        raise ValueError(f"kv_dtype=torch.bfloat16 on a ring of {capacity} slots: rings of <= 64 slots are read by the short-ring decode "
+                         "kernel, which reads fp32 only; use kv_dtype=torch.float32 or a context above 64")
 
 
 @dataclass
@@ -455,9 +509,12 @@ class LLAMAStreamingTransformer(StreamingModule[_StepState]):
         self.h = nn.ModuleList([Block(config, **fk) for _ in range(config.n_layer)])
         self.ln_f = _LitNorm(config.n_embd, config.norm_eps, **fk)
         self.fp8 = False      # opt-in: run the block linears on the fp8 (e4m3, per-row scales) matrix-core path
+        self.kv_dtype = torch.float32      # precision of the KV rings (GPT.from_state_dict(..., kv_dtype=))
 
-    def _make_state(self, batch_size: int, capacity: int) -> _StepState:
+    def _make_state(self, batch_size: int, capacity: int, kv_dtype: Optional[torch.dtype] = None) -> _StepState:
         c = self.config
+        kvd = self.kv_dtype if kv_dtype is None else kv_dtype
+        check_kv_dtype(kvd, capacity)
         dev = self.ln_f.weight.device
         shape = (batch_size, c.n_query_groups, capacity, c.head_size)
         scratch = None
@@ -465,7 +522,8 @@ class LLAMAStreamingTransformer(StreamingModule[_StepState]):
             splits = ops.lm_attn_splits(capacity, batch_size * c.n_head)
             scratch = (torch.empty(batch_size, c.n_head, splits, c.head_size + 2, device=dev),
                        torch.zeros(batch_size, c.n_head, device=dev, dtype=torch.int32))
-        return _StepState([torch.zeros(shape, device=dev) for _ in self.h], [torch.zeros(shape, device=dev) for _ in self.h],
+        return _StepState([torch.zeros(shape, device=dev, dtype=kvd) for _ in self.h],
+                          [torch.zeros(shape, device=dev, dtype=kvd) for _ in self.h],
                           torch.zeros(1, device=dev, dtype=torch.long), scratch)
 
     def _init_streaming_state(self, batch_size: int) -> _StepState:
@@ -474,23 +532,52 @@ class LLAMAStreamingTransformer(StreamingModule[_StepState]):
         return self._make_state(batch_size, self.config.context)
 
     def run(self, x: torch.Tensor, B: int, T: int, st: _StepState) -> torch.Tensor:
-        """x fp32 ``[B*T, n_embd]`` (T new positions per stream) -> final-normed hidden ``[B*T, n_embd]``."""
+        """x fp32 ``[B*T, n_embd]`` (T new positions per stream) -> final-normed hidden ``[B*T, n_embd]``.  ``T > 1``: one pass per
+        entry of ``prefill_chunks`` (decided from the host counter ``st.offset_cpu``), equal to the same positions fed one at a time
+        on any ring -- empty, partly filled or wrapped, fp32 or bf16."""
+        c = self.config
+        if T == 1:
+            return ops.rmsnorm(self._blocks(x, B, 1, st, None), self.ln_f.gain_f32(), self.ln_f.eps)
+        cap = st.k[0].shape[2]
+        plan = prefill_chunks(cap, st.offset_cpu, T, st.k[0].dtype, _lm_model.PREFILL_CHUNK)
+        if len(plan) == 1:
+            y = self._blocks(x, B, T, st, plan[0][2])
+        else:
+            xv = x.view(B, T, c.n_embd)
+            yv = torch.empty_like(xv)
+            for t0, Tc, route in plan:
+                yv[:, t0:t0 + Tc] = self._blocks(xv[:, t0:t0 + Tc].reshape(B * Tc, c.n_embd), B, Tc, st, route).view(B, Tc, c.n_embd)
+            y = yv.view(B * T, c.n_embd)
+        return ops.rmsnorm(y, self.ln_f.gain_f32(), self.ln_f.eps)
+
+    def _blocks(self, x: torch.Tensor, B: int, T: int, st: _StepState, route: Optional[str]) -> torch.Tensor:
+        """The blocks over ``T`` consecutive positions (``route`` of ``prefill_route`` for ``T > 1``); advances the counters by ``T``."""
         c = self.config
         H, G, hs, n = c.n_head, c.n_query_groups, c.head_size, c.rope_n_elem
         f8 = self.fp8
-        rope_table = None
+        base = float(c.rope_base)
+        rope_table = window = freqs = None
         if T == 1 and st.k[0].shape[2] > 64:      # the step's rotation once for all blocks (long rings)
-            rope_table = ops.lm_rope_table(st.pos, hs, max_period=float(c.rope_base), rope_dims=n)
+            rope_table = ops.lm_rope_table(st.pos, hs, max_period=base, rope_dims=n)
+        if route == ROUTE_PREFILL:
+            window = prefill_window(c.context, st.k[0].shape[2])
+            freqs = ops.gpt_rope_freqs(x.device, base, n)      # the table the reference evaluates (build_rope_cache)
         for l, blk in enumerate(self.h):
             wqkv, bqkv = blk.attn.packed_qkv()
             n1 = dict(prologue=ops.PROLOGUE_RMSNORM, alpha=blk.norm_1.gain_f32(), eps=blk.norm_1.eps)
             qkv = _lora_add(ops.lm_linear(x, wqkv, bias=bqkv, fp8=f8, **n1), x, blk.attn.packed_qkv_adapter(), **n1)
             if T == 1:
-                a = ops.lm_attn_decode(qkv, st.k[l], st.v[l], st.pos, rope=True, context=c.context, max_period=float(c.rope_base),
+                a = ops.lm_attn_decode(qkv, st.k[l], st.v[l], st.pos, rope=True, context=c.context, max_period=base,
                                        scratch=st.scratch, heads=H, rope_dims=n, packed=B > 2 and not f8, rope_table=rope_table)
+            elif route == ROUTE_PREFILL:
+                q3 = qkv.view(B, T, -1)
+                a = ops.lm_attn_prefill(q3, st.k[l], st.v[l], st.pos, window=window, rope=True, max_period=base, rope_dims=n, heads=H,
+                                        freqs=freqs)
+                # after the attention, in stream order: the slot of position pos + t still held position pos + t - cap
+                ops.lm_ring_append(q3, st.k[l], st.v[l], st.pos, rope=True, max_period=base, rope_dims=n, heads=H, freqs=freqs)
             else:
                 q = ops.lm_rope_append(qkv.view(B, T, -1), st.k[l], st.v[l], st.pos, heads=H, rope=True,
-                                       max_period=float(c.rope_base), rope_dims=n)
+                                       max_period=base, rope_dims=n)
                 a = ops.attention(q, st.k[l], st.v[l], pos_dev=st.pos, ring=True, context=c.context).view(B * T, H * hs)
             x = _lora_add(ops.lm_linear(a, blk.attn.proj.weight, res=x, bias=blk.attn.proj.bias_f32(), fp8=f8), a, blk.attn.proj.adapter())
             wfc, bfc = blk.mlp.packed_fc()
@@ -505,7 +592,7 @@ class LLAMAStreamingTransformer(StreamingModule[_StepState]):
                                             fp8=f8), u, ad_proj, prologue=ops.PROLOGUE_SILU_GATE)
         st.pos.add_(T)
         st.offset_cpu += T
-        return ops.rmsnorm(x, self.ln_f.gain_f32(), self.ln_f.eps)
+        return x
 
 
 @dataclass
@@ -585,6 +672,16 @@ class GPT(StreamingModule[_GPTState]):
     def device(self):
         return next(iter(self.parameters())).device
 
+    @property
+    def kv_dtype(self) -> torch.dtype:
+        """Precision of the global transformer's KV rings: fp32 (default), or bf16 for rings of more than 64 slots."""
+        return self.transformer.kv_dtype
+
+    @kv_dtype.setter
+    def kv_dtype(self, value: torch.dtype) -> None:
+        check_kv_dtype(value)
+        self.transformer.kv_dtype = value
+
     def _get_initial_token(self) -> torch.Tensor:
         tok = torch.full([1, self.num_codebooks, 1], self.initial_token_id, device=self.device, dtype=torch.long)
         tok[:, 0] = self.text_initial_token_id
@@ -622,10 +719,11 @@ class GPT(StreamingModule[_GPTState]):
         c = self.config
         st = self.transformer._streaming_state
         if st is not None and T == 1 and self._streaming_state is not None:
-            h, logits = self._streaming_state.graphed_global(sequence.reshape(B, K).contiguous())
+            h, logits = counted_step(st, self._streaming_state.graphed_global, sequence.reshape(B, K).contiguous())
             return h.view(B, 1, c.n_embd), logits.view(B, 1, -1)
         if st is None:
-            st = self.transformer._make_state(B, T + 1)      # a ring that never fills: positions 0..T-1 all addressable
+            # a ring that never fills: positions 0..T-1 all addressable (bf16 rings: above the 64 slots of the fp32-only short-ring kernel)
+            st = self.transformer._make_state(B, T + 1 if self.kv_dtype == torch.float32 else max(T + 1, 65))
         toks = sequence.permute(0, 2, 1).reshape(B * T, K).contiguous()
         h = self.transformer.run(self._embed(toks), B, T, st)
         logits = self._head(h)
@@ -701,14 +799,17 @@ class GPT(StreamingModule[_GPTState]):
 
     # ---- loading
     @classmethod
-    def from_state_dict(cls, sd: Dict[str, torch.Tensor], config: Config, keep_lora_base: bool = False, merge_lora: bool = True) -> "GPT":
+    def from_state_dict(cls, sd: Dict[str, torch.Tensor], config: Config, keep_lora_base: bool = False, merge_lora: bool = True,
+                        kv_dtype: torch.dtype = torch.float32) -> "GPT":
         """Model for ``config`` with weights taken from ``sd`` (reference key names, legacy base-checkpoint names accepted,
         LoRA adapters merged) without copying the dense tensors.  ``keep_lora_base``: also keep a copy of the un-adapted weight
         of every adapted linear, so that ``load_adapters`` can swap adapter sets later (the reference keeps adapters unmerged
         for that, llama_streaming.py:113-143; here a swap re-merges in place).  ``merge_lora=False``: the dense weights stay as
         they are and the adapters run as their own thin products behind every adapted linear (the reference's forward before
         ``merge_lora_weights``; ``state_dict()`` then carries ``<name>.lora_A`` / ``<name>.lora_B`` like the reference's, and
-        ``load_adapters`` swaps the tensors without touching a dense weight)."""
+        ``load_adapters`` swaps the tensors without touching a dense weight).  ``kv_dtype``: precision of the global transformer's KV
+        rings, fp32 or bf16 (bf16 needs rings of more than 64 slots: refused when a state is created)."""
+        check_kv_dtype(kv_dtype)      # (before any weight is touched; the setter below is what stores it)
         sd = _remap_legacy(dict(sd))
         sd = {k: v for k, v in sd.items() if not k.endswith(("cos", "sin", "_lora_ind"))}
         bases = None
@@ -719,6 +820,7 @@ class GPT(StreamingModule[_GPTState]):
                 is_ad = lambda k: k.endswith((".lora_A", ".lora_B"))
                 model = cls._from_merged({k: v for k, v in sd.items() if not is_ad(k)}, config)
                 model._unmerged = True
+                model.kv_dtype = kv_dtype
                 model._set_adapters({k: v for k, v in sd.items() if is_ad(k)})
                 return model
             if keep_lora_base:
@@ -726,6 +828,7 @@ class GPT(StreamingModule[_GPTState]):
             sd = merge_lora_state_dict(sd, config)
         model = cls._from_merged(sd, config)
         model._lora_base = bases
+        model.kv_dtype = kv_dtype
         return model
 
     def load_adapters(self, adapters: Optional[Dict[str, torch.Tensor]]) -> None:

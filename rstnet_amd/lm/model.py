@@ -138,6 +138,8 @@ class _StepState:
     v: List[torch.Tensor]
     pos: torch.Tensor          # int64 [1] on device: steps appended so far (= position of the next step)
     scratch: Optional[tuple] = None   # (split workspace, arrival counters) of the long-ring attention kernel
+    # host mirror of `pos`.  Graph replays move `pos` without running Python: whoever replays a captured step keeps the mirror in step
+    # (LMGen through temporal_base, GPT / GPTGen through lm.gpt.counted_step) -- GPT chooses the route of a T > 1 call from it
     offset_cpu: int = 0
     tables: object = None             # ops.TemporalFrameTables of the persistent batch-1 launch (built at the first step that takes it)
     tables_key: object = None

@@ -1267,47 +1267,74 @@ def _rope_freqs(device, max_period: float, n: int) -> torch.Tensor:
     return tab
 
 
-def _prefill_args(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos_dev: torch.Tensor):
+def gpt_rope_freqs(device, base: float, n: int) -> torch.Tensor:
+    """litgpt's frequency table ``1 / base ** (arange(0, n, 2) / n)`` (lit_model.build_rope_cache) evaluated as that reference writes
+    it, by torch in fp32, once per (device, base, n): the table ``GPT`` hands to ``lm_attn_prefill`` / ``lm_ring_append`` as ``freqs``."""
+    key = ("gpt", device, float(base), n)
+    tab = _rope_freq_tables.get(key)
+    if tab is None:
+        tab = _rope_freq_tables[key] = (1.0 / (base ** (torch.arange(0, n, 2).float() / n))).to(device)
+    return tab
+
+
+def _prefill_args(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos_dev: torch.Tensor, heads: Optional[int],
+                  freqs: Optional[torch.Tensor], rope_dims: int):
     _chk(qkv, "qkv")
     kv16 = k_cache.dtype == torch.bfloat16
     _chk(k_cache, "k_cache", k_cache.dtype if kv16 else torch.float32)
     _chk(v_cache, "v_cache", k_cache.dtype)
     _chk(pos_dev, "pos_dev", torch.int64)
-    B, H, cap, D = k_cache.shape
-    assert qkv.dim() == 3 and qkv.shape[0] == B and qkv.shape[2] == 3 * H * D, (tuple(qkv.shape), B, H, D)
+    _chk(freqs, "freqs")
+    B, G, cap, D = k_cache.shape
+    H = heads or G
+    assert qkv.dim() == 3 and qkv.shape[0] == B and qkv.shape[2] == (H + 2 * G) * D, (tuple(qkv.shape), B, H, G, D)
     assert v_cache.shape == k_cache.shape
-    return B, qkv.shape[1], H, D, cap, kv16
+    assert freqs is None or freqs.numel() >= (rope_dims or D) // 2, "freqs: one frequency per rotating pair"
+    return B, qkv.shape[1], H, G, D, cap, kv16
 
 
 @_on_tensor_device
 def lm_attn_prefill(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos_dev: torch.Tensor, *, window: int,
-                    rope: bool, max_period: float = 10000.0, rope_dims: int = 0) -> torch.Tensor:
-    """Attention of ``Tc`` new positions given their in-projection ``qkv [B, Tc, 3*H*D]`` against the ring ``[B,H,cap,D]`` (bf16 or
+                    rope: bool, max_period: float = 10000.0, rope_dims: int = 0, heads: Optional[int] = None,
+                    freqs: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Attention of ``Tc`` new positions given their in-projection ``qkv [B, Tc, (H+2G)*D]`` against the ring ``[B,G,cap,D]`` (bf16 or
     fp32) plus the chunk itself, BEFORE anything is appended -> ``[B*Tc, H*D]``.  The query at position ``p`` (``pos_dev`` = position of
     row 0) sees keys ``max(0, p - window + 1) .. p``; the chunk's own keys / values take part rounded to the ring's dtype.  Follow with
-    ``lm_ring_append`` (rst_lm_attn_prefill_f32; head dim 64 / 128, ``Tc <= cap``, ``1 <= window <= cap``)."""
-    B, Tc, H, D, cap, kv16 = _prefill_args(qkv, k_cache, v_cache, pos_dev)
-    nbytes = int(_lib.lib().rst_lm_attn_prefill_workspace_bytes(B, Tc, H, D, int(kv16)))
+    ``lm_ring_append`` (head dim 64 / 128, ``Tc <= cap``, ``1 <= window <= cap``).  ``heads`` = H when the ring holds G < H grouped
+    key/value heads (as in ``lm_attn_decode``; None: G == H, rst_lm_attn_prefill_f32, else rst_lm_attn_prefill_gqa_f32).  ``freqs``: the
+    fp32 frequency table of the caller's reference (``rope_dims / 2`` values); None: the Moshi table of ``_rope_freqs``."""
+    B, Tc, H, G, D, cap, kv16 = _prefill_args(qkv, k_cache, v_cache, pos_dev, heads, freqs, rope_dims)
+    L = _lib.lib()
+    nbytes = int(L.rst_lm_attn_prefill_workspace_bytes(B, Tc, H, D, int(kv16)) if heads is None else
+                 L.rst_lm_attn_prefill_gqa_workspace_bytes(B, Tc, H, G, D, int(kv16)))
     if nbytes <= 0:
-        raise ValueError(f"rstnet_amd.ops: lm_attn_prefill workspace for B={B} Tc={Tc} H={H} D={D} is not addressable")
+        raise ValueError(f"rstnet_amd.ops: lm_attn_prefill workspace for B={B} Tc={Tc} H={H} G={G} D={D} is not addressable")
     ws = _scratch(_prefill_ws, qkv.device, ("prefill", nbytes), lambda: torch.empty((nbytes + 7) // 8, device=qkv.device, dtype=torch.int64))
     out = torch.empty(B * Tc, H * D, device=qkv.device, dtype=torch.float32)
-    _lib.check(_lib.lib().rst_lm_attn_prefill_f32(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(ws), nbytes, _ptr(out), _ptr(pos_dev),
-                                                 B, Tc, H, D, cap, int(window), qkv.shape[2], int(rope),
-                                                 rope_coef(max_period, rope_dims or D), rope_dims, int(kv16),
-                                                 _ptr(_rope_freqs(qkv.device, max_period, rope_dims or D)) if rope else None, _stream()))
+    if freqs is None:
+        freqs = _rope_freqs(qkv.device, max_period, rope_dims or D)
+    head = (_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(ws), nbytes, _ptr(out), _ptr(pos_dev), B, Tc, H)
+    tail = (D, cap, int(window), qkv.shape[2], int(rope), rope_coef(max_period, rope_dims or D), rope_dims, int(kv16),
+            _ptr(freqs) if rope else None, _stream())
+    _lib.check(L.rst_lm_attn_prefill_f32(*head, *tail) if heads is None else L.rst_lm_attn_prefill_gqa_f32(*head, G, *tail))
     return out
 
 
 @_on_tensor_device
 def lm_ring_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos_dev: torch.Tensor, *, rope: bool,
-                   max_period: float = 10000.0, rope_dims: int = 0) -> None:
-    """The append that follows ``lm_attn_prefill`` in stream order: the ``Tc`` keys of ``qkv [B, Tc, 3*H*D]`` rotated at positions
-    ``pos_dev + t``, and the values, into ring slots ``(pos_dev + t) % cap`` in the ring's dtype (rst_lm_ring_append)."""
-    B, Tc, H, D, cap, kv16 = _prefill_args(qkv, k_cache, v_cache, pos_dev)
-    _lib.check(_lib.lib().rst_lm_ring_append(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(pos_dev), B, Tc, H, D, cap, qkv.shape[2],
-                                            int(rope), rope_coef(max_period, rope_dims or D), rope_dims, int(kv16),
-                                            _ptr(_rope_freqs(qkv.device, max_period, rope_dims or D)) if rope else None, _stream()))
+                   max_period: float = 10000.0, rope_dims: int = 0, heads: Optional[int] = None,
+                   freqs: Optional[torch.Tensor] = None) -> None:
+    """The append that follows ``lm_attn_prefill`` in stream order: the ``Tc`` keys of ``qkv [B, Tc, (H+2G)*D]`` rotated at positions
+    ``pos_dev + t``, and the values, into ring slots ``(pos_dev + t) % cap`` of ``[B,G,cap,D]`` in the ring's dtype (rst_lm_ring_append;
+    ``heads`` given: rst_lm_ring_append_gqa).  ``heads`` / ``freqs`` as in ``lm_attn_prefill``."""
+    B, Tc, H, G, D, cap, kv16 = _prefill_args(qkv, k_cache, v_cache, pos_dev, heads, freqs, rope_dims)
+    L = _lib.lib()
+    if freqs is None:
+        freqs = _rope_freqs(qkv.device, max_period, rope_dims or D)
+    head = (_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(pos_dev), B, Tc, H)
+    tail = (D, cap, qkv.shape[2], int(rope), rope_coef(max_period, rope_dims or D), rope_dims, int(kv16), _ptr(freqs) if rope else None,
+            _stream())
+    _lib.check(L.rst_lm_ring_append(*head, *tail) if heads is None else L.rst_lm_ring_append_gqa(*head, G, *tail))
 
 
 _sample_ws: dict = {}
