@@ -331,6 +331,26 @@ int rst_gemv_fp8w_supported(int B, int N, int K);
 int rst_gemv_fp8w_f32(const float* x, const float* alpha, const uint8_t* q, const float* scale, const float* res, const float* bias,
                       float* y, int B, int N, int K, int ldx, int ldy, int prologue, float eps, int gate_out, rst_stream_t stream);
 
+/* Weight-only MXFP4 storage for the same GEMV (opt-in: LMModel.quantize_weights_("mxfp4")), at the per-layer call sites of the
+ * temporal stack -- in_proj / out_proj (modules/transformer.py:376-423), gating linear_in / linear_out (modules/gating.py:12-51) --
+ * with the weight stored as OCP e2m1 codes q [N][K / 2] (two per byte, even k in the low nibble, bit 3 of a code the sign) plus one
+ * scale byte e + 127 per block of 32 consecutive k, scale [N][K / 32]: a power of two 2^e per block.  Activations and accumulation
+ * stay fp32.
+ *   rst_quant_blocks_mxfp4: w bf16 [N][K] (finite, |w| < 2^120; the host refuses anything else), K % 32 == 0, w and q 16-byte aligned
+ *     -> q, scale.  e = the smallest integer with amax / 2^e <= 6 over the block (from the exponent and mantissa bits of amax), clamped
+ *     below at -125; an all-zero block takes e = 0.  code = |w| / 2^e (exact) rounded to nearest on {0, 0.5, 1, 1.5, 2, 3, 4, 6}, ties
+ *     to the code with an even mantissa bit; nothing saturates.  code * 2^e is a normal number and exactly a bf16 number.
+ *   rst_gemv_mxfp4w_f32: y[b][n] = (res ? res[b][n] : 0) + (bias ? bias[n] : 0) + sum_k P(x)[b][k] * dec(q[n][k]) * 2^e[n][k / 32] --
+ *     the scales multiply the products only.  Arguments as rst_gemv_fp8w_f32 (prologue 0 / 1 / 2, gate_out), 1 <= B <= 4,
+ *     K % 32 == 0, x and q 16-byte aligned, and B * roundup(K, 2048) <= 32768 (the fp32 activation stage);
+ *     rst_gemv_mxfp4w_supported(B, N, K) answers 1 for exactly these shapes -- callers take the fp8 or bf16 route (same values, more
+ *     bytes) for the others.  Schedules: batch-1 layers with N*K >= 2^24, K <= 4096 (RMSNorm or plain) take whole rows per wave with
+ *     x requested before the weight stream; everything else stages x in LDS once per workgroup. */
+int rst_quant_blocks_mxfp4(const uint16_t* w, uint8_t* q, uint8_t* scale, int N, int K, rst_stream_t stream);
+int rst_gemv_mxfp4w_supported(int B, int N, int K);
+int rst_gemv_mxfp4w_f32(const float* x, const float* alpha, const uint8_t* q, const uint8_t* scale, const float* res, const float* bias,
+                        float* y, int B, int N, int K, int ldx, int ldy, int prologue, float eps, int gate_out, rst_stream_t stream);
+
 /* Two fused forms of the batch <= 2 GEMV for the depth transformer ("depformer", models/model.py:392-428,564-597;
  * "codecformer", models/llama_streaming.py:727-749), whose 8 steps x 6 layers are a chain of ~5 us launches:
  *

@@ -67,6 +67,9 @@ SIGNATURES = {
     "rst_quant_rows_fp8": [_p, _p, _p, _i, _i, _p],
     "rst_gemv_fp8w_supported": [_i, _i, _i],
     "rst_gemv_fp8w_f32": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p],
+    "rst_quant_blocks_mxfp4": [_p, _p, _p, _i, _i, _p],
+    "rst_gemv_mxfp4w_supported": [_i, _i, _i],
+    "rst_gemv_mxfp4w_f32": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p],
     "rst_gemv_attn_bf16_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "rst_gemv_embed_bf16_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
     "rst_depth_frame_workspace_bytes": [_i, _i, _i, _i],

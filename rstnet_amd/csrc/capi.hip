@@ -24,7 +24,7 @@ int rst_check_launch(const char* what) {
 
 extern "C" {
 
-int rst_version(void) { return 122; }      // 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
+int rst_version(void) { return 123; }      // 123: + rst_quant_blocks_mxfp4, rst_gemv_mxfp4w_f32 / _supported (MXFP4 weight-only GEMV); 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
                                            // rst_rvq_search_chain_f32, rst_embed_sum_bf16(add_stride); 105: round 4
 const char* rst_last_error(void) { return g_err; }
 
@@ -359,6 +359,20 @@ int rst_gemv_fp8w_f32(const float* x, const float* alpha, const uint8_t* q, cons
     p.x = x; p.alpha = alpha; p.q = q; p.scale = scale; p.res = res; p.bias = bias; p.y = y; p.B = B; p.N = N;
     p.K = K; p.ldx = ldx; p.ldy = ldy; p.prologue = prologue; p.gate_out = gate_out; p.eps = eps;
     return rst_launch_gemv_fp8w(p, (hipStream_t)stream);
+}
+
+int rst_quant_blocks_mxfp4(const uint16_t* w, uint8_t* q, uint8_t* scale, int N, int K, rst_stream_t stream) {
+    return rst_launch_quant_blocks_mxfp4(w, q, scale, N, K, (hipStream_t)stream);
+}
+
+int rst_gemv_mxfp4w_supported(int B, int N, int K) { return rst_gemv_mxfp4w_supported_impl(B, N, K); }
+
+int rst_gemv_mxfp4w_f32(const float* x, const float* alpha, const uint8_t* q, const uint8_t* scale, const float* res, const float* bias,
+                        float* y, int B, int N, int K, int ldx, int ldy, int prologue, float eps, int gate_out, rst_stream_t stream) {
+    GemvFp4Params p;
+    p.x = x; p.alpha = alpha; p.q = q; p.scale = scale; p.res = res; p.bias = bias; p.y = y; p.B = B; p.N = N;
+    p.K = K; p.ldx = ldx; p.ldy = ldy; p.prologue = prologue; p.gate_out = gate_out; p.eps = eps;
+    return rst_launch_gemv_mxfp4w(p, (hipStream_t)stream);
 }
 
 int rst_gemv_attn_bf16_f32(const float* qkv, float* k_cache, float* v_cache, const int64_t* pos_dev, const uint16_t* w,

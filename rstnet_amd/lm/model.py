@@ -36,18 +36,50 @@ def _gating_hidden(dim: int, dim_feedforward: int) -> int:
     return (21 * dim) // 8 if dim_feedforward == 4 * dim else (2 * dim_feedforward) // 3
 
 
-def _w8(mod: nn.Module, name: str = "weight") -> Optional[tuple]:
-    """The ``(q, scale)`` fp8 copy of parameter ``name`` of ``mod`` (``LMModel.quantize_weights_``), or None.  The copy is dropped when
-    the bf16 parameter was replaced or written since: it then no longer holds the same values."""
-    q = getattr(mod, name + "_q8", None)
+def _wq(mod: nn.Module, name: str, tag: str) -> Optional[tuple]:
+    q = getattr(mod, name + "_q" + tag, None)
     if q is None:
         return None
     w = getattr(mod, name)
-    if mod._w8_of.get(name) != (w.data_ptr(), w._version):
-        setattr(mod, name + "_q8", None)
-        setattr(mod, name + "_s8", None)
+    if getattr(mod, "_w" + tag + "_of").get(name) != (w.data_ptr(), w._version):
+        setattr(mod, name + "_q" + tag, None)
+        setattr(mod, name + "_s" + tag, None)
         return None
-    return q, getattr(mod, name + "_s8")
+    return q, getattr(mod, name + "_s" + tag)
+
+
+def _w8(mod: nn.Module, name: str = "weight") -> Optional[tuple]:
+    """The ``(q, scale)`` fp8 copy of parameter ``name`` of ``mod`` (``LMModel.quantize_weights_``), or None.  The copy is dropped when
+    the bf16 parameter was replaced or written since: it then no longer holds the same values."""
+    return _wq(mod, name, "8")
+
+
+def _w4(mod: nn.Module, name: str = "weight") -> Optional[tuple]:
+    """The MXFP4 copy (``ops.Mxfp4Copy``) of parameter ``name`` of ``mod`` (``LMModel.quantize_weights_("mxfp4")``), or None; dropped
+    like the fp8 copy of ``_w8`` when the bf16 parameter was replaced or written since."""
+    c = _wq(mod, name, "4")
+    return None if c is None else ops.Mxfp4Copy(*c)
+
+
+def _wcopy(mod: nn.Module, name: str, weight_dtype: str) -> Optional[tuple]:
+    """The copy of a quantised model's matrix that the batch <= 2 GEMV route streams: under ``"mxfp4"`` the MXFP4 copy where the matrix
+    has one, else the fp8 copy (heads; K no multiple of 32); under ``"fp8"`` the fp8 copy; None for bf16."""
+    if weight_dtype == "bf16":
+        return None
+    return (_w4(mod, name) if weight_dtype == "mxfp4" else None) or _w8(mod, name)
+
+
+def _attach_copy(mod: nn.Module, name: str, tag: str, q: torch.Tensor, scale: torch.Tensor) -> None:
+    """``(q, scale)`` become the non-persistent buffers ``<name>_q<tag>`` / ``<name>_s<tag>`` of ``mod``, valid for the parameter as it is now."""
+    w = getattr(mod, name)
+    if not hasattr(mod, "_w" + tag + "_of"):
+        setattr(mod, "_w" + tag + "_of", {})
+    for suffix, t in (("_q" + tag, q), ("_s" + tag, scale)):
+        if hasattr(mod, name + suffix):
+            setattr(mod, name + suffix, t)
+        else:
+            mod.register_buffer(name + suffix, t, persistent=False)
+    getattr(mod, "_w" + tag + "_of")[name] = (w.data_ptr(), w._version)
 
 
 def adopt_state_dict(model: nn.Module, sd: Dict[str, torch.Tensor]) -> None:
@@ -166,7 +198,7 @@ class StreamingTransformer(StreamingModule[_StepState]):
             raise NotImplementedError(f"positional_embedding={positional_embedding!r}")
         self.d_model, self.num_heads, self.context = d_model, num_heads, context
         self.rope, self.max_period, self.weights_per_step = positional_embedding == "rope", max_period, weights_per_step
-        self.weight_dtype = "bf16"        # "fp8": LMModel.quantize_weights_ left fp8 copies on the layers; the chain route streams them
+        self.weight_dtype = "bf16"        # "fp8" / "mxfp4": LMModel.quantize_weights_ left copies on the layers; the chain route streams them
         self.layers = nn.ModuleList([_Layer(d_model, dim_feedforward, weights_per_step, device=device, dtype=dtype)
                                      for _ in range(num_layers)])
 
@@ -229,9 +261,9 @@ class StreamingTransformer(StreamingModule[_StepState]):
                 gate = layer.gating[k_idx]
             else:
                 w_in, w_out, gate = att.in_proj_weight, att.out_proj.weight, layer.gating
-            # fp8 copies of a quantised model (never the depth transformer: its weights are not covered)
-            q8 = self.weight_dtype == "fp8" and not self.weights_per_step
-            w8_in = _w8(att, "in_proj_weight") if q8 else None
+            # fp8 / MXFP4 copies of a quantised model (never the depth transformer: its weights are not covered)
+            wd = "bf16" if self.weights_per_step else self.weight_dtype
+            w8_in = _wcopy(att, "in_proj_weight", wd)
             if l == 0 and embed is not None:
                 add, table, tokens, col = embed
                 if B <= 2 and E <= 4096 and E % 8 == 0:
@@ -246,9 +278,9 @@ class StreamingTransformer(StreamingModule[_StepState]):
             else:
                 a = ops.lm_attn_decode(qkv, st.k[l], st.v[l], pos_t, rope=self.rope, context=self.context,
                                        max_period=self.max_period, scratch=st.scratch, packed=B > 2, rope_table=rope_table)
-                x = ops.lm_linear(a, w_out, res=x, w8=_w8(att.out_proj) if q8 else None)
+                x = ops.lm_linear(a, w_out, res=x, w8=_wcopy(att.out_proj, "weight", wd))
             x = ops.lm_gated_pair(x, gate.linear_in.weight, gate.linear_out.weight, alpha=layer.norm2.alpha_f32(), eps=layer.norm2.eps,
-                                  res=x, w8_in=_w8(gate.linear_in) if q8 else None, w8_out=_w8(gate.linear_out) if q8 else None)
+                                  res=x, w8_in=_wcopy(gate.linear_in, "weight", wd), w8_out=_wcopy(gate.linear_out, "weight", wd))
         if pos is None:
             st.pos.add_(1)
             st.offset_cpu += 1
@@ -275,7 +307,7 @@ class StreamingTransformer(StreamingModule[_StepState]):
         assert x.shape == (B * T, E), (tuple(x.shape), B, T, E)
         cap = st.k[0].shape[2]
         window = self.window(cap)
-        q8 = self.weight_dtype == "fp8"
+        wd = self.weight_dtype
         xv = x.view(B, T, E)
         y = torch.empty_like(xv)
         for t0 in range(0, T, min(PREFILL_CHUNK, cap)):
@@ -284,13 +316,13 @@ class StreamingTransformer(StreamingModule[_StepState]):
             for l, layer in enumerate(self.layers):
                 att, gate = layer.self_attn, layer.gating
                 qkv = ops.lm_linear(h, att.in_proj_weight, prologue=ops.PROLOGUE_RMSNORM, alpha=layer.norm1.alpha_f32(), eps=layer.norm1.eps,
-                                    w8=_w8(att, "in_proj_weight") if q8 else None).view(B, Tc, 3 * E)
+                                    w8=_wcopy(att, "in_proj_weight", wd)).view(B, Tc, 3 * E)
                 a = ops.lm_attn_prefill(qkv, st.k[l], st.v[l], st.pos, window=window, rope=self.rope, max_period=self.max_period)
                 # after the attention, in stream order: the slot of position pos + t still held position pos + t - cap
                 ops.lm_ring_append(qkv, st.k[l], st.v[l], st.pos, rope=self.rope, max_period=self.max_period)
-                h = ops.lm_linear(a, att.out_proj.weight, res=h, w8=_w8(att.out_proj) if q8 else None)
+                h = ops.lm_linear(a, att.out_proj.weight, res=h, w8=_wcopy(att.out_proj, "weight", wd))
                 h = ops.lm_gated_pair(h, gate.linear_in.weight, gate.linear_out.weight, alpha=layer.norm2.alpha_f32(), eps=layer.norm2.eps,
-                                      res=h, w8_in=_w8(gate.linear_in) if q8 else None, w8_out=_w8(gate.linear_out) if q8 else None)
+                                      res=h, w8_in=_wcopy(gate.linear_in, "weight", wd), w8_out=_wcopy(gate.linear_out, "weight", wd))
             y[:, t0:t0 + Tc] = h.view(B, Tc, E)
             st.pos.add_(Tc)
             st.offset_cpu += Tc
@@ -384,7 +416,7 @@ class LMModel(StreamingContainer):
     def depformer_in_all_w8(self) -> Optional[tuple]:
         """The ``(q, scale)`` fp8 copy of ``depformer_in_all()`` of a quantised model (rows quantise independently, so stacking the
         per-matrix copies IS the copy of the stacked matrix), or None."""
-        if self.weight_dtype != "fp8":
+        if self.weight_dtype == "bf16":
             return None
         pairs = [_w8(m) for m in self.depformer_in]
         if any(c is None for c in pairs):
@@ -392,13 +424,17 @@ class LMModel(StreamingContainer):
         return self._in_cat8.get(tuple(c[0] for c in pairs), lambda: (torch.cat([c[0] for c in pairs], 0).contiguous(),
                                                                      torch.cat([c[1] for c in pairs], 0).contiguous()))
 
-    def _covered_weights(self):
-        """(module, parameter name) of every matrix ``quantize_weights_`` covers."""
+    def _layer_weights(self):
+        """(module, parameter name) of the four per-layer matrices of the temporal stack: the ones ``"mxfp4"`` stores as MXFP4."""
         for layer in self.transformer.layers:
             yield layer.self_attn, "in_proj_weight"
             yield layer.self_attn.out_proj, "weight"
             yield layer.gating.linear_in, "weight"
             yield layer.gating.linear_out, "weight"
+
+    def _covered_weights(self):
+        """(module, parameter name) of every matrix ``quantize_weights_`` covers."""
+        yield from self._layer_weights()
         yield self.text_linear, "weight"
         for m in self.depformer_in:
             yield m, "weight"
@@ -420,13 +456,25 @@ class LMModel(StreamingContainer):
         A quantised model does not take the persistent temporal launch (it reads bf16).
 
         Captured frame graphs embed weight pointers, so quantising while a streaming session of this model is live raises
-        ``RuntimeError``: quantise first, then open the session.  Speech quality under fp8 weights has not been evaluated."""
+        ``RuntimeError``: quantise first, then open the session.  Speech quality under fp8 weights has not been evaluated.
+
+        ``weight_dtype="mxfp4"``: the four per-layer matrices of the temporal stack (6.6 of those GB) are stored as OCP MXFP4 instead
+        -- e2m1 codes in blocks of 32 along K with one power-of-two scale byte per block (``ops.quantize_blocks_mxfp4``, buffers
+        ``<name>_q4`` / ``<name>_s4``, streamed by ``ops.gemv_mxfp4w``), again with the bf16 parameter overwritten by the exactly
+        representable dequantised values; a per-layer matrix whose K is no multiple of 32 is stored as fp8.  The two output-facing
+        matrices, ``text_linear`` and the ``depformer_in[k]``, stay at fp8.  Round-to-nearest MXFP4 has an rms relative weight
+        error of 11.5 % on Gaussian rows (fp8: 2.7 %) and speech quality under it has not been evaluated.  Weights with
+        ``|w| >= 2^120`` are refused.  A model quantised to one format cannot be quantised to the other: its parameters have
+        already been rounded once (``ValueError``)."""
         if weight_dtype == "bf16":
             if self.weight_dtype != "bf16":
                 raise ValueError("a quantised model cannot return to bf16: the bf16 parameters already hold the rounded values")
             return self
-        if weight_dtype != "fp8":
-            raise ValueError(f"weight_dtype must be 'bf16' or 'fp8', got {weight_dtype!r}")
+        if weight_dtype not in ("fp8", "mxfp4"):
+            raise ValueError(f"weight_dtype must be 'bf16', 'fp8' or 'mxfp4', got {weight_dtype!r}")
+        if self.weight_dtype not in ("bf16", weight_dtype):
+            raise ValueError(f"the model is already quantised to {self.weight_dtype!r}: its parameters hold values rounded once and "
+                             f"cannot be quantised to {weight_dtype!r}")
         if self._streaming_state is not None or self.transformer._streaming_state is not None:
             raise RuntimeError("quantize_weights_ inside a live streaming session: a captured frame graph would keep streaming the "
                                "bf16 weights; quantise before `streaming()`")
@@ -437,21 +485,26 @@ class LMModel(StreamingContainer):
                 raise TypeError(f"quantize_weights_ needs bf16 weights, got {w.dtype}")
             if not bool(torch.isfinite(w).all()):
                 raise ValueError(f"quantize_weights_: non-finite values in a {tuple(w.shape)} weight; nothing was quantised")
+        as_mxfp4 = set()
+        if weight_dtype == "mxfp4":
+            for mod, name in self._layer_weights():
+                w = getattr(mod, name)
+                if w.shape[1] % 32 == 0:
+                    as_mxfp4.add((id(mod), name))
+                    if bool((w.abs() >= 2.0 ** 120).any()):
+                        raise ValueError(f"quantize_weights_: magnitudes >= 2^120 in a {tuple(w.shape)} weight; nothing was quantised")
         for mod, name in covered:
-            if _w8(mod, name) is not None:
-                continue
             w = getattr(mod, name)
-            q, scale = ops.quantize_rows_fp8(w.detach())
-            w.copy_(ops.dequantize_rows_fp8(q, scale))
-            if not hasattr(mod, "_w8_of"):
-                mod._w8_of = {}
-            for suffix, t in (("_q8", q), ("_s8", scale)):
-                if hasattr(mod, name + suffix):
-                    setattr(mod, name + suffix, t)
-                else:
-                    mod.register_buffer(name + suffix, t, persistent=False)
-            mod._w8_of[name] = (w.data_ptr(), w._version)
-        self.weight_dtype = self.transformer.weight_dtype = "fp8"
+            if (id(mod), name) in as_mxfp4:
+                if _w4(mod, name) is None:
+                    q, scale = ops.quantize_blocks_mxfp4(w.detach())
+                    w.copy_(ops.dequantize_blocks_mxfp4(q, scale))
+                    _attach_copy(mod, name, "4", q, scale)
+            elif _w8(mod, name) is None:
+                q, scale = ops.quantize_rows_fp8(w.detach())
+                w.copy_(ops.dequantize_rows_fp8(q, scale))
+                _attach_copy(mod, name, "8", q, scale)
+        self.weight_dtype = self.transformer.weight_dtype = weight_dtype
         return self
 
     # ---- token-id conventions (models/model.py:226-277)
@@ -548,7 +601,7 @@ class LMModel(StreamingContainer):
         B, K, S = sequence.shape
         assert K == self.num_codebooks, f"Sequence shape {sequence.shape} must match the number of codebooks."
         tables = [e.weight for e in self.emb] + [self.text_emb.weight]
-        w8 = _w8(self.text_linear) if self.weight_dtype == "fp8" else None
+        w8 = _w8(self.text_linear) if self.weight_dtype != "bf16" else None
         if S == 1:
             toks = sequence.reshape(B, K).contiguous()
             x = ops.embed_sum(toks, tables, list(range(1, K)) + [0])     # ((e_0 + e_1) + ...) + text, as the reference
@@ -584,7 +637,7 @@ class LMModel(StreamingContainer):
                           step_index: Optional[int] = None, h_all: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Depth step ``k``: previous token = ``tokens[:, col]`` (int64 ``[B, n]``), ``h_t`` fp32 ``[B, dim]`` -> logits ``[B, card]``.
         ``h_all`` (``[B, dep_q * depformer_dim]``, the stacked ``depformer_in`` products of the frame) replaces ``h_t``."""
-        w8 = _w8(self.depformer_in[k]) if h_all is None and self.weight_dtype == "fp8" else None
+        w8 = _w8(self.depformer_in[k]) if h_all is None and self.weight_dtype != "bf16" else None
         return self.depth_decoder.step_logits(k, tokens, col, h_t, h_all=h_all, w8=w8, pos=pos, step_index=step_index)
 
     @classmethod
@@ -592,7 +645,7 @@ class LMModel(StreamingContainer):
                         weight_dtype: str = "bf16") -> "LMModel":
         """Model for ``cfg`` (keys of ``rstnet_amd.synth.LM_*``) with weights taken from ``sd`` WITHOUT copying them
         (a 7.7 B-parameter state dict stays a single 15 GB allocation).  ``kv_dtype``: precision of the temporal KV rings.
-        ``weight_dtype="fp8"``: ``quantize_weights_("fp8")`` on the loaded model (it rewrites the covered tensors of ``sd`` in place)."""
+        ``weight_dtype="fp8"`` / ``"mxfp4"``: ``quantize_weights_`` on the loaded model (it rewrites the covered tensors of ``sd`` in place)."""
         model = cls(kv_dtype=kv_dtype, causal=True, layer_scale=None, gating="silu", norm="rms_norm_f32", positional_embedding="rope",
                     depformer_causal=True, depformer_layer_scale=None, depformer_multi_linear=True, depformer_context=8,
                     depformer_gating="silu", depformer_pos_emb="none", depformer_weights_per_step=True, device="meta", **cfg)

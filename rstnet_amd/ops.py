@@ -889,6 +889,74 @@ def gemv_fp8w(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, *, prologue
     return out
 
 
+_E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+class Mxfp4Copy(NamedTuple):
+    """``(q, scale)`` of ``quantize_blocks_mxfp4``, typed so that ``lm_linear`` / ``lm_gated_pair`` can tell it from an fp8 ``(q, scale)``
+    pair in their ``w8=`` / ``w8_in=`` / ``w8_out=`` arguments."""
+    q: torch.Tensor
+    scale: torch.Tensor
+
+
+@_on_tensor_device
+def quantize_blocks_mxfp4(w: torch.Tensor) -> "Mxfp4Copy":
+    """bf16 ``[N, K]``, ``K % 32 == 0`` -> (``q`` uint8 ``[N, K/2]``: OCP e2m1 codes, two per byte, even ``k`` in the low nibble;
+    ``scale`` uint8 ``[N, K/32]``: ``e + 127`` per block of 32 ``k``, ``e`` the smallest integer with ``amax / 2^e <= 6``, at least
+    -125; rst_quant_blocks_mxfp4).  ``code * 2^e`` is exactly a bf16 number.  Non-finite weights and ``|w| >= 2^120`` raise."""
+    _chk(w, "w", torch.bfloat16)
+    assert w.dim() == 2, tuple(w.shape)
+    N, K = w.shape
+    if K % 32:
+        raise ValueError(f"rstnet_amd.ops.quantize_blocks_mxfp4: K = {K} is not a multiple of the block size 32")
+    if not bool(torch.isfinite(w).all()) or bool((w.abs() >= 2.0 ** 120).any()):
+        raise ValueError("rstnet_amd.ops.quantize_blocks_mxfp4: the weight holds non-finite values or magnitudes >= 2^120")
+    q = torch.empty(N, K // 2, device=w.device, dtype=torch.uint8)
+    scale = torch.empty(N, K // 32, device=w.device, dtype=torch.uint8)
+    _lib.check(_lib.lib().rst_quant_blocks_mxfp4(_ptr(w), _ptr(q), _ptr(scale), N, K, _stream()))
+    return Mxfp4Copy(q, scale)
+
+
+def dequantize_blocks_mxfp4(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The bf16 ``[N, K]`` matrix that ``(q, scale)`` of ``quantize_blocks_mxfp4`` stands for (exact: 2 significant bits times a
+    power of two, a normal number)."""
+    N = q.shape[0]
+    codes = torch.stack((q & 0xF, q >> 4), dim=-1).view(N, -1).long()
+    mag = torch.tensor(_E2M1_VALUES, device=q.device, dtype=torch.float32)[codes & 7]
+    val = torch.where(codes >= 8, -mag, mag).view(N, -1, 32) * torch.exp2(scale.to(torch.float32) - 127.0)[:, :, None]
+    return val.view(N, -1).to(torch.bfloat16)
+
+
+def gemv_mxfp4w_supported(B: int, N: int, K: int) -> bool:
+    """Shapes ``gemv_mxfp4w`` serves (``K % 32 == 0``, ``B <= 4``, ``B * roundup(K, 2048) <= 32768``); others take fp8 or bf16."""
+    return bool(_lib.lib().rst_gemv_mxfp4w_supported(B, N, K))
+
+
+@_on_tensor_device
+def gemv_mxfp4w(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Optional[torch.Tensor] = None,
+                eps: float = 1e-8, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None, gate_out: bool = False) -> torch.Tensor:
+    """``gemv_bf16`` on MXFP4 weight storage: ``y[B,N] = (res +) (bias +) P(x) @ dequantize_blocks_mxfp4(q, scale).T`` with ``q`` packed
+    e2m1 codes ``[N,K/2]`` and one scale byte per 32 ``k`` (``quantize_blocks_mxfp4``; rst_gemv_mxfp4w_f32)."""
+    _chk(x, "x")
+    _chk(q, "q", torch.uint8)
+    _chk(scale, "scale", torch.uint8)
+    _chk(alpha, "alpha")
+    _chk(res, "res")
+    _chk(bias, "bias")
+    B = x.shape[0]
+    N, K = q.shape[0], 2 * q.shape[1]
+    assert K % 32 == 0 and scale.shape == (N, K // 32), (tuple(q.shape), tuple(scale.shape))
+    assert x.shape[1] == (2 * K if prologue == PROLOGUE_SILU_GATE else K), (tuple(x.shape), N, K, prologue)
+    No = N // 2 if gate_out else N
+    if out is None:
+        out = torch.empty(B, No, device=x.device, dtype=torch.float32)
+    with _profiled("gemv_mxfp4w", 2.0 * B * N * K, N * K // 2 + N * K // 32 + 4 * (x.numel() + out.numel()), (B, N, K)):
+        _lib.check(_lib.lib().rst_gemv_mxfp4w_f32(_ptr(x), _ptr(alpha), _ptr(q), _ptr(scale), _ptr(res), _ptr(bias), _ptr(out), B, N, K,
+                                                 x.shape[1], No, prologue, eps, int(gate_out), _stream()))
+    return out
+
+
 # Measured on MI355X (tools/bench_depth.py, graph-replayed chains at the depth transformer's shape): the out-projection with the
 # attention as its prologue costs 8.8 us per launch against 4.0 us (plain out-projection) + 3.2 us (attn_small) for the two
 # launches it replaces -- the prologue's dependent chain (qkv row -> 16 K/V rows -> scores -> softmax -> LDS) is longer than a
@@ -1090,7 +1158,11 @@ def _gemv_route(B: int, K: int) -> bool:
 
 
 def _w8_usable(w8, B: int, w: torch.Tensor) -> bool:
-    return w8 is not None and gemv_fp8w_supported(B, w.shape[0], w.shape[1])
+    return w8 is not None and not isinstance(w8, Mxfp4Copy) and gemv_fp8w_supported(B, w.shape[0], w.shape[1])
+
+
+def _w4_usable(w8, B: int, w: torch.Tensor) -> bool:
+    return isinstance(w8, Mxfp4Copy) and gemv_mxfp4w_supported(B, w.shape[0], w.shape[1])
 
 
 @_on_tensor_device
@@ -1100,14 +1172,19 @@ def lm_gated_pair(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, *, a
     """The gated MLP of a decode step: ``res + W_out (silu(u) * v)``, ``[u ; v] = W_in rmsnorm(x)`` (modules/gating.py:12-51,
     lit_model.py:399-403).  Batch <= 2: two GEMVs, the gate in the epilogue of the first (row pairs per wave).  Above: the first skinny GEMM applies
     the gate in its epilogue and hands the packed operand straight to the second -- the gated activation never exists in fp32.
-    ``w8_in`` / ``w8_out``: ``(q, scale)`` fp8 copies of the two weights (``quantize_rows_fp8``), read by the GEMV pair only."""
+    ``w8_in`` / ``w8_out``: ``(q, scale)`` fp8 copies of the two weights (``quantize_rows_fp8``), read by the GEMV pair only.
+    Either may instead be an ``Mxfp4Copy`` (``quantize_blocks_mxfp4``): the same rule, streamed by ``gemv_mxfp4w``."""
     B = x.shape[0]
     if not fp8 and B <= 2 and B * max(w_out.shape[1], w_in.shape[1]) <= 32768 and w_in.shape[0] % 2 == 0:
         # GEMV pair: every wave of the first owns a (u, v) row pair and writes silu(u) * v; the second is a plain GEMV
-        if _w8_usable(w8_in, B, w_in):
+        if _w4_usable(w8_in, B, w_in):
+            g = gemv_mxfp4w(x, w8_in[0], w8_in[1], prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, gate_out=True)
+        elif _w8_usable(w8_in, B, w_in):
             g = gemv_fp8w(x, w8_in[0], w8_in[1], prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, gate_out=True)
         else:
             g = gemv_bf16(x, w_in, prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, gate_out=True)
+        if _w4_usable(w8_out, B, w_out):
+            return gemv_mxfp4w(g, w8_out[0], w8_out[1], res=res, bias=bias_out)
         if _w8_usable(w8_out, B, w_out):
             return gemv_fp8w(g, w8_out[0], w8_out[1], res=res, bias=bias_out)
         return gemv_bf16(g, w_out, res=res, bias=bias_out)
@@ -1125,7 +1202,8 @@ def lm_linear(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE
     """Batch-size dispatch of one decode-step linear: weight-streaming GEMV for B <= 2, bf16-MFMA skinny GEMM above (the
     prologue then runs inside the activation-packing launch).  ``fp8``: the opt-in e4m3 path (any batch <= 64).
     ``w8 = (q, scale)``: an fp8 copy of ``w`` holding the SAME values (``quantize_rows_fp8`` of a weight that was overwritten with its
-    dequantised form): the GEMV route streams it instead of ``w``; every other route reads ``w``."""
+    dequantised form): the GEMV route streams it instead of ``w``; every other route reads ``w``.  ``w8`` may instead be an ``Mxfp4Copy``
+    (``quantize_blocks_mxfp4``) under the same rule: the GEMV route then streams it with ``gemv_mxfp4w``."""
     if isinstance(x, PackedAct):
         return gemm_skinny(x, w, prologue=prologue, res=res, bias=bias)
     if fp8 and x.shape[0] <= 64 and w.shape[1] % 32 == 0 and w.shape[1] <= 16384:
@@ -1133,6 +1211,8 @@ def lm_linear(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE
     # the GEMV stages B x K fp32 activations in LDS: beyond two rows that footprint costs occupancy (fewer weight loads in
     # flight) and the matrix-core path is as fast or faster (measured: 4096 x 4096 at B = 3: 16.4 vs 16.5 us, B = 4: 20.9 vs 16.5)
     if _gemv_route(x.shape[0], w.shape[1]):
+        if _w4_usable(w8, x.shape[0], w):
+            return gemv_mxfp4w(x, w8[0], w8[1], prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
         if _w8_usable(w8, x.shape[0], w):
             return gemv_fp8w(x, w8[0], w8[1], prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
         return gemv_bf16(x, w, prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)

@@ -267,9 +267,10 @@ def main(argv=None) -> None:
     p.add_argument("--synthetic", action="store_true", help="seeded random-init weights of the real shapes (no checkpoints needed)")
     p.add_argument("--lm-config", choices=["moshi7b", "tiny"], default="moshi7b")
     p.add_argument("--device", type=str, default="cuda")
-    p.add_argument("--lm-weights", choices=["bf16", "fp8"], default="bf16",
-                   help="storage of the LM's streamed weights: fp8 = e4m3 weight-only copies for the batch-1 step (LMModel.quantize_weights_; "
-                        "speech quality under fp8 weights has not been evaluated)")
+    p.add_argument("--lm-weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
+                   help="storage of the LM's streamed weights: fp8 = e4m3 weight-only copies for the batch-1 step, mxfp4 = OCP MXFP4 copies "
+                        "of the temporal stack's per-layer matrices with the heads at fp8 (LMModel.quantize_weights_; speech quality "
+                        "under fp8 or mxfp4 weights has not been evaluated)")
     args = p.parse_args(argv)
     if not args.synthetic and not (args.moshi_weight and args.mimi_weight):
         p.error("give --moshi-weight and --mimi-weight, or --synthetic")

@@ -3,6 +3,7 @@
     python tools/bench_kernels.py [case ...]        cases: res64 res64pre res64post res128 gemm:<M>x<N>x<K>[:elu]
                                                            conv:<B>x<T>x<Cin>x<N>x<Kw>x<S>[:elu][:res] ...
                                                            gemv:<B>x<N>x<K>[:norm|normgate|gate]  gemv8:<B>x<N>x<K>[:...] (fp8 weights)
+                                                           gemv4:<B>x<N>x<K>[:...] (MXFP4 weights)
 """
 import os
 import sys
@@ -109,13 +110,18 @@ def skinny_case(B, N, K, gate=False):
     return ms, 2.0 * N * K
 
 
-def gemv_case(B, N, K, mode="plain", copies=None, fp8=False):
+def gemv_case(B, N, K, mode="plain", copies=None, fp8=False, fp4=False):
     """Batch <= 2 GEMV over ROTATING weight copies (> 1 GB in total, so no launch finds its weights in the 256 MB MALL).
-    ``fp8``: the same launch on fp8 weight storage (ops.gemv_fp8w: e4m3 bytes + one scale per row, half the bytes per copy)."""
+    ``fp8``: the same launch on fp8 weight storage (ops.gemv_fp8w: e4m3 bytes + one scale per row, half the bytes per copy).
+    ``fp4``: on MXFP4 storage (ops.gemv_mxfp4w: e2m1 codes + one scale byte per 32 k, N*K/2 + N*K/32 bytes per copy)."""
     g = torch.Generator().manual_seed(0)
-    copies = copies or max(2, int(1.5e9 // ((1 if fp8 else 2) * N * K)) + 1)
+    copies = copies or max(2, int(1.5e9 // ((0.53125 if fp4 else 1 if fp8 else 2) * N * K)) + 1)
     ws = [(torch.randn(N, K, device=DEV) * 0.05).bfloat16()]
-    if fp8:
+    if fp4:
+        q, sc = ops.quantize_blocks_mxfp4(ws[0])
+        ws = [(q, sc)] + [(q.clone(), sc.clone()) for _ in range(copies - 1)]
+        gemv = lambda x, w, **kw: ops.gemv_mxfp4w(x, w[0], w[1], **kw)      # noqa: E731
+    elif fp8:
         q, sc = ops.quantize_rows_fp8(ws[0])
         ws = [(q, sc)] + [(q.clone(), sc.clone()) for _ in range(copies - 1)]
         gemv = lambda x, w, **kw: ops.gemv_fp8w(x, w[0], w[1], **kw)      # noqa: E731
@@ -138,23 +144,23 @@ def gemv_case(B, N, K, mode="plain", copies=None, fp8=False):
             gemv(x, w, res=r, prologue=ops.PROLOGUE_SILU_GATE)
         else:
             gemv(x, w, res=r)
-    return fn, max(copies, 48), (1.0 * N * K + 4 * N) if fp8 else 2.0 * N * K
+    return fn, max(copies, 48), (0.53125 * N * K) if fp4 else (1.0 * N * K + 4 * N) if fp8 else 2.0 * N * K
 
 
 def gemv_cases(cases):
     """python tools/bench_kernels.py gemv:BxNxK[:norm|normgate|gate] gemv8:BxNxK[:...] ...   -- graph-timed, weights rotating through
-    > 1 GB; gemv8 = the fp8 weight-only form of the same launch (TB/s of ITS bytes: N*K + 4*N)."""
+    > 1 GB; gemv8 = the fp8 weight-only form of the same launch (TB/s of ITS bytes: N*K + 4*N), gemv4 = the MXFP4 form (N*K/2 + N*K/32)."""
     for c in cases:
         parts = c.split(":")
         Bq, N, K = [int(v) for v in parts[1].split("x")]
         mode = parts[2] if len(parts) > 2 else "plain"
-        fn, iters, nbytes = gemv_case(Bq, N, K, mode, fp8=parts[0] == "gemv8")
+        fn, iters, nbytes = gemv_case(Bq, N, K, mode, fp8=parts[0] == "gemv8", fp4=parts[0] == "gemv4")
         ms = timeit_graph(fn, iters=iters)
         print(f"{c:28s} {ms * 1e3:6.1f} us {nbytes / ms / 1e9:5.2f} TB/s", flush=True)
 
 
 def main():
-    if len(sys.argv) > 1 and all(a.startswith(("gemv:", "gemv8:")) for a in sys.argv[1:]):
+    if len(sys.argv) > 1 and all(a.startswith(("gemv:", "gemv8:", "gemv4:")) for a in sys.argv[1:]):
         return gemv_cases(sys.argv[1:])
     cases = sys.argv[1:] or ["res64", "res64pre", "res64post", "res128", "gemm:3840000x128x512:elu", "gemm:16000x1024x8192",
                              "gemm:128000x512x3072", "gemm:16000x512x512"]
