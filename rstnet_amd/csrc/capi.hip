@@ -347,6 +347,15 @@ int rst_gemv_bf16_f32(const float* x, const float* alpha, const uint16_t* w, con
     return rst_launch_gemv(p, (hipStream_t)stream);
 }
 
+static GemvQuantParams gemv_quant_params(const float* x, const float* alpha, const uint8_t* q, const void* scale, const float* res,
+                                         const float* bias, float* y, int B, int N, int K, int ldx, int ldy, int prologue, float eps,
+                                         int gate_out) {
+    GemvQuantParams p;
+    p.x = x; p.alpha = alpha; p.q = q; p.scale = scale; p.res = res; p.bias = bias; p.y = y; p.B = B; p.N = N;
+    p.K = K; p.ldx = ldx; p.ldy = ldy; p.prologue = prologue; p.gate_out = gate_out; p.eps = eps;
+    return p;
+}
+
 int rst_quant_rows_fp8(const uint16_t* w, uint8_t* q, float* scale, int N, int K, rst_stream_t stream) {
     return rst_launch_quant_rows_fp8(w, q, scale, N, K, (hipStream_t)stream);
 }
@@ -355,10 +364,7 @@ int rst_gemv_fp8w_supported(int B, int N, int K) { return rst_gemv_fp8w_supporte
 
 int rst_gemv_fp8w_f32(const float* x, const float* alpha, const uint8_t* q, const float* scale, const float* res, const float* bias,
                       float* y, int B, int N, int K, int ldx, int ldy, int prologue, float eps, int gate_out, rst_stream_t stream) {
-    GemvFp8Params p;
-    p.x = x; p.alpha = alpha; p.q = q; p.scale = scale; p.res = res; p.bias = bias; p.y = y; p.B = B; p.N = N;
-    p.K = K; p.ldx = ldx; p.ldy = ldy; p.prologue = prologue; p.gate_out = gate_out; p.eps = eps;
-    return rst_launch_gemv_fp8w(p, (hipStream_t)stream);
+    return rst_launch_gemv_fp8w(gemv_quant_params(x, alpha, q, scale, res, bias, y, B, N, K, ldx, ldy, prologue, eps, gate_out), (hipStream_t)stream);
 }
 
 int rst_quant_blocks_mxfp4(const uint16_t* w, uint8_t* q, uint8_t* scale, int N, int K, rst_stream_t stream) {
@@ -369,10 +375,7 @@ int rst_gemv_mxfp4w_supported(int B, int N, int K) { return rst_gemv_mxfp4w_supp
 
 int rst_gemv_mxfp4w_f32(const float* x, const float* alpha, const uint8_t* q, const uint8_t* scale, const float* res, const float* bias,
                         float* y, int B, int N, int K, int ldx, int ldy, int prologue, float eps, int gate_out, rst_stream_t stream) {
-    GemvFp4Params p;
-    p.x = x; p.alpha = alpha; p.q = q; p.scale = scale; p.res = res; p.bias = bias; p.y = y; p.B = B; p.N = N;
-    p.K = K; p.ldx = ldx; p.ldy = ldy; p.prologue = prologue; p.gate_out = gate_out; p.eps = eps;
-    return rst_launch_gemv_mxfp4w(p, (hipStream_t)stream);
+    return rst_launch_gemv_mxfp4w(gemv_quant_params(x, alpha, q, scale, res, bias, y, B, N, K, ldx, ldy, prologue, eps, gate_out), (hipStream_t)stream);
 }
 
 int rst_gemv_attn_bf16_f32(const float* qkv, float* k_cache, float* v_cache, const int64_t* pos_dev, const uint16_t* w,

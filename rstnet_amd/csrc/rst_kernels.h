@@ -452,38 +452,25 @@ int rst_launch_skinny_pack_weight(const unsigned short* w, unsigned short* wp, i
 int rst_launch_skinny_pack_act(const float* x, const float* alpha, unsigned short* xp, int B, int K, int ldx, int mode, float eps,
                                hipStream_t stream);
 
-// ---- lm_gemv_fp8.hip: the small-batch GEMV on fp8 (OCP e4m3fn) weights with one power-of-two scale per row, and its quantiser
-struct GemvFp8Params {
+// ---- lm_gemv_fp8.hip, lm_gemv_fp4.hip: the small-batch GEMV on quantised weights (schedules: lm_gemv_quant.h) and the quantisers.
+// fp8: OCP e4m3fn bytes with one power-of-two fp32 scale per row.  MXFP4: OCP e2m1 codes with one power-of-two scale byte per 32 k.
+struct GemvQuantParams {
     const float* x;             // [B][ldx] fp32 activations (prologue 2: [B][2K] = [u ; v])
     const float* alpha;         // prologue 1: RMSNorm gain [K]
-    const unsigned char* q;     // [N][K] e4m3fn bytes
-    const float* scale;         // [N] row scales: multiply the dot product only (the bias is added after the scale)
+    const unsigned char* q;     // fp8: [N][K] e4m3fn bytes; MXFP4: [N][K / 2] e2m1 codes, two per byte, even k in the low nibble
+    const void* scale;          // fp8: float [N] row scales; MXFP4: unsigned char [N][K / 32] block scales e + 127.  Either multiplies
+                                // the weights' products only (the bias is added unscaled)
     const float* res;           // optional [B][ldy]
     const float* bias;          // optional [N]
     float* y;                   // [B][ldy]
     int B, N, K, ldx, ldy;
     int prologue;               // 0 none, 1 RMSNorm, 2 SiLU gate
-    int gate_out;               // N even, no res: y[b][n] = silu(row n) * (row N/2 + n), n < N/2, each row with its own scale
+    int gate_out;               // N even, no res: y[b][n] = silu(row n) * (row N/2 + n), n < N/2, each row with its own scale(s)
     float eps;
 };
 int rst_gemv_fp8w_supported_impl(int B, int N, int K);
-int rst_launch_gemv_fp8w(const GemvFp8Params& p, hipStream_t stream);
+int rst_launch_gemv_fp8w(const GemvQuantParams& p, hipStream_t stream);
 int rst_launch_quant_rows_fp8(const unsigned short* w, unsigned char* q, float* scale, int N, int K, hipStream_t stream);
-
-// ---- lm_gemv_fp4.hip: the small-batch GEMV on MXFP4 weights (OCP e2m1 codes, one power-of-two scale byte per 32 k), and its quantiser
-struct GemvFp4Params {
-    const float* x;             // [B][ldx] fp32 activations (prologue 2: [B][2K] = [u ; v])
-    const float* alpha;         // prologue 1: RMSNorm gain [K]
-    const unsigned char* q;     // [N][K / 2] e2m1 codes, two per byte, even k in the low nibble
-    const unsigned char* scale; // [N][K / 32] block scales e + 127: multiply the block's products only (the bias is added unscaled)
-    const float* res;           // optional [B][ldy]
-    const float* bias;          // optional [N]
-    float* y;                   // [B][ldy]
-    int B, N, K, ldx, ldy;
-    int prologue;               // 0 none, 1 RMSNorm, 2 SiLU gate
-    int gate_out;               // N even, no res: y[b][n] = silu(row n) * (row N/2 + n), n < N/2
-    float eps;
-};
 int rst_gemv_mxfp4w_supported_impl(int B, int N, int K);
-int rst_launch_gemv_mxfp4w(const GemvFp4Params& p, hipStream_t stream);
+int rst_launch_gemv_mxfp4w(const GemvQuantParams& p, hipStream_t stream);
 int rst_launch_quant_blocks_mxfp4(const unsigned short* w, unsigned char* q, unsigned char* scale, int N, int K, hipStream_t stream);

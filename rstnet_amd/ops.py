@@ -864,29 +864,36 @@ def gemv_fp8w_supported(B: int, N: int, K: int) -> bool:
     return bool(_lib.lib().rst_gemv_fp8w_supported(B, N, K))
 
 
+def _gemv_quant(op: str, x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, K: int, scale_dtype, scale_shape: tuple, wbytes: int,
+                prologue: int, alpha, eps: float, res, bias, out, gate_out: bool) -> torch.Tensor:
+    """The body of ``gemv_fp8w`` and ``gemv_mxfp4w``: argument checks, output, the profile row ``op`` and the launch ``rst_<op>_f32``.
+    ``K``, the scales' dtype and shape and ``wbytes`` (weight + scale bytes streamed) are what the two formats differ in."""
+    _chk(x, "x")
+    _chk(q, "q", torch.uint8)
+    _chk(scale, "scale", scale_dtype)
+    _chk(alpha, "alpha")
+    _chk(res, "res")
+    _chk(bias, "bias")
+    B, N = x.shape[0], q.shape[0]
+    assert scale.shape == scale_shape, (tuple(q.shape), tuple(scale.shape))
+    assert x.shape[1] == (2 * K if prologue == PROLOGUE_SILU_GATE else K), (tuple(x.shape), N, K, prologue)
+    No = N // 2 if gate_out else N
+    if out is None:
+        out = torch.empty(B, No, device=x.device, dtype=torch.float32)
+    with _profiled(op, 2.0 * B * N * K, wbytes + 4 * (x.numel() + out.numel()), (B, N, K)):
+        _lib.check(getattr(_lib.lib(), f"rst_{op}_f32")(_ptr(x), _ptr(alpha), _ptr(q), _ptr(scale), _ptr(res), _ptr(bias), _ptr(out), B, N, K,
+                                                       x.shape[1], No, prologue, eps, int(gate_out), _stream()))
+    return out
+
+
 @_on_tensor_device
 def gemv_fp8w(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Optional[torch.Tensor] = None,
               eps: float = 1e-8, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
               out: Optional[torch.Tensor] = None, gate_out: bool = False) -> torch.Tensor:
     """``gemv_bf16`` on fp8 weight storage: ``y[B,N] = (res +) (bias +) scale * (P(x) @ q.T)`` with ``q`` e4m3fn bytes ``[N,K]`` and
     one fp32 scale per row (``quantize_rows_fp8``; rst_gemv_fp8w_f32).  The scale multiplies the dot product only."""
-    _chk(x, "x")
-    _chk(q, "q", torch.uint8)
-    _chk(scale, "scale")
-    _chk(alpha, "alpha")
-    _chk(res, "res")
-    _chk(bias, "bias")
-    B = x.shape[0]
     N, K = q.shape
-    assert scale.shape == (N,), (tuple(scale.shape), N)
-    assert x.shape[1] == (2 * K if prologue == PROLOGUE_SILU_GATE else K), (tuple(x.shape), N, K, prologue)
-    No = N // 2 if gate_out else N
-    if out is None:
-        out = torch.empty(B, No, device=x.device, dtype=torch.float32)
-    with _profiled("gemv_fp8w", 2.0 * B * N * K, N * K + 4 * N + 4 * (x.numel() + out.numel()), (B, N, K)):
-        _lib.check(_lib.lib().rst_gemv_fp8w_f32(_ptr(x), _ptr(alpha), _ptr(q), _ptr(scale), _ptr(res), _ptr(bias), _ptr(out), B, N, K, x.shape[1],
-                                               No, prologue, eps, int(gate_out), _stream()))
-    return out
+    return _gemv_quant("gemv_fp8w", x, q, scale, K, torch.float32, (N,), N * K + 4 * N, prologue, alpha, eps, res, bias, out, gate_out)
 
 
 _E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
@@ -938,23 +945,10 @@ def gemv_mxfp4w(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, *, prolog
                 out: Optional[torch.Tensor] = None, gate_out: bool = False) -> torch.Tensor:
     """``gemv_bf16`` on MXFP4 weight storage: ``y[B,N] = (res +) (bias +) P(x) @ dequantize_blocks_mxfp4(q, scale).T`` with ``q`` packed
     e2m1 codes ``[N,K/2]`` and one scale byte per 32 ``k`` (``quantize_blocks_mxfp4``; rst_gemv_mxfp4w_f32)."""
-    _chk(x, "x")
-    _chk(q, "q", torch.uint8)
-    _chk(scale, "scale", torch.uint8)
-    _chk(alpha, "alpha")
-    _chk(res, "res")
-    _chk(bias, "bias")
-    B = x.shape[0]
     N, K = q.shape[0], 2 * q.shape[1]
-    assert K % 32 == 0 and scale.shape == (N, K // 32), (tuple(q.shape), tuple(scale.shape))
-    assert x.shape[1] == (2 * K if prologue == PROLOGUE_SILU_GATE else K), (tuple(x.shape), N, K, prologue)
-    No = N // 2 if gate_out else N
-    if out is None:
-        out = torch.empty(B, No, device=x.device, dtype=torch.float32)
-    with _profiled("gemv_mxfp4w", 2.0 * B * N * K, N * K // 2 + N * K // 32 + 4 * (x.numel() + out.numel()), (B, N, K)):
-        _lib.check(_lib.lib().rst_gemv_mxfp4w_f32(_ptr(x), _ptr(alpha), _ptr(q), _ptr(scale), _ptr(res), _ptr(bias), _ptr(out), B, N, K,
-                                                 x.shape[1], No, prologue, eps, int(gate_out), _stream()))
-    return out
+    assert K % 32 == 0, tuple(q.shape)
+    return _gemv_quant("gemv_mxfp4w", x, q, scale, K, torch.uint8, (N, K // 32), N * K // 2 + N * K // 32, prologue, alpha, eps, res, bias, out,
+                       gate_out)
 
 
 # Measured on MI355X (tools/bench_depth.py, graph-replayed chains at the depth transformer's shape): the out-projection with the
@@ -1157,12 +1151,16 @@ def _gemv_route(B: int, K: int) -> bool:
     return B <= 2 and B * K <= 32768
 
 
-def _w8_usable(w8, B: int, w: torch.Tensor) -> bool:
-    return w8 is not None and not isinstance(w8, Mxfp4Copy) and gemv_fp8w_supported(B, w.shape[0], w.shape[1])
-
-
-def _w4_usable(w8, B: int, w: torch.Tensor) -> bool:
-    return isinstance(w8, Mxfp4Copy) and gemv_mxfp4w_supported(B, w.shape[0], w.shape[1])
+def _gemv_stored(x: torch.Tensor, w: torch.Tensor, copy, **kw) -> torch.Tensor:
+    """One GEMV of the weight-streaming route on the cheapest stored form of ``w`` that serves the shape: an ``Mxfp4Copy`` and
+    ``gemv_mxfp4w_supported``, else a plain ``(q, scale)`` fp8 pair and ``gemv_fp8w_supported``, else the bf16 ``w`` itself."""
+    B, (N, K) = x.shape[0], w.shape
+    if isinstance(copy, Mxfp4Copy):
+        if gemv_mxfp4w_supported(B, N, K):
+            return gemv_mxfp4w(x, copy[0], copy[1], **kw)
+    elif copy is not None and gemv_fp8w_supported(B, N, K):
+        return gemv_fp8w(x, copy[0], copy[1], **kw)
+    return gemv_bf16(x, w, **kw)
 
 
 @_on_tensor_device
@@ -1177,17 +1175,8 @@ def lm_gated_pair(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, *, a
     B = x.shape[0]
     if not fp8 and B <= 2 and B * max(w_out.shape[1], w_in.shape[1]) <= 32768 and w_in.shape[0] % 2 == 0:
         # GEMV pair: every wave of the first owns a (u, v) row pair and writes silu(u) * v; the second is a plain GEMV
-        if _w4_usable(w8_in, B, w_in):
-            g = gemv_mxfp4w(x, w8_in[0], w8_in[1], prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, gate_out=True)
-        elif _w8_usable(w8_in, B, w_in):
-            g = gemv_fp8w(x, w8_in[0], w8_in[1], prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, gate_out=True)
-        else:
-            g = gemv_bf16(x, w_in, prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, gate_out=True)
-        if _w4_usable(w8_out, B, w_out):
-            return gemv_mxfp4w(g, w8_out[0], w8_out[1], res=res, bias=bias_out)
-        if _w8_usable(w8_out, B, w_out):
-            return gemv_fp8w(g, w8_out[0], w8_out[1], res=res, bias=bias_out)
-        return gemv_bf16(g, w_out, res=res, bias=bias_out)
+        g = _gemv_stored(x, w_in, w8_in, prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, gate_out=True)
+        return _gemv_stored(g, w_out, w8_out, res=res, bias=bias_out)
     if fp8 or B <= 2 or B > 64 or w_in.shape[0] % 32:
         u = lm_linear(x, w_in, prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, fp8=fp8, w8=w8_in)
         return lm_linear(u, w_out, prologue=PROLOGUE_SILU_GATE, res=res, bias=bias_out, fp8=fp8, w8=w8_out)
@@ -1211,11 +1200,7 @@ def lm_linear(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE
     # the GEMV stages B x K fp32 activations in LDS: beyond two rows that footprint costs occupancy (fewer weight loads in
     # flight) and the matrix-core path is as fast or faster (measured: 4096 x 4096 at B = 3: 16.4 vs 16.5 us, B = 4: 20.9 vs 16.5)
     if _gemv_route(x.shape[0], w.shape[1]):
-        if _w4_usable(w8, x.shape[0], w):
-            return gemv_mxfp4w(x, w8[0], w8[1], prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
-        if _w8_usable(w8, x.shape[0], w):
-            return gemv_fp8w(x, w8[0], w8[1], prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
-        return gemv_bf16(x, w, prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
+        return _gemv_stored(x, w, w8, prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
     if x.shape[0] <= 64:
         return gemm_skinny(x, w, prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
     # more rows than one skinny tile set (prompt prefill): chunks of 64 rows, each streaming the weights once

@@ -9,7 +9,8 @@
 8  host logic: idempotence, state_dict, B = 8, no persistent temporal launch, the profile of an eager frame, quantising in a session;
 9  StreamingPipeline with a quantised LM against the composed oracles.
 
-Mutations built once while writing these tests (each in a scratch copy of csrc/lm_gemv_fp8.hip, all three schedules): applying row
+Mutations built once while writing these tests (each in a scratch copy of the kernels, all three schedules; the scale now
+multiplies in `sum` of the two schedules of csrc/lm_gemv_quant.h and in the K-split epilogue of csrc/lm_gemv_fp8.hip): applying row
 0's scale to every row fails every case of test_gemv_fp8w_elementwise_bound and test_decode_table; scaling the bias as well
 (``(acc + bias) * scale``) fails every case of test_gemv_fp8w_elementwise_bound that has a bias."""
 import math

@@ -10,7 +10,8 @@
 5  the model: host logic, route equivalence against a plain bf16 LMModel on the dequantised state dict, the CPU oracle fed the
    dequantised weights (logits, greedy LMGen tokens), no persistent temporal launch, StreamingPipeline.
 
-Mutations built once while writing these tests (each in a scratch copy of csrc/lm_gemv_fp4.hip, every schedule): block 0's
+Mutations built once while writing these tests (each in a scratch copy of the kernels, every schedule; scale byte and nibble order
+now live in W4Chunk of csrc/lm_gemv_fp4.hip, the bias in the epilogues of csrc/lm_gemv_quant.h): block 0's
 scale byte for every block of a row fails every case of test_decode_table and every case of test_gemv_mxfp4w_elementwise_bound with
 more than one block per row (the eight K = 32 cases pass, as they must); swapped nibbles (the two weights of a byte exchanged) fail
 every case of both; the scale applied to the bias as well (``bias * 2^e`` of the row's first block) fails every case of
