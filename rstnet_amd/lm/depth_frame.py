@@ -116,6 +116,30 @@ class DepthDecoder:
         """``step_hidden`` + head ``k`` -> logits fp32 ``[B, card]``."""
         return ops.lm_linear(self.step_hidden(k, tokens, col, h, **step), self.heads[k].weight, bias=self._head_bias(k))
 
+    def forward_local(self, start: torch.Tensor, sequence: torch.Tensor, transformer_out: torch.Tensor) -> torch.Tensor:
+        """Teacher-forced depth logits: ``start`` = the text ids int64 ``[B, T]`` or their float embedding ``[B, T, E]``, ``sequence`` int64
+        ``[B, dep_q, T]``, ``transformer_out`` ``[B, T, dim]`` -> ``[B, T, dep_q, card]``: ``dep_q`` steps over ``B * T`` rows on a throw-away
+        ring that never fills."""
+        B, K, T = sequence.shape
+        assert K == len(self.heads), f"Sequence shape {sequence.shape} must match the moshi stream output."
+        dep, N = self.dep, B * T
+        saved = dep._streaming_state
+        dep._streaming_state = dep._init_streaming_state(N, capacity=K + 1)
+        try:
+            h = transformer_out.reshape(N, -1).float().contiguous()
+            outs = []
+            for k in range(K):
+                w = self.in_proj[k].weight
+                if k == 0 and start.dtype != torch.long:
+                    x = ops.lm_linear(h, w, res=start.reshape(N, -1).float().contiguous())
+                else:
+                    prev = start if k == 0 else sequence[:, k - 1]
+                    x = ops.embed_sum(prev.reshape(N, 1).contiguous(), [self.emb[k].weight], [0], add=ops.lm_linear(h, w))
+                outs.append(ops.lm_linear(dep.step(x), self.heads[k].weight, bias=self._head_bias(k)).view(B, T, 1, -1))
+        finally:
+            dep._streaming_state = saved
+        return torch.cat(outs, dim=2)
+
     def decode_frame(self, tokens: torch.Tensor, h: torch.Tensor, noise: Optional[torch.Tensor], pos: torch.Tensor, *, use_sampling: bool,
                      temp: float, top_k: int, limits: Optional[torch.Tensor] = None, rings=None, w8: Optional[tuple] = None, keep=None,
                      persistent: bool = True) -> None:

@@ -161,7 +161,7 @@ class GPTGen:
             self._fused = _Graphed(self._step_fn)
         self._frames += 1
         self._g_idx += 1
-        # (a graph replay advances the device counter only; `prefill` decides its route from the host mirror: lm.gpt.counted_step)
+        # (a graph replay advances the device counter only; `prefill` decides its route from the host mirror: lm.stack.counted_step)
         self.last_h, self.last_logits = counted_step(self.model.transformer._streaming_state, self._fused)
         return col[:, 0], col[:, 1:cfg.dep_q + 1]
 

@@ -36,60 +36,9 @@ from ..packed import _PackedCache
 from .depth_frame import DepthDecoder
 from . import model as _lm_model       # PREFILL_CHUNK is read at call time
 from .model import RMSNorm as _AlphaNorm  # noqa: F401  (key layout of the codecformer norms)
-from .model import ScaledEmbedding, StreamingTransformer, _StepState, _Weight, adopt_state_dict
-
-KV_DTYPES = (torch.float32, torch.bfloat16)
-ROUTE_APPEND_FIRST = "append_first"      # lm_rope_append, then attention over the ring: fp32 rings that the chunk does not fill
-ROUTE_PREFILL = "prefill"                # lm_attn_prefill against ring + chunk, then lm_ring_append (csrc/lm_prefill.hip)
-
-
-def prefill_window(context: Optional[int], cap: int) -> int:
-    """Keys a query of a multi-position pass sees on a ring of ``cap`` slots, itself included: what ``T`` single steps see there --
-    the context, and never more than ``cap - 1`` because the step kernels hide the oldest slot of a full ring (the rule of
-    ``StreamingTransformer.window``).  ``GPTGen``'s rings of ``context + 1`` slots give the plain context."""
-    return min(context, cap - 1) if context else cap - 1
-
-
-def prefill_route(cap: int, pos: int, T: int, kv_dtype: torch.dtype) -> str:
-    """Route of ``T`` new positions behind ``pos`` appended ones on a ring of ``cap`` slots.  Appending first is only right while the
-    ring is not full after the chunk, ``pos + T < cap``, and its kernels read fp32 rings only.  (``pos + T > cap`` rewrites slots the
-    chunk's earlier queries still see; at ``pos + T == cap`` nothing is rewritten, but those kernels apply the slot -> position map of
-    the ring as it is AFTER the chunk to every query, and on a ring that is exactly full that map hides the oldest slot, SURVEY Q1:
-    position 0 is lost to queries that single steps let see it.)  Everything else attends before it appends."""
-    if kv_dtype == torch.float32 and pos + T < cap:
-        return ROUTE_APPEND_FIRST
-    return ROUTE_PREFILL
-
-
-def prefill_chunks(cap: int, pos: int, T: int, kv_dtype: torch.dtype, chunk: int) -> list:
-    """``[(t0, Tc, route)]`` of a ``T``-position call: a call that appends first as a whole stays ONE pass (the launches it always
-    took); otherwise position chunks of ``min(chunk, cap)``, each with its own route."""
-    if prefill_route(cap, pos, T, kv_dtype) == ROUTE_APPEND_FIRST:
-        return [(0, T, ROUTE_APPEND_FIRST)]
-    step = min(chunk, cap)
-    return [(t0, min(step, T - t0), prefill_route(cap, pos + t0, min(step, T - t0), kv_dtype)) for t0 in range(0, T, step)]
-
-
-def counted_step(st: _StepState, step, *args):
-    """Run ONE T = 1 step of the global transformer through ``step`` -- a ``Graphed`` callable or a plain one -- and leave the host
-    mirror ``st.offset_cpu`` one further, whether Python ran (warm-up, capture, eager: ``_blocks`` counted already) or a graph was
-    replayed (the device counter ``st.pos`` moved, no Python ran).  ``prefill_chunks`` decides the route of a later ``T > 1`` call from
-    that mirror without a device synchronisation, and a mirror that lags sends a chunk across the wrap down the append-first route:
-    wrong values, no error.  So EVERY caller that may replay a captured step goes through here, and code that moves ``st.pos`` by hand
-    (a benchmark that seeds a full ring) sets ``st.offset_cpu`` with it."""
-    at = st.offset_cpu
-    out = step(*args)
-    st.offset_cpu = at + 1
-    return out
-
-
-def check_kv_dtype(kv_dtype: torch.dtype, capacity: Optional[int] = None) -> None:
-    """The one place that says which ring dtypes exist, and (given a capacity) which rings can hold them."""
-    if kv_dtype not in KV_DTYPES:
-        raise ValueError(f"kv_dtype {kv_dtype}: the KV rings are torch.float32 or torch.bfloat16")
-    if kv_dtype == torch.bfloat16 and capacity is not None and capacity <= 64:
-        raise ValueError(f"kv_dtype=torch.bfloat16 on a ring of {capacity} slots: rings of <= 64 slots are read by the short-ring decode "
-                         "kernel, which reads fp32 only; use kv_dtype=torch.float32 or a context above 64")
+from .model import ScaledEmbedding, StreamingTransformer, _Weight, adopt_state_dict
+from .stack import KV_DTYPES, ROUTE_APPEND_FIRST, ROUTE_PREFILL, prefill_route, prefill_window  # noqa: F401  (the route rules, under the names callers know)
+from .stack import ROUTE_DECODE, Geometry, LayerView, LinearView, _lora_add, _StepState, check_kv_dtype, counted_step, prefill_chunks, run_chunks
 
 
 @dataclass
@@ -318,17 +267,6 @@ def _pad_rank(A: torch.Tensor, Bm: torch.Tensor, scale: float):
     return Ap.contiguous(), Bp.contiguous(), (1.0 if fold else float(scale))
 
 
-def _lora_add(y: torch.Tensor, x, ad, **prologue) -> torch.Tensor:
-    """``y + B (scaling * (A P(x)))`` -- the unmerged LoRA branch (llama_streaming.py:136-143) as two thin products."""
-    if ad is None:
-        return y
-    A, Bm, scale = ad
-    a = ops.lm_linear(x, A, **prologue)
-    if scale != 1.0:
-        a = a * scale
-    return ops.lm_linear(a, Bm, res=y)
-
-
 # ----------------------------------------------------------------------------------------------------------------- modules
 class _Linear(nn.Module):
     """``<name>.linear.{weight,bias}`` holder (a merged LoRALinear)."""
@@ -497,6 +435,14 @@ class Block(nn.Module):
         self.norm_2 = _LitNorm(config.n_embd, config.norm_eps, **fk)
         self.mlp = LLaMAMLP(config, **fk)
 
+    def view(self) -> LayerView:
+        """The block as ``stack.run_layers`` reads it: packed weights and biases, unmerged adapters in kernel form."""
+        att, mlp = self.attn, self.mlp
+        (wqkv, bqkv), (wfc, bfc) = att.packed_qkv(), mlp.packed_fc()
+        return LayerView(LinearView(wqkv, bqkv, lora=att.packed_qkv_adapter()), LinearView(att.proj.weight, att.proj.bias_f32(), lora=att.proj.adapter()),
+                         LinearView(wfc, bfc, lora=mlp.packed_fc_adapter()), LinearView(mlp.proj.weight, mlp.proj.bias_f32(), lora=mlp.proj.adapter()),
+                         (self.norm_1.gain_f32(), self.norm_1.eps), (self.norm_2.gain_f32(), self.norm_2.eps))
+
 
 class LLAMAStreamingTransformer(StreamingModule[_StepState]):
     """llama_streaming.py:775-800: ``wte`` + blocks + ``ln_f``; the streaming state holds the grouped KV rings."""
@@ -515,16 +461,7 @@ class LLAMAStreamingTransformer(StreamingModule[_StepState]):
         c = self.config
         kvd = self.kv_dtype if kv_dtype is None else kv_dtype
         check_kv_dtype(kvd, capacity)
-        dev = self.ln_f.weight.device
-        shape = (batch_size, c.n_query_groups, capacity, c.head_size)
-        scratch = None
-        if capacity > 64:
-            splits = ops.lm_attn_splits(capacity, batch_size * c.n_head)
-            scratch = (torch.empty(batch_size, c.n_head, splits, c.head_size + 2, device=dev),
-                       torch.zeros(batch_size, c.n_head, device=dev, dtype=torch.int32))
-        return _StepState([torch.zeros(shape, device=dev, dtype=kvd) for _ in self.h],
-                          [torch.zeros(shape, device=dev, dtype=kvd) for _ in self.h],
-                          torch.zeros(1, device=dev, dtype=torch.long), scratch)
+        return _StepState.make(batch_size, c.n_query_groups, c.n_head, c.head_size, capacity, kvd, self.ln_f.weight.device, len(self.h))
 
     def _init_streaming_state(self, batch_size: int) -> _StepState:
         if self.config.context is None:
@@ -536,63 +473,11 @@ class LLAMAStreamingTransformer(StreamingModule[_StepState]):
         entry of ``prefill_chunks`` (decided from the host counter ``st.offset_cpu``), equal to the same positions fed one at a time
         on any ring -- empty, partly filled or wrapped, fp32 or bf16."""
         c = self.config
-        if T == 1:
-            return ops.rmsnorm(self._blocks(x, B, 1, st, None), self.ln_f.gain_f32(), self.ln_f.eps)
-        cap = st.k[0].shape[2]
-        plan = prefill_chunks(cap, st.offset_cpu, T, st.k[0].dtype, _lm_model.PREFILL_CHUNK)
-        if len(plan) == 1:
-            y = self._blocks(x, B, T, st, plan[0][2])
-        else:
-            xv = x.view(B, T, c.n_embd)
-            yv = torch.empty_like(xv)
-            for t0, Tc, route in plan:
-                yv[:, t0:t0 + Tc] = self._blocks(xv[:, t0:t0 + Tc].reshape(B * Tc, c.n_embd), B, Tc, st, route).view(B, Tc, c.n_embd)
-            y = yv.view(B * T, c.n_embd)
+        plan = [(0, 1, ROUTE_DECODE)] if T == 1 else prefill_chunks(st.k[0].shape[2], st.offset_cpu, T, st.k[0].dtype, _lm_model.PREFILL_CHUNK)
+        plan = [(t0, Tc, ROUTE_DECODE if Tc == 1 else route) for t0, Tc, route in plan]      # a one-position tail is a decode step, as a lone one
+        geo = Geometry(c.n_head, c.context, True, float(c.rope_base), c.rope_n_elem, litgpt_freqs=True)
+        y = run_chunks(x, B, st, plan, geo, [blk.view() for blk in self.h], fp8=self.fp8)
         return ops.rmsnorm(y, self.ln_f.gain_f32(), self.ln_f.eps)
-
-    def _blocks(self, x: torch.Tensor, B: int, T: int, st: _StepState, route: Optional[str]) -> torch.Tensor:
-        """The blocks over ``T`` consecutive positions (``route`` of ``prefill_route`` for ``T > 1``); advances the counters by ``T``."""
-        c = self.config
-        H, G, hs, n = c.n_head, c.n_query_groups, c.head_size, c.rope_n_elem
-        f8 = self.fp8
-        base = float(c.rope_base)
-        rope_table = window = freqs = None
-        if T == 1 and st.k[0].shape[2] > 64:      # the step's rotation once for all blocks (long rings)
-            rope_table = ops.lm_rope_table(st.pos, hs, max_period=base, rope_dims=n)
-        if route == ROUTE_PREFILL:
-            window = prefill_window(c.context, st.k[0].shape[2])
-            freqs = ops.gpt_rope_freqs(x.device, base, n)      # the table the reference evaluates (build_rope_cache)
-        for l, blk in enumerate(self.h):
-            wqkv, bqkv = blk.attn.packed_qkv()
-            n1 = dict(prologue=ops.PROLOGUE_RMSNORM, alpha=blk.norm_1.gain_f32(), eps=blk.norm_1.eps)
-            qkv = _lora_add(ops.lm_linear(x, wqkv, bias=bqkv, fp8=f8, **n1), x, blk.attn.packed_qkv_adapter(), **n1)
-            if T == 1:
-                a = ops.lm_attn_decode(qkv, st.k[l], st.v[l], st.pos, rope=True, context=c.context, max_period=base,
-                                       scratch=st.scratch, heads=H, rope_dims=n, packed=B > 2 and not f8, rope_table=rope_table)
-            elif route == ROUTE_PREFILL:
-                q3 = qkv.view(B, T, -1)
-                a = ops.lm_attn_prefill(q3, st.k[l], st.v[l], st.pos, window=window, rope=True, max_period=base, rope_dims=n, heads=H,
-                                        freqs=freqs)
-                # after the attention, in stream order: the slot of position pos + t still held position pos + t - cap
-                ops.lm_ring_append(q3, st.k[l], st.v[l], st.pos, rope=True, max_period=base, rope_dims=n, heads=H, freqs=freqs)
-            else:
-                q = ops.lm_rope_append(qkv.view(B, T, -1), st.k[l], st.v[l], st.pos, heads=H, rope=True,
-                                       max_period=base, rope_dims=n)
-                a = ops.attention(q, st.k[l], st.v[l], pos_dev=st.pos, ring=True, context=c.context).view(B * T, H * hs)
-            x = _lora_add(ops.lm_linear(a, blk.attn.proj.weight, res=x, bias=blk.attn.proj.bias_f32(), fp8=f8), a, blk.attn.proj.adapter())
-            wfc, bfc = blk.mlp.packed_fc()
-            ad_fc, ad_proj = blk.mlp.packed_fc_adapter(), blk.mlp.proj.adapter()
-            if ad_fc is None and ad_proj is None:
-                x = ops.lm_gated_pair(x, wfc, blk.mlp.proj.weight, alpha=blk.norm_2.gain_f32(), eps=blk.norm_2.eps, res=x, bias_in=bfc,
-                                      bias_out=blk.mlp.proj.bias_f32(), fp8=f8)
-            else:       # unmerged adapters: the gate follows fc_1 / fc_2 WITH their updates, so the pair runs as two plain products
-                n2 = dict(prologue=ops.PROLOGUE_RMSNORM, alpha=blk.norm_2.gain_f32(), eps=blk.norm_2.eps)
-                u = _lora_add(ops.lm_linear(x, wfc, bias=bfc, fp8=f8, **n2), x, ad_fc, **n2)
-                x = _lora_add(ops.lm_linear(u, blk.mlp.proj.weight, prologue=ops.PROLOGUE_SILU_GATE, res=x, bias=blk.mlp.proj.bias_f32(),
-                                            fp8=f8), u, ad_proj, prologue=ops.PROLOGUE_SILU_GATE)
-        st.pos.add_(T)
-        st.offset_cpu += T
-        return x
 
 
 @dataclass
@@ -742,12 +627,6 @@ class GPT(StreamingModule[_GPTState]):
         """One depth step up to its head: ``prev`` int64 ``[N]``, ``h`` fp32 ``[N, n_embd]`` (or ``h_all = h @ codecformer_in_all().T``) -> ``[N, codecformer_dim]``."""
         return self.depth_decoder.step_hidden(k, prev.reshape(-1, 1).contiguous(), 0, h, h_all=h_all)
 
-    def _codec_in(self, k: int, prev: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
-        """codecformer_in[k](h) + embedding of the previous token (text embedding for k = 0): prev int64 [N], h fp32 [N, n_embd]."""
-        x = ops.lm_linear(h, self.codecformer_in[k].weight)
-        table = self.codecformer_text_emb.weight if k == 0 else self.codecformer_emb[k - 1].weight
-        return ops.embed_sum(prev.reshape(-1, 1).contiguous(), [table], [0], add=x)
-
     @torch.no_grad()
     def forward_codecformer(self, codecformer_cb_index: int, sequence: torch.Tensor, transformer_out: torch.Tensor) -> torch.Tensor:
         """sequence int64 ``[B,1,1]`` (previous token), transformer_out fp32 ``[B,1,n_embd]`` -> logits fp32 ``[B,1,1,card]``;
@@ -767,25 +646,7 @@ class GPT(StreamingModule[_GPTState]):
         stays inside the kernel); ``sequence`` int64 ``[B,dep_q,T]``, ``transformer_out`` fp32 ``[B,T,n_embd]`` ->
         ``[B,T,dep_q,card]``.  Runs dep_q steps over B*T rows on a ring that never fills (the non-streaming reference path has
         no ring, hence no Q1 slot quirk at the last codebook)."""
-        B, K, T = sequence.shape
-        assert K == self.config.dep_q, f"Sequence shape {sequence.shape} must match the moshi stream output."
-        dep, N = self.codecformer, B * T
-        saved = dep._streaming_state
-        dep._streaming_state = dep._init_streaming_state(N, capacity=self.config.dep_q + 1)
-        try:
-            h = transformer_out.reshape(N, -1).float().contiguous()
-            outs = []
-            for k in range(K):
-                if k == 0 and local_start_token.dtype != torch.long:
-                    x = ops.lm_linear(h, self.codecformer_in[0].weight, res=local_start_token.reshape(N, -1).float().contiguous())
-                else:
-                    x = self._codec_in(k, local_start_token.reshape(N) if k == 0 else sequence[:, k - 1].reshape(N), h)
-                y = dep.step(x)
-                head = self.audio_linears[k]
-                outs.append(ops.lm_linear(y, head.weight, bias=head.bias_f32()).view(B, T, 1, -1))
-        finally:
-            dep._streaming_state = saved
-        return torch.cat(outs, dim=2)
+        return self.depth_decoder.forward_local(local_start_token, sequence, transformer_out)
 
     @torch.no_grad()
     def forward(self, sequence: torch.Tensor, input_pos: Optional[torch.Tensor] = None, lm_head_chunk_size: int = 0):

@@ -25,6 +25,7 @@ from ..codec.streaming import StreamingContainer, StreamingModule
 from ..graphs import Graphed as _Graphed, RecaptureGate
 from ..packed import _PackedCache
 from .depth_frame import DepthDecoder
+from .stack import ROUTE_DECODE, ROUTE_DECODE_FUSED, ROUTE_PREFILL, Geometry, LayerView, LinearView, _StepState, prefill_window, run_chunks, run_layers
 
 
 # positions per launch chain of the multi-position pass (StreamingTransformer.run); a chunk is also never longer than the ring
@@ -164,23 +165,6 @@ class _Layer(nn.Module):
             self.gating = ActivationGating(dim, dim_feedforward, **fk)
 
 
-@dataclass
-class _StepState:
-    k: List[torch.Tensor]      # per layer [B, H, cap, D] fp32 ring
-    v: List[torch.Tensor]
-    pos: torch.Tensor          # int64 [1] on device: steps appended so far (= position of the next step)
-    scratch: Optional[tuple] = None   # (split workspace, arrival counters) of the long-ring attention kernel
-    # host mirror of `pos`.  Graph replays move `pos` without running Python: whoever replays a captured step keeps the mirror in step
-    # (LMGen through temporal_base, GPT / GPTGen through lm.gpt.counted_step) -- GPT chooses the route of a T > 1 call from it
-    offset_cpu: int = 0
-    tables: object = None             # ops.TemporalFrameTables of the persistent batch-1 launch (built at the first step that takes it)
-    tables_key: object = None
-
-    def reset(self) -> None:
-        self.pos.zero_()
-        self.offset_cpu = 0
-
-
 class StreamingTransformer(StreamingModule[_StepState]):
     """Decode-step executor with the parameter layout of modules/transformer.py:595-690 (norm rms_norm_f32, SiLU gating,
     causal, rope or no positional embedding, optional per-step weights)."""
@@ -212,17 +196,29 @@ class StreamingTransformer(StreamingModule[_StepState]):
         if self.context is None and not self.weights_per_step:
             raise RuntimeError("Cannot create a streaming KVCache without a context to estimate capacity.")
         cap = capacity or (self.context if self.context is not None else self.weights_per_step)
-        dev = self.layers[0].norm1.alpha.device
-        shape = (batch_size, self.num_heads, cap, self.d_model // self.num_heads)
-        scratch = None
-        if cap > 64:
-            splits = ops.lm_attn_splits(cap, batch_size * self.num_heads)
-            scratch = (torch.empty(batch_size, self.num_heads, splits, shape[3] + 2, device=dev),
-                       torch.zeros(batch_size, self.num_heads, device=dev, dtype=torch.int32))
-        kvd = self.kv_dtype if cap > 64 else torch.float32
-        return _StepState([torch.zeros(shape, device=dev, dtype=kvd) for _ in self.layers],
-                          [torch.zeros(shape, device=dev, dtype=kvd) for _ in self.layers],
-                          torch.zeros(1, device=dev, dtype=torch.long), scratch)
+        H = self.num_heads
+        return _StepState.make(batch_size, H, H, self.d_model // H, cap, self.kv_dtype if cap > 64 else torch.float32,
+                               self.layers[0].norm1.alpha.device, len(self.layers))
+
+    def _geometry(self) -> Geometry:
+        return Geometry(None, self.context, self.rope, self.max_period)
+
+    def _views(self, k_idx: int = 0) -> List[LayerView]:
+        """The layers as ``stack.run_layers`` reads them: with per-step weights the matrices of step ``k_idx``; of a quantised model also the
+        fp8 / MXFP4 copies (never the depth transformer: its weights are not covered)."""
+        E, Q = self.d_model, self.weights_per_step
+        wd = "bf16" if Q else self.weight_dtype
+
+        def view(layer):
+            att, gate = layer.self_attn, layer.gating[k_idx] if Q else layer.gating
+            w_in, w_out = att.in_proj_weight, att.out_proj.weight
+            if Q:
+                w_in, w_out = w_in.view(Q, 3 * E, E)[k_idx], w_out.view(Q, E, E)[k_idx]
+            return LayerView(LinearView(w_in, w8=_wcopy(att, "in_proj_weight", wd)), LinearView(w_out, w8=_wcopy(att.out_proj, "weight", wd)),
+                             LinearView(gate.linear_in.weight, w8=_wcopy(gate.linear_in, "weight", wd)),
+                             LinearView(gate.linear_out.weight, w8=_wcopy(gate.linear_out, "weight", wd)),
+                             (layer.norm1.alpha_f32(), layer.norm1.eps), (layer.norm2.alpha_f32(), layer.norm2.eps))
+        return [view(layer) for layer in self.layers]
 
     def step(self, x: Optional[torch.Tensor], step_index: Optional[int] = None, pos: Optional[torch.Tensor] = None,
              embed: Optional[tuple] = None) -> torch.Tensor:
@@ -243,53 +239,18 @@ class StreamingTransformer(StreamingModule[_StepState]):
         k_idx = 0
         if self.weights_per_step:
             k_idx = st.offset_cpu if step_index is None else step_index
-        pos_t = st.pos if pos is None else pos
         if B == 1 and x is not None and not self.weights_per_step and cap > 64 and ops.temporal_frame_wanted(st.offset_cpu):
-            y = self._persistent_step(st, x, pos_t, cap)
+            y = self._persistent_step(st, x, st.pos if pos is None else pos, cap)
             if y is not None:
                 if pos is None:
                     st.pos.add_(1)
                     st.offset_cpu += 1
                 return y
-        # the step's rotation once for all layers (long rings: the attention launches read it instead of evaluating 24 libm calls per lane)
-        rope_table = ops.lm_rope_table(pos_t, E // H, max_period=self.max_period) if self.rope and cap > 64 else None
-        for l, layer in enumerate(self.layers):
-            att = layer.self_attn
-            if self.weights_per_step:
-                w_in = att.in_proj_weight.view(self.weights_per_step, 3 * E, E)[k_idx]
-                w_out = att.out_proj.weight.view(self.weights_per_step, E, E)[k_idx]
-                gate = layer.gating[k_idx]
-            else:
-                w_in, w_out, gate = att.in_proj_weight, att.out_proj.weight, layer.gating
-            # fp8 / MXFP4 copies of a quantised model (never the depth transformer: its weights are not covered)
-            wd = "bf16" if self.weights_per_step else self.weight_dtype
-            w8_in = _wcopy(att, "in_proj_weight", wd)
-            if l == 0 and embed is not None:
-                add, table, tokens, col = embed
-                if B <= 2 and E <= 4096 and E % 8 == 0:
-                    qkv, x = ops.gemv_embed(add, table, tokens, col, w_in, alpha=layer.norm1.alpha_f32(), eps=layer.norm1.eps)
-                else:
-                    x = ops.embed_sum(tokens, [table], [col], add=add)        # (a column block of h_all is read in place: no copy launch)
-            if l > 0 or embed is None or not (B <= 2 and E <= 4096 and E % 8 == 0):
-                qkv = ops.lm_linear(x, w_in, prologue=ops.PROLOGUE_RMSNORM, alpha=layer.norm1.alpha_f32(), eps=layer.norm1.eps,
-                                    w8=w8_in)
-            if fused_attn:
-                x = ops.gemv_attn(qkv, st.k[l], st.v[l], pos_t, w_out, context=self.context, res=x)
-            else:
-                a = ops.lm_attn_decode(qkv, st.k[l], st.v[l], pos_t, rope=self.rope, context=self.context,
-                                       max_period=self.max_period, scratch=st.scratch, packed=B > 2, rope_table=rope_table)
-                x = ops.lm_linear(a, w_out, res=x, w8=_wcopy(att.out_proj, "weight", wd))
-            x = ops.lm_gated_pair(x, gate.linear_in.weight, gate.linear_out.weight, alpha=layer.norm2.alpha_f32(), eps=layer.norm2.eps,
-                                  res=x, w8_in=_wcopy(gate.linear_in, "weight", wd), w8_out=_wcopy(gate.linear_out, "weight", wd))
-        if pos is None:
-            st.pos.add_(1)
-            st.offset_cpu += 1
-        return x
+        return run_layers(x, 1, st, ROUTE_DECODE_FUSED if fused_attn else ROUTE_DECODE, self._geometry(), self._views(k_idx), pos=pos, embed=embed)
 
     def window(self, cap: int) -> int:
-        """Keys a query sees on a ring of ``cap`` slots, itself included: the context, and never more than ``cap - 1`` because
-        ``RingKVCache.complete`` hides the oldest slot of a full ring -- exactly what single steps see."""
-        return min(self.context, cap - 1) if self.context else cap - 1
+        """Keys a query sees on a ring of ``cap`` slots, itself included (``stack.prefill_window`` of this transformer's context)."""
+        return prefill_window(self.context, cap)
 
     def run(self, x: torch.Tensor, B: int, T: int) -> torch.Tensor:
         """x fp32 ``[B*T, d_model]`` (row ``b*T + t``) -> ``[B*T, d_model]``: ``T`` new positions per stream through every layer, equal to
@@ -303,30 +264,10 @@ class StreamingTransformer(StreamingModule[_StepState]):
             raise NotImplementedError("run() serves the temporal transformer; per-step-weights (depth) transformers advance by `step`")
         if T == 1:
             return self.step(x)
-        E = self.d_model
-        assert x.shape == (B * T, E), (tuple(x.shape), B, T, E)
-        cap = st.k[0].shape[2]
-        window = self.window(cap)
-        wd = self.weight_dtype
-        xv = x.view(B, T, E)
-        y = torch.empty_like(xv)
-        for t0 in range(0, T, min(PREFILL_CHUNK, cap)):
-            Tc = min(PREFILL_CHUNK, cap, T - t0)
-            h = xv[:, t0:t0 + Tc].reshape(B * Tc, E)
-            for l, layer in enumerate(self.layers):
-                att, gate = layer.self_attn, layer.gating
-                qkv = ops.lm_linear(h, att.in_proj_weight, prologue=ops.PROLOGUE_RMSNORM, alpha=layer.norm1.alpha_f32(), eps=layer.norm1.eps,
-                                    w8=_wcopy(att, "in_proj_weight", wd)).view(B, Tc, 3 * E)
-                a = ops.lm_attn_prefill(qkv, st.k[l], st.v[l], st.pos, window=window, rope=self.rope, max_period=self.max_period)
-                # after the attention, in stream order: the slot of position pos + t still held position pos + t - cap
-                ops.lm_ring_append(qkv, st.k[l], st.v[l], st.pos, rope=self.rope, max_period=self.max_period)
-                h = ops.lm_linear(a, att.out_proj.weight, res=h, w8=_wcopy(att.out_proj, "weight", wd))
-                h = ops.lm_gated_pair(h, gate.linear_in.weight, gate.linear_out.weight, alpha=layer.norm2.alpha_f32(), eps=layer.norm2.eps,
-                                      res=h, w8_in=_wcopy(gate.linear_in, "weight", wd), w8_out=_wcopy(gate.linear_out, "weight", wd))
-            y[:, t0:t0 + Tc] = h.view(B, Tc, E)
-            st.pos.add_(Tc)
-            st.offset_cpu += Tc
-        return y.view(B * T, E)
+        assert x.shape == (B * T, self.d_model), (tuple(x.shape), B, T, self.d_model)
+        chunk = min(PREFILL_CHUNK, st.k[0].shape[2])      # (this pass always attends before it appends and plans without the host counter)
+        plan = [(t0, min(chunk, T - t0), ROUTE_PREFILL) for t0 in range(0, T, chunk)]
+        return run_chunks(x, B, st, plan, self._geometry(), self._views())
 
     def _persistent_step(self, st: _StepState, x: torch.Tensor, pos_t: torch.Tensor, cap: int) -> Optional[torch.Tensor]:
         """All layers of a batch-1 step as ONE persistent launch (csrc/lm_temporal.hip) when the library serves the shape and the
@@ -570,27 +511,7 @@ class LMModel(StreamingContainer):
         text ids, float ``[B,T,depformer_dim]`` as in the reference, or the int64 ids ``[B,T]`` themselves; ``sequence`` int64
         ``[B,dep_q,T]``, ``transformer_out`` fp32 ``[B,T,dim]`` -> ``[B,T,dep_q,card]``.  ``dep_q`` depth steps over ``B*T`` rows on a
         ring of capacity ``dep_q + 1`` (the non-streaming reference path has no ring, hence no Q1 slot quirk at the last codebook)."""
-        B, K, T = sequence.shape
-        assert K == self.dep_q, f"Sequence shape {sequence.shape} must match the moshi stream output."
-        dep, N = self.depformer, B * T
-        saved = dep._streaming_state
-        dep._streaming_state = dep._init_streaming_state(N, capacity=self.dep_q + 1)
-        try:
-            h = transformer_out.reshape(N, -1).float().contiguous()
-            outs = []
-            for k in range(K):
-                w = self.depformer_in[k].weight
-                if k == 0 and local_start_token.dtype != torch.long:
-                    x = ops.lm_linear(h, w, res=local_start_token.reshape(N, -1).float().contiguous())
-                else:
-                    prev = local_start_token if k == 0 else sequence[:, k - 1]
-                    table = self.depformer_text_emb.weight if k == 0 else self.depformer_emb[k - 1].weight
-                    x = ops.embed_sum(prev.reshape(N, 1).contiguous(), [table], [0], add=ops.lm_linear(h, w))
-                y = dep.step(x)
-                outs.append(ops.lm_linear(y, self.linears[k].weight).view(B, T, 1, -1))
-        finally:
-            dep._streaming_state = saved
-        return torch.cat(outs, dim=2)
+        return self.depth_decoder.forward_local(local_start_token, sequence, transformer_out)
 
     # ---- decode step / multi-position pass
     def forward_text(self, sequence: torch.Tensor, masks: Optional[torch.Tensor] = None):
