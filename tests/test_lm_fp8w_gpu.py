@@ -28,6 +28,7 @@ from rstnet_amd.lm.model import LMGen, LMModel
 from rstnet_amd.pipeline import StreamingPipeline
 from tests.golden import cases
 from tests.helpers import lm_fp8w as Q
+from tests.helpers.gemv_bounds import gate_carry, mixed_rows as _mixed_rows
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -38,13 +39,6 @@ EPS = 1e-8
 def rel_err(a, b):
     a, b = a.detach().cpu().double(), b.detach().cpu().double()
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
-
-
-def _mixed_rows(rows, cols, g, lo, hi):
-    """randn rows scaled by 2^e, e uniform in [lo, hi] (row 0 at the low end, the last row at the high end)."""
-    e = torch.randint(lo, hi + 1, (rows,), generator=g)
-    e[0], e[-1] = lo, hi
-    return torch.randn(rows, cols, generator=g) * torch.exp2(e.double()).float()[:, None]
 
 
 # ---- 3 ----------------------------------------------------------------------------------------------------------------------------------
@@ -167,10 +161,7 @@ def test_gemv_fp8w_elementwise_bound(B, N, K, mode, res, gate, bias):
     if mode == 2:       # the fp32 silu(u) = u / (1 + expf(-u)) is -0 where expf(-u) overflows (u < -88.7): there |silu(u)| < 2^-121
         dh = dh + (x[:, K:].double().abs() * 2.0 ** -120) @ w64.abs().t()
     if gate:
-        I = N // 2
-        u, v, du, dv = h[:, :I], h[:, I:], dh[:, :I], dh[:, I:]
-        ref = F.silu(u) * v
-        bound = 1.1 * (v.abs() + dv) * du + F.silu(u).abs() * dv + 8 * U * ref.abs() + v.abs() * 2.0 ** -110
+        ref, bound = gate_carry(h, dh)
     else:
         ref = h + (r.double() if res else 0)
         bound = dh + (c * r.double().abs() if res else 0)

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from rstnet_amd import _lib, ops
 from tests.helpers import lm_operands as O
+from tests.helpers.gemv_bounds import mixed_rows as _mixed_rows, p_ref as _p_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -64,13 +65,6 @@ def _p(t):
 
 def _sentinel(*shape, dtype=torch.bfloat16):
     return torch.full(shape, SENTINEL, dtype=torch.int16, device=DEV).view(dtype)
-
-
-def _mixed_rows(rows, cols, g, lo=-20, hi=20):
-    """randn rows scaled by 2^e, e uniform in [lo, hi] (row 0 at the low end, the last row at the high end: every tile mixes them)."""
-    e = torch.randint(lo, hi + 1, (rows,), generator=g)
-    e[0], e[-1] = lo, hi
-    return torch.randn(rows, cols, generator=g) * torch.exp2(e.double()).float()[:, None]
 
 
 def _planes(xp, K):
@@ -134,16 +128,6 @@ def test_pack_act_identity_is_the_exact_split(B, K):
     assert bad.size == 0, [(int(b), int(k), hex(int(O.f32_bits(x[b, k].numpy()))), hex(int(hi[b, k])), hex(int(lo[b, k])))
                            for b, k in bad[:8]]
     assert not hi[B:].any() and not lo[B:].any(), "rows B .. ceil(B/32)*32 must be zero in both planes"
-
-
-def _p_ref(x64, K, mode, alpha64=None, eps=EPS):
-    if mode == 1:
-        e = float(np.float32(eps))
-        return x64 * alpha64 / torch.sqrt(e + (x64 * x64).mean(dim=1, keepdim=True))
-    if mode == 2:
-        u, v = x64[:, :K], x64[:, K:]
-        return F.silu(u) * v
-    return x64
 
 
 @pytest.mark.parametrize("mode", [1, 2])
