@@ -1,5 +1,12 @@
-// sample_token of MLLM_v2/utils/sampling.py on the device: greedy argmax or exact top-k + Exp(1) race, bit-identical to the
-// oracle given the same noise (ties to the lowest index, plateaus, vocabularies up to 2^20, id blanking).
+// sample_token of MLLM_v2/utils/sampling.py on the device: greedy argmax or exact top-k + Exp(1) race.  Given the same noise the
+// candidates are the oracle's, in the oracle's order (equal logits to the lowest index, plateaus, vocabularies up to 2^20, id
+// blanking), wherever the order of the scaled logits (logits / temp) is the order of their fp32 probabilities.  That is where it ends:
+// the kernels select and rank by (scaled logit, index) keys, the oracle sorts the rounded probabilities, so DISTINCT scaled logits
+// whose fp32 probabilities round to the same number (logits a few ulps apart, or closer than the spacing of fp32 at their distance
+// from the maximum) are ranked by value here and by index there -- a different order within such a run, and a different top-k set
+// where the run straddles the k-th place.  Ordering by probability would put a division per element on the hot path.  The race
+// terms are p_j / noise_j in fp32 with a softmax denominator summed in another order than torch's: tokens are the oracle's unless two
+// terms of a race agree to within a few 2^-24 (tests/test_sampler_readout_gpu.py: ranks read out one by one, races 2^-12 apart).
 #include "lm_common.h"
 #include "lm_sample_impl.h"
 
@@ -249,7 +256,12 @@ __global__ __launch_bounds__(256) void sample_merge_kernel(const LmSampleParams 
         const float mx = from_key(bk);
         float d = 0.f;
         if (sampling)
-            for (int c = lane; c < chunks; c += 64) { const SplitRec r = rec[c]; d += r.sum_exp * expf(from_key(r.max_key) - mx); }
+            for (int c = lane; c < chunks; c += 64) {
+                // a chunk whose ids are all -inf reports the maximum -inf and the exp-sum NaN (-inf - -inf): it adds nothing
+                const SplitRec r = rec[c];
+                const float w = expf(from_key(r.max_key) - mx);
+                d += w > 0.f ? r.sum_exp * w : 0.f;
+            }
         d = wave_sum(d);
         if (lane == 0) { s_mx = mx; s_denom = d; s_tok = bi; }
     }
