@@ -12,6 +12,7 @@ when the oracle's own decision margin between the two candidates is below 1e-4 o
 ~1e-6), and the comparison of that frame stops there.  Observed errors are written to ``gpurun_out/real_shapes.json``."""
 import json
 import os
+from types import SimpleNamespace
 
 import pytest
 import torch
@@ -24,6 +25,7 @@ from rstnet_amd.codec.mimi import MimiCodec
 from rstnet_amd.lm.gpt import GPT, Config
 from rstnet_amd.lm.model import LMGen, LMModel
 from rstnet_amd.pipeline import StreamingPipeline
+from tests.helpers.depth_frame_ref import read_handoff, workspace as depth_workspace
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -127,9 +129,7 @@ def test_depth_phase_at_the_moshi_shape_matches_the_oracle(B, sampling, monkeypa
             if mode == "1" and torch.equal(got[:, :Q - 1], want[:, :Q - 1]):
                 # the logits of the LAST step are still in the launch's hand-off workspace ({tag, fp32} granules): with the same tokens
                 # fed to steps 0..Q-2 they are the oracle's -- 8 steps x 6 layers of accumulated error
-                ws = [v for k, v in ops._depth_ws.items() if k[-4:] == (B, E, Hd, card) and k[1] != "graph"][0]
-                off = B * (5 * E + Hd)
-                lg = ws[off:off + B * card].view(torch.int32).view(-1, 2)[:, 0].contiguous().view(torch.float32).view(B, card)      # low word = value
+                lg = read_handoff(depth_workspace(ops, B, E, Hd, card), SimpleNamespace(E=E, Hd=Hd, card=card), B).LOG
                 worst["persistent_last_logits"] = max(worst["persistent_last_logits"], rel_err(lg, logits_o[Q - 1]))
         # the launch-per-op chain step by step, teacher-forced with the oracle's tokens: every step's logits
         monkeypatch.setenv("RST_DEPTH_FRAME", "0")
