@@ -19,6 +19,7 @@
 //     order of gemv_norm_kernel: thread t owns k = t + 256 i), rotate and append the new key, merge the attention partials.
 // Arithmetic equals the launch-per-op chain's (lm_step.hip, lm_attn.hip) up to the order of additions inside the wave reductions, the
 // single k chain of the plain-vector GEMVs (gemv_ksplit_kernel sums four chains) and the split / merge order of the attention.
+#include <type_traits>
 #include <utility>
 
 #include "lm_common.h"
@@ -200,7 +201,7 @@ __global__ __launch_bounds__(TF_THREADS) void temporal_frame_kernel(const Tempor
     const int wg = blockIdx.x, G = gridDim.x;
     const int E = p.E, Hd = p.Hd, H = p.H, L = p.L, cap = p.cap;
     // staged vectors are padded with zeros to whole blocks of 8 pieces (4096 k): a piece past the end of a row repeats the last valid weights
-    // and multiplies zeros, so the multiply needs no per-piece condition
+    // (a clamped address; only a block of all 4096 k is loaded unclamped) and multiplies zeros, so the multiply needs no per-piece condition
     const int EP = (E + 4095) & ~4095, HdP = (Hd + 4095) & ~4095;
     // LDS carve (floats): header | xA [EP] (norm1 / norm2 output) | xB [EP] (attention output) | xD [HdP] (gated activation) |
     //                     xres0 [E] (layer input) | xres1 [E] (after the attention block) | qh [3D] | pw_o [TF_WW][D] |
@@ -323,7 +324,10 @@ __global__ __launch_bounds__(TF_THREADS) void temporal_frame_kernel(const Tempor
             d.arr1 = d.arr0;
             const int rem = min(K - kb, 4096);
             d.kb = kb;
-            d.meta = gop | ((flags | (has1 ? 4 : 0)) << 3) | (((rem + 511) >> 9) << 6);
+            // pieces == 8 selects `issue`'s unclamped whole-block loads: only a block of 4096 k may say so (3585 .. 4095 k are eight pieces
+            // as well, but the eighth is partial -- read unclamped it ran up to 1 KB past the row, for the last row past the matrix)
+            const int pieces = rem == 4096 ? 8 : min((rem + 511) >> 9, 7);
+            d.meta = gop | ((flags | (has1 ? 4 : 0)) << 3) | (pieces << 6);
             d.off0 = ((long)r0 * K + kb) * 2;
             d.off1 = gop == TF_OP_C ? (((long)Hd + r0) * K) * 2 : (has1 ? d.off0 + (long)W * K * 2 : d.off0);
             d.r0 = r0;
@@ -890,6 +894,21 @@ int rst_temporal_frame_grid(const TemporalFrameParams& p) {
     return f > 0 ? G : 0;
 }
 
+namespace {
+// The opt-in to more than 64 KB of dynamic LDS is per kernel and per device.  The flag is keyed by the kernel itself (a template on its
+// pointer): all eight instantiations have the same function-pointer type, so a flag inside a generic lambda over `auto kern` is one flag
+// for all of them and only the first variant launched would ever get the attribute.
+template <auto KERN>
+void tf_launch(const TemporalFrameParams& pk, int grid, size_t lds, hipStream_t stream) {
+    static RstOncePerDevice attr_once;
+    if (attr_once.first()) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        (void)hipGetLastError();
+    }
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(TF_THREADS), lds, stream, pk);
+}
+}  // namespace
+
 int rst_launch_temporal_frame(const TemporalFrameParams& p, hipStream_t stream) {
     RST_REQUIRE(p.tab && p.x && p.y && p.pos_dev && p.gran && p.status, "temporal_frame: null buffers");
     const int G = rst_temporal_frame_grid(p);
@@ -902,21 +921,17 @@ int rst_launch_temporal_frame(const TemporalFrameParams& p, hipStream_t stream) 
         rst_set_error("temporal_frame: workspace memset failed");
         return RST_ERR_LAUNCH;
     }
-    auto go = [&](auto kern, int grid) {
-        static RstOncePerDevice attr_once;
-        if (attr_once.first()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            (void)hipGetLastError();
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(TF_THREADS), lds, stream, pk);
-    };
     static const int no_repair = rst_knob("RST_TF_NO_REPAIR", 0);      // tools build only
+    auto go = [&](auto KV16, auto D) {      // the persistent launch and, behind it in the stream, its one-workgroup repair launch
+        tf_launch<temporal_frame_kernel<decltype(KV16)::value, decltype(D)::value, false>>(pk, G, lds, stream);
+        if (!no_repair) tf_launch<temporal_frame_kernel<decltype(KV16)::value, decltype(D)::value, true>>(pk, 1, lds, stream);
+    };
     const int key = (p.kv_bf16 ? 2 : 0) + (p.D == 128 ? 1 : 0);
     switch (key) {
-        case 3: go(temporal_frame_kernel<true, 128, false>, G); if (!no_repair) go(temporal_frame_kernel<true, 128, true>, 1); break;
-        case 2: go(temporal_frame_kernel<true, 64, false>, G); if (!no_repair) go(temporal_frame_kernel<true, 64, true>, 1); break;
-        case 1: go(temporal_frame_kernel<false, 128, false>, G); if (!no_repair) go(temporal_frame_kernel<false, 128, true>, 1); break;
-        default: go(temporal_frame_kernel<false, 64, false>, G); if (!no_repair) go(temporal_frame_kernel<false, 64, true>, 1); break;
+        case 3: go(std::true_type{}, std::integral_constant<int, 128>{}); break;
+        case 2: go(std::true_type{}, std::integral_constant<int, 64>{}); break;
+        case 1: go(std::false_type{}, std::integral_constant<int, 128>{}); break;
+        default: go(std::false_type{}, std::integral_constant<int, 64>{}); break;
     }
     return rst_check_launch("temporal_frame");
 }
