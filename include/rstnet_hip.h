@@ -461,6 +461,29 @@ int rst_gemm_skinny_x32_bf16_f32(const float* x, const float* alpha, float eps, 
  * (deterministic).  split_k <= 1 (ws / counters may be NULL): one workgroup per column tile(s) over all of K, as before. */
 int rst_skinny_bf16_split_plan(int B, int N, int K);
 
+/* Weight-only fp8 form of rst_gemm_skinny_bf16_f32, for a model quantised with LMModel.quantize_weights_ at 2 < B <= 64 rows and in
+ * prompt prefill (chunks of 64 rows): the same call sites as rst_gemv_fp8w_f32 -- in_proj / out_proj (modules/transformer.py:376-423),
+ * gating linear_in / linear_out (modules/gating.py:12-51), text_linear and depformer_in (models/model.py:364-389) -- on the stored
+ * (q, scale) of rst_quant_rows_fp8.  Activations are the packed bf16 hi / lo planes xp of rst_skinny_pack_act_f32 (or of a producer),
+ * unchanged; the weight bytes are decoded to the bf16 operand inside the launch (exact: e4m3 has 3 mantissa bits) and run on the
+ * same v_mfma_f32_32x32x16_bf16; the row scale s_n = 2^e_n multiplies the fp32 accumulator of column n (exact) before the wave sum,
+ * the split partials, bias and silu(u) * v.  y is what rst_gemm_skinny_bf16_f32 computes on the dequantised matrix, to within
+ * summation order (with the shared launch plan: bit for bit, while nothing leaves the normal range).
+ *   rst_skinny_pack_weight_fp8w: q [N][K] e4m3fn bytes, scale [N] -> qp [ceil(N/32)*32][K] bytes in the order [tile of 32 rows][K/32]
+ *     [64 lanes = 32 * ((k / 8) % 2) + row % 32][16 B = 8 k of step 2p | 8 k of step 2p+1] (a 16-byte lane load carries two MFMA steps;
+ *     pad rows zero bytes) and sp [ceil(N/32)*32] the scales in the same row order (pad rows 0); once per weight.  interleave_halves as
+ *     rst_skinny_pack_weight_bf16 (N % 32 == 0), applied to q rows and scales alike.  K % 32 == 0, q 8-byte and qp 16-byte aligned.
+ *   rst_gemm_skinny_fp8w_supported(B, N, K): 1 for exactly the served shapes, 1 <= B <= 64, N > 0, K % 32 == 0; callers take the bf16
+ *     route (same values, twice the bytes) for the others.
+ *   rst_gemm_skinny_fp8w_f32: arguments as rst_gemm_skinny_bf16_f32 with (qp, sp) in place of wp: res / bias optional, gate_out (qp
+ *     packed with interleave_halves, no residual, y may be NULL), split_k = rst_skinny_bf16_split_plan(B, N, K) with the same ws /
+ *     counters scratch and protocol. */
+int rst_skinny_pack_weight_fp8w(const uint8_t* q, const float* scale, uint8_t* qp, float* sp, int N, int K, int interleave_halves,
+                                rst_stream_t stream);
+int rst_gemm_skinny_fp8w_supported(int B, int N, int K);
+int rst_gemm_skinny_fp8w_f32(const uint16_t* xp, const uint8_t* qp, const float* sp, const float* res, const float* bias, float* y, int B,
+                             int N, int K, int ldy, uint16_t* gate_out, int split_k, float* ws, uint32_t* counters, rst_stream_t stream);
+
 /* Opt-in fp8 form of the three entry points above (BASELINE.json configs[4]: fp8 MFMA GEMMs on the temporal blocks at batch
  * 32): OCP e4m3 operands on v_mfma_f32_32x32x16_fp8_fp8, weights with one scale per row (amax / 448, quantised once),
  * activations with one dynamic scale per batch row (quantised by the prologue launch), y = scale_x[b] * scale_w[n] * acc.

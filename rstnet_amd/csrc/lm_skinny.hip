@@ -95,7 +95,32 @@ constexpr int SKINNY_WAVES = 8;
 // weight byte instead of 3) and, for the longest K, only a slice of it (gridDim.y splits, so that ~256-384 workgroups exist); the partial tiles go to
 // `ws` with write-through stores, one arrival counter per column group, and the LAST workgroup to arrive sums them in split order
 // (deterministic) and runs the epilogue (the protocol of the fp32 few-row GEMM, csrc/skinny_f32.hip).
-template <int NB, int CT>   // batch tiles of 32, weight-row tiles per workgroup
+//
+// W8 (weight-only fp8, rst_gemm_skinny_fp8w_f32): the weights are e4m3fn bytes in the order of fp8_packed_index below --
+// [tile of 32 rows][K/32][64 lanes][16 B = the lane's 8 k of step 2p | of step 2p+1] -- so a 16-byte lane load carries the operand of
+// TWO steps (a wave-level load is still one contiguous KB, of half as many of them).  Decode: v_cvt_pk_f32_fp8 (exact) and the upper
+// halves of the two floats packed by v_perm_b32 -- e4m3 has 3 mantissa bits, so the truncation drops zeros only: 2 + 2 VALU per
+// dword, 8 per step and column tile.  The row scale (a power of two) multiplies the accumulator of column n = lane % 32 on its way
+// to LDS, i.e. before the wave sum, the split partials, bias and silu(u) * v (u and v rows carry different scales).  Steps are
+// dealt to splits and waves exactly as in the bf16 form (a wave whose first step is odd loads the pair it shares with its neighbour
+// and multiplies that half by zero activations), so the result is the bf16 form's on the dequantised matrix, bit for bit, wherever no
+// product or partial sum leaves the normal range.
+typedef float f32x2w __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void decode_fp8w_pair(const u32x4 q, bf16x8& e, bf16x8& o) {
+    u32x4 r[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const f32x2w lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)q[2 * h + j], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)q[2 * h + j], true);
+            r[h][2 * j] = __builtin_amdgcn_perm(__float_as_uint(lo[1]), __float_as_uint(lo[0]), 0x07060302u);
+            r[h][2 * j + 1] = __builtin_amdgcn_perm(__float_as_uint(hi[1]), __float_as_uint(hi[0]), 0x07060302u);
+        }
+    e = __builtin_bit_cast(bf16x8, r[0]);
+    o = __builtin_bit_cast(bf16x8, r[1]);
+}
+
+template <int NB, int CT, bool W8 = false>   // batch tiles of 32, weight-row tiles per workgroup, fp8 weight bytes + row scales
 __global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_skinny_kernel(const SkinnyParams p) {
     __shared__ float red[SKINNY_WAVES][NB * 32][33];
     __shared__ float gtile[NB * 32 * 16];      // gated epilogue: silu(u) * v of a column tile
@@ -113,8 +138,15 @@ __global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_skinny_kernel(const Sk
     const unsigned short* xh = p.xp + (long)lane * 8;
     const unsigned short* xl = xh + xplane;
     const unsigned short* wt[CT];
+    const unsigned char* wq[CT];
+    float wsc[CT];                  // W8: scale of weight row n = lane % 32 of each column tile (pad rows: 0)
 #pragma unroll
-    for (int c = 0; c < CT; ++c) wt[c] = p.w + ((long)min(tile0 + c, tiles - 1) * steps * 64 + lane) * 8;
+    for (int c = 0; c < CT; ++c) {
+        const long tc = min(tile0 + c, tiles - 1);
+        wt[c] = W8 ? nullptr : p.w + (tc * steps * 64 + lane) * 8;
+        wq[c] = W8 ? p.w8 + (tc * (steps / 2) * 64 + lane) * 16 : nullptr;
+        wsc[c] = W8 ? p.wscale[tc * 32 + (lane & 31)] : 1.f;
+    }
     f32x16 acc[NB][CT];
 #pragma unroll
     for (int t = 0; t < NB; ++t)
@@ -144,20 +176,37 @@ __global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_skinny_kernel(const Sk
     // (Measured and dropped, round 3: requesting the weights of 32 / 16 steps up front with the activations following 8 steps at a time --
     // one HBM round trip per 32 steps instead of per 8 -- is SLOWER: 7.32 vs 7.10 ms per frame at the Moshi-7B shape, batch 32, 3.64 vs
     // 3.62 ms for the GPT frame, A/B inside one session.)
-    for (int s = s0; s < s1; s += UN) {
+    static_assert(UN % 2 == 0, "W8: a lane load carries two steps");
+    for (int s = W8 ? (s0 & ~1) : s0; s < s1; s += UN) {      // W8: s stays even, a pair of steps per weight load
         bf16x8 a[UN][CT], bh[UN][NB], bl[UN][NB];
+        u32x4 aq[UN / 2][CT];
+        if (W8) {
+#pragma unroll
+            for (int u = 0; u < UN / 2; ++u)
+#pragma unroll
+                for (int c = 0; c < CT; ++c)
+                    aq[u][c] = s + 2 * u < s1 ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wq[c] + (long)(s / 2 + u) * 1024)) : u32x4{0u, 0u, 0u, 0u};
+        }
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
-            const bool ok = s + u < s1;
+            const bool ok = (!W8 || s + u >= s0) && s + u < s1;
             const long so = (long)(s + u) * 512;
+            if (!W8) {
 #pragma unroll
-            for (int c = 0; c < CT; ++c)
-                a[u][c] = ok ? __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wt[c] + so)) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                for (int c = 0; c < CT; ++c)
+                    a[u][c] = ok ? __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wt[c] + so)) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            }
 #pragma unroll
             for (int t = 0; t < NB; ++t) {
                 bh[u][t] = ok ? *reinterpret_cast<const bf16x8*>(xh + (long)t * steps * 512 + so) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
                 bl[u][t] = ok ? *reinterpret_cast<const bf16x8*>(xl + (long)t * steps * 512 + so) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
             }
+        }
+        if (W8) {
+#pragma unroll
+            for (int u = 0; u < UN / 2; ++u)
+#pragma unroll
+                for (int c = 0; c < CT; ++c) decode_fp8w_pair(aq[u][c], a[2 * u][c], a[2 * u + 1][c]);
         }
 #pragma unroll
         for (int u = 0; u < UN; ++u)
@@ -227,7 +276,7 @@ __global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_skinny_kernel(const Sk
 #pragma unroll
         for (int t = 0; t < NB; ++t)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) red[wave][t * 32 + rst_mfma32_row(e, lane)][i] = acc[t][c][e];
+            for (int e = 0; e < 16; ++e) red[wave][t * 32 + rst_mfma32_row(e, lane)][i] = W8 ? acc[t][c][e] * wsc[c] : acc[t][c][e];
         __syncthreads();
         if (nsplit == 1) {
             emit(c);
@@ -584,8 +633,10 @@ int rst_skinny_bf16_split_plan_impl(int B, int N, int K) {
 
 int rst_launch_gemm_skinny(const SkinnyParams& p, hipStream_t stream) {
     RST_REQUIRE(p.B >= 1 && p.B <= 64 && p.N > 0 && p.K > 0 && p.K % 16 == 0, "gemm_skinny: need 1 <= B <= 64 and K %% 16 == 0 (B=%d K=%d)", p.B, p.K);
-    RST_REQUIRE((p.xp || p.xf) && p.w && (p.y || p.gate_out), "gemm_skinny: null pointer");
+    RST_REQUIRE((p.xp || p.xf) && (p.w || p.w8) && (p.y || p.gate_out), "gemm_skinny: null pointer");
     const bool xf = p.xp == nullptr;
+    RST_REQUIRE(!p.w8 || (!p.w && !xf && p.wscale && p.K % 32 == 0 && (uintptr_t)p.w8 % 16 == 0),
+                "gemm_skinny_fp8w: needs packed activations, row scales, K %% 32 == 0 and 16-byte aligned weights (K=%d)", p.K);
     RST_REQUIRE(!xf || (p.K % 256 == 0 && p.ldx % 4 == 0 && p.ldx >= p.K && (uintptr_t)p.xf % 16 == 0 && (p.xmode == 0 || (p.xmode == 1 && p.alpha)) && p.split_k <= 1),
                 "gemm_skinny: the fp32-input form needs K %% 256 == 0, 16-byte aligned rows (ldx %% 4 == 0), mode 0 / 1 (with alpha) and no K split");
     RST_REQUIRE(!p.gate_out || (p.N % 32 == 0 && !p.res), "gemm_skinny: the gated epilogue needs N %% 32 == 0 and takes no residual");
@@ -607,6 +658,19 @@ int rst_launch_gemm_skinny(const SkinnyParams& p, hipStream_t stream) {
             else hipLaunchKernelGGL((gemm_skinny_x32_kernel<2, 1>), grid, dim3(threads), 0, stream, p);
         }
         return rst_check_launch("gemm_skinny_x32");
+    }
+    if (p.w8) {
+        if (p.B <= 32) {
+            if (ct == 4) hipLaunchKernelGGL((gemm_skinny_kernel<1, 4, true>), grid, dim3(threads), 0, stream, p);
+            else if (ct == 3) hipLaunchKernelGGL((gemm_skinny_kernel<1, 3, true>), grid, dim3(threads), 0, stream, p);
+            else if (ct == 2) hipLaunchKernelGGL((gemm_skinny_kernel<1, 2, true>), grid, dim3(threads), 0, stream, p);
+            else hipLaunchKernelGGL((gemm_skinny_kernel<1, 1, true>), grid, dim3(threads), 0, stream, p);
+        } else {
+            if (ct == 3) hipLaunchKernelGGL((gemm_skinny_kernel<2, 3, true>), grid, dim3(threads), 0, stream, p);
+            else if (ct == 2) hipLaunchKernelGGL((gemm_skinny_kernel<2, 2, true>), grid, dim3(threads), 0, stream, p);
+            else hipLaunchKernelGGL((gemm_skinny_kernel<2, 1, true>), grid, dim3(threads), 0, stream, p);
+        }
+        return rst_check_launch("gemm_skinny_fp8w");
     }
     if (p.B <= 32) {
         if (ct == 4) hipLaunchKernelGGL((gemm_skinny_kernel<1, 4>), grid, dim3(threads), 0, stream, p);
@@ -844,4 +908,44 @@ int rst_launch_gemm_skinny_fp8(const SkinnyFp8Params& p, hipStream_t stream) {
         else hipLaunchKernelGGL((gemm_skinny_fp8_kernel<2, 1>), dim3(tiles), dim3(threads), 0, stream, p);
     }
     return rst_check_launch("gemm_skinny_fp8");
+}
+
+// ======================================================================================================================
+// Weight-only fp8 operand of gemm_skinny_kernel<NB, CT, true>: the stored (q, scale) of rst_quant_rows_fp8 -> q in the order of
+// fp8_packed_index (pad rows: zero bytes), scales in the same row order padded with zeros to a multiple of 32.  interleave: the row
+// permutation of skinny_pack_weight_kernel (tile t = u rows 16t.. then the matching v rows), applied to the scales too.
+// ======================================================================================================================
+namespace {
+
+__global__ __launch_bounds__(256) void skinny_pack_weight_fp8w_kernel(const unsigned char* __restrict__ q, const float* __restrict__ scale,
+                                                                     unsigned char* __restrict__ qp, float* __restrict__ sp, int N, int K,
+                                                                     int interleave) {
+    const long total = (long)((N + 31) / 32) * 32 * (K / 8);
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int row = (int)(idx / (K / 8)), k = (int)(idx % (K / 8)) * 8;
+        int src = row;
+        if (interleave) {
+            const int t = row >> 5, r = row & 31;
+            src = (r < 16 ? 0 : N / 2) + t * 16 + (r & 15);
+        }
+        uint2 v = make_uint2(0u, 0u);
+        if (row < N) v = *reinterpret_cast<const uint2*>(q + (long)src * K + k);
+        *reinterpret_cast<uint2*>(qp + fp8_packed_index(row, k, K)) = v;
+        if (k == 0) sp[row] = row < N ? scale[src] : 0.f;
+    }
+}
+
+}  // namespace
+
+int rst_gemm_skinny_fp8w_supported_impl(int B, int N, int K) { return B >= 1 && B <= 64 && N > 0 && K > 0 && K % 32 == 0; }
+
+int rst_launch_skinny_pack_weight_fp8w(const unsigned char* q, const float* scale, unsigned char* qp, float* sp, int N, int K, int interleave,
+                                       hipStream_t stream) {
+    RST_REQUIRE(q && scale && qp && sp && N > 0 && K > 0 && K % 32 == 0 && (uintptr_t)q % 8 == 0 && (uintptr_t)qp % 16 == 0,
+                "skinny_pack_weight_fp8w: bad arguments (K %% 32 == 0 and aligned buffers required, K=%d)", K);
+    RST_REQUIRE(!interleave || N % 32 == 0, "skinny_pack_weight_fp8w: interleaving the two halves needs N %% 32 == 0 (N=%d)", N);
+    const long total = (long)((N + 31) / 32) * 32 * (K / 8);
+    hipLaunchKernelGGL(skinny_pack_weight_fp8w_kernel, dim3(cap_grid((total + 255) / 256, 8192)), dim3(256), 0, stream, q, scale, qp, sp, N, K,
+                       interleave);
+    return rst_check_launch("skinny_pack_weight_fp8w");
 }

@@ -431,8 +431,14 @@ struct SkinnyParams {
     const float* alpha;         // xmode 1: RMSNorm gains [K]
     int ldx, xmode;             // 0: x as is; 1: RMSNorm (x * alpha in the operand, 1 / rms applied to the accumulators)
     float eps;
+    // weight-only fp8 form (w == nullptr, packed activations only): e4m3fn bytes decoded to the bf16 operand inside the launch
+    const unsigned char* w8;    // packed weights [ceil(N/32)][K/32][64][16] (rst_launch_skinny_pack_weight_fp8w)
+    const float* wscale;        // [ceil(N/32)*32] power-of-two row scales in packed row order, applied to the accumulators
 };
 int rst_launch_gemm_skinny(const SkinnyParams& p, hipStream_t stream);
+int rst_gemm_skinny_fp8w_supported_impl(int B, int N, int K);
+int rst_launch_skinny_pack_weight_fp8w(const unsigned char* q, const float* scale, unsigned char* qp, float* sp, int N, int K, int interleave,
+                                       hipStream_t stream);
 int rst_skinny_bf16_split_plan_impl(int B, int N, int K);
 struct SkinnyFp8Params {
     const unsigned char* xp;    // packed fp8 activations [ceil(B/32)][K/32][64][16]

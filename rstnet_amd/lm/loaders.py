@@ -21,7 +21,7 @@ def get_moshi_lm(weights: Union[str, Path, Dict[str, torch.Tensor]], device: Uni
     """``weights``: a ``.safetensors`` file, a ``torch.save``d package (``pkg["fsdp_best_state"]["model"]``, loaders.py:153-158) or a
     ``state_dict``.  Tensors are moved to ``device`` as bf16 and adopted without copying; ``lm_kwargs`` overrides the Moshi-7B
     hyper-parameters (e.g. a smaller model trained with the same code).  ``weight_dtype="fp8"`` / ``"mxfp4"``: the loaded model is quantised with
-    ``LMModel.quantize_weights_`` (weight-only e4m3 / MXFP4 copies for the batch <= 2 step; bf16 is the default)."""
+    ``LMModel.quantize_weights_`` (weight-only e4m3 / MXFP4 copies; fp8 copies serve every batch size and prefill, MXFP4 the batch <= 2 step; bf16 is the default)."""
     if isinstance(weights, dict):
         sd = weights
     elif Path(weights).suffix in (".safetensors", ".sft", ".sfts"):

@@ -63,8 +63,10 @@ def _w4(mod: nn.Module, name: str = "weight") -> Optional[tuple]:
 
 
 def _wcopy(mod: nn.Module, name: str, weight_dtype: str) -> Optional[tuple]:
-    """The copy of a quantised model's matrix that the batch <= 2 GEMV route streams: under ``"mxfp4"`` the MXFP4 copy where the matrix
-    has one, else the fp8 copy (heads; K no multiple of 32); under ``"fp8"`` the fp8 copy; None for bf16."""
+    """The stored copy of a quantised model's matrix that ``ops.lm_linear`` / ``ops.lm_gated_pair`` stream instead of the bf16 parameter:
+    under ``"mxfp4"`` the MXFP4 copy where the matrix has one (batch <= 2 GEMV route only; above two rows that matrix is read as bf16),
+    else the fp8 copy (heads; K no multiple of 32); under ``"fp8"`` the fp8 copy, which serves the batch <= 2 GEMVs and, above two rows
+    and in prefill, the weight-only fp8 skinny GEMM (``ops.gemm_skinny_fp8w``); None for bf16."""
     if weight_dtype == "bf16":
         return None
     return (_w4(mod, name) if weight_dtype == "mxfp4" else None) or _w8(mod, name)
@@ -382,15 +384,18 @@ class LMModel(StreamingContainer):
 
     @torch.no_grad()
     def quantize_weights_(self, weight_dtype: str = "fp8") -> "LMModel":
-        """Weight-only fp8 storage for the batch <= 2 decode step, in place; returns ``self``.  Idempotent.
+        """Weight-only fp8 storage for the decode step at every batch size and for prefill, in place; returns ``self``.  Idempotent.
 
         Every COVERED matrix -- the temporal transformer's ``in_proj_weight``, ``out_proj.weight``, ``gating.linear_in.weight``,
         ``gating.linear_out.weight``, ``text_linear.weight`` and the ``depformer_in[k]`` (13.5 of the 14.76 GB a Moshi-7B frame
         streams) -- is quantised to e4m3fn bytes with one power-of-two scale per row (``ops.quantize_rows_fp8``), its bf16 parameter is
         OVERWRITTEN with the dequantised values (exact in bf16; also in the tensors of a state dict the model was built from
-        without copying), and ``(q, scale)`` stay on the module as non-persistent buffers.  ``state_dict()``, the batch > 2 routes and
-        anything else that reads ``.weight`` therefore see the same model as the batch <= 2 GEMVs, which stream the fp8 copy
-        (``ops.gemv_fp8w``).  The bf16 copies stay resident.
+        without copying), and ``(q, scale)`` stay on the module as non-persistent buffers.  ``state_dict()`` and anything else that
+        reads ``.weight`` therefore see the same model as the kernels that stream the fp8 copy: the batch <= 2 GEMVs (``ops.gemv_fp8w``)
+        and, above two rows -- the batched step, the many-stream server and pipeline, ``LMGen.prefill`` / ``forward_text(S > 1)`` in
+        64-row chunks -- the weight-only fp8 skinny GEMM (``ops.gemm_skinny_fp8w``: K a multiple of 32, else the bf16 parameter), which
+        returns what the bf16 route returns on these parameters.  The bf16 copies stay resident; the MFMA-ordered bf16 copies of the
+        batched bf16 route are not built for the matrices the fp8 route serves.
 
         NOT covered, on purpose: embeddings (row lookups, not streams), the depth transformer and the audio heads (they live in
         the persistent depth-frame launch's bf16 pointer tables: 1.27 GB per frame, a separate piece of work) and the norms.
@@ -401,9 +406,10 @@ class LMModel(StreamingContainer):
 
         ``weight_dtype="mxfp4"``: the four per-layer matrices of the temporal stack (6.6 of those GB) are stored as OCP MXFP4 instead
         -- e2m1 codes in blocks of 32 along K with one power-of-two scale byte per block (``ops.quantize_blocks_mxfp4``, buffers
-        ``<name>_q4`` / ``<name>_s4``, streamed by ``ops.gemv_mxfp4w``), again with the bf16 parameter overwritten by the exactly
-        representable dequantised values; a per-layer matrix whose K is no multiple of 32 is stored as fp8.  The two output-facing
-        matrices, ``text_linear`` and the ``depformer_in[k]``, stay at fp8.  Round-to-nearest MXFP4 has an rms relative weight
+        ``<name>_q4`` / ``<name>_s4``, streamed by ``ops.gemv_mxfp4w`` at batch <= 2; above two rows these matrices are read as bf16),
+        again with the bf16 parameter overwritten by the exactly representable dequantised values; a per-layer matrix whose K is no
+        multiple of 32 is stored as fp8.  The two output-facing matrices, ``text_linear`` and the ``depformer_in[k]``, stay at fp8 (and
+        take the fp8 skinny GEMM above two rows).  Round-to-nearest MXFP4 has an rms relative weight
         error of 11.5 % on Gaussian rows (fp8: 2.7 %) and speech quality under it has not been evaluated.  Weights with
         ``|w| >= 2^120`` are refused.  A model quantised to one format cannot be quantised to the other: its parameters have
         already been rounded once (``ValueError``)."""

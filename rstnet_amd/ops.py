@@ -1105,6 +1105,71 @@ def gemm_skinny(x, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Opt
     return PackedAct(gp, B, N // 2) if gate_out else out
 
 
+_skinny_weights_fp8w = _PackedWeights()
+_skinny_weights_fp8w_gated = _PackedWeights()
+
+
+def gemm_skinny_fp8w_supported(B: int, N: int, K: int) -> bool:
+    """Shapes ``gemm_skinny_fp8w`` serves (``1 <= B <= 64``, ``K % 32 == 0``, any ``N``); others take the bf16 weight."""
+    return bool(_lib.lib().rst_gemm_skinny_fp8w_supported(B, N, K))
+
+
+@_on_tensor_device
+def skinny_pack_weight_fp8w(q: torch.Tensor, scale: torch.Tensor, interleave_halves: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(q, scale)`` of ``quantize_rows_fp8`` -> (``qp`` uint8 ``[ceil(N/32)*32, K]``: the bytes in the MFMA order of
+    rst_skinny_pack_weight_fp8w, pad rows zero; ``sp`` fp32 ``[ceil(N/32)*32]``: the scales in the same row order, pad rows 0), cached
+    per ``q`` storage (the row-major ``q`` stays: the batch <= 2 GEMV streams that one).  ``interleave_halves``: the layout of gated
+    layers, as ``skinny_pack_weight``."""
+    _chk(q, "q", torch.uint8)
+    _chk(scale, "scale")
+    N, K = q.shape
+    assert scale.shape == (N,), (tuple(q.shape), tuple(scale.shape))
+    if K % 32:
+        raise ValueError(f"rstnet_amd.ops.skinny_pack_weight_fp8w: K = {K} is not a multiple of 32")
+
+    def build():
+        n32 = (N + 31) // 32 * 32
+        qp = torch.empty(n32, K, device=q.device, dtype=torch.uint8)
+        sp = torch.empty(n32, device=q.device, dtype=torch.float32)
+        _lib.check(_lib.lib().rst_skinny_pack_weight_fp8w(_ptr(q), _ptr(scale), _ptr(qp), _ptr(sp), N, K, int(interleave_halves), _stream()))
+        return qp, sp
+    return (_skinny_weights_fp8w_gated if interleave_halves else _skinny_weights_fp8w).get(q, build, also=(scale,))
+
+
+@_on_tensor_device
+def gemm_skinny_fp8w(x, q: torch.Tensor, scale: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Optional[torch.Tensor] = None,
+                     eps: float = 1e-8, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, gate_out: bool = False):
+    """``gemm_skinny`` on fp8 weight storage: ``y[B,N] = (res +) (bias +) scale * (P(x) @ q.T)`` for 1 <= B <= 64, ``q`` e4m3fn bytes
+    ``[N,K]`` with one power-of-two fp32 scale per row (``quantize_rows_fp8``).  ``x``: fp32 rows (packed into bf16 hi / lo planes by one
+    small launch, with the prologue) or a ``PackedAct``; the weight bytes are decoded to bf16 inside rst_gemm_skinny_fp8w_f32 (exact) and
+    the scale multiplies the fp32 accumulators: the values of ``gemm_skinny`` on ``dequantize_rows_fp8(q, scale)`` from half the
+    weight bytes.  ``gate_out``: as ``gemm_skinny`` (returns a ``PackedAct``)."""
+    _chk(res, "res")
+    _chk(bias, "bias")
+    N, K = q.shape
+    B = x.B if isinstance(x, PackedAct) else x.shape[0]
+    if not gemm_skinny_fp8w_supported(B, N, K):
+        raise ValueError(f"rstnet_amd.ops.gemm_skinny_fp8w: no fp8 weight-only skinny GEMM for B = {B}, N = {N}, K = {K} "
+                         "(1 <= B <= 64 and K % 32 == 0 required)")
+    gate_out = gate_out and N % 32 == 0 and res is None
+    qp, sp = skinny_pack_weight_fp8w(q, scale, interleave_halves=gate_out)
+    if isinstance(x, PackedAct):
+        assert prologue == PROLOGUE_NONE and x.K == K
+        xp = x = x.xp
+    else:
+        xp = skinny_pack_act(x, prologue=prologue, alpha=alpha, eps=eps)
+    assert xp.shape[2] == K, (tuple(x.shape), N, K, prologue)
+    out = None if gate_out else torch.empty(B, N, device=xp.device, dtype=torch.float32)
+    gp = _packed_buffer(xp.device, B, N // 2, "gate") if gate_out else None
+    with _profiled("gemm_skinny_fp8w", 2.0 * B * N * K, N * K + 4 * N + 4 * (x.numel() + B * N), (B, N, K)):
+        # the launch plan and its scratch are the bf16 route's (same shape key: launches on one stream are ordered)
+        sc = _split_scratch(xp.device, ("skinny_bf16", B, N, K), lambda: _lib.lib().rst_skinny_bf16_split_plan(B, N, K),
+                            (B + 31) // 32 * 32, N, lambda: (N + 31) // 32)
+        _lib.check(_lib.lib().rst_gemm_skinny_fp8w_f32(_ptr(xp), _ptr(qp), _ptr(sp), _ptr(res), _ptr(bias), _ptr(out), B, N, K, N, _ptr(gp),
+                                                      sc[0], _ptr(sc[1]), _ptr(sc[2]), _stream()))
+    return PackedAct(gp, B, N // 2) if gate_out else out
+
+
 _skinny_weights_fp8 = _PackedWeights()
 
 
@@ -1163,6 +1228,15 @@ def _gemv_stored(x: torch.Tensor, w: torch.Tensor, copy, **kw) -> torch.Tensor:
     return gemv_bf16(x, w, **kw)
 
 
+def _skinny_stored(x, w: torch.Tensor, copy, **kw):
+    """One skinny GEMM (<= 64 rows) on the cheapest stored form of ``w`` that serves it: a plain ``(q, scale)`` fp8 pair and
+    ``gemm_skinny_fp8w_supported``, else the bf16 ``w`` itself (an ``Mxfp4Copy`` has no batched form)."""
+    B, (N, K) = x.B if isinstance(x, PackedAct) else x.shape[0], w.shape
+    if copy is not None and not isinstance(copy, Mxfp4Copy) and gemm_skinny_fp8w_supported(B, N, K):
+        return gemm_skinny_fp8w(x, copy[0], copy[1], **kw)
+    return gemm_skinny(x, w, **kw)
+
+
 @_on_tensor_device
 def lm_gated_pair(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, *, alpha: torch.Tensor, eps: float, res: torch.Tensor,
                   bias_in: Optional[torch.Tensor] = None, bias_out: Optional[torch.Tensor] = None, fp8: bool = False,
@@ -1170,8 +1244,10 @@ def lm_gated_pair(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, *, a
     """The gated MLP of a decode step: ``res + W_out (silu(u) * v)``, ``[u ; v] = W_in rmsnorm(x)`` (modules/gating.py:12-51,
     lit_model.py:399-403).  Batch <= 2: two GEMVs, the gate in the epilogue of the first (row pairs per wave).  Above: the first skinny GEMM applies
     the gate in its epilogue and hands the packed operand straight to the second -- the gated activation never exists in fp32.
-    ``w8_in`` / ``w8_out``: ``(q, scale)`` fp8 copies of the two weights (``quantize_rows_fp8``), read by the GEMV pair only.
-    Either may instead be an ``Mxfp4Copy`` (``quantize_blocks_mxfp4``): the same rule, streamed by ``gemv_mxfp4w``."""
+    ``w8_in`` / ``w8_out``: ``(q, scale)`` fp8 copies of the two weights (``quantize_rows_fp8``): the GEMV pair streams them, and so
+    does the skinny pair above two rows (``gemm_skinny_fp8w``, the gate in the first epilogue as for bf16).
+    Either may instead be an ``Mxfp4Copy`` (``quantize_blocks_mxfp4``): streamed by ``gemv_mxfp4w`` at batch <= 2 only; above, that
+    weight is read as bf16."""
     B = x.shape[0]
     if not fp8 and B <= 2 and B * max(w_out.shape[1], w_in.shape[1]) <= 32768 and w_in.shape[0] % 2 == 0:
         # GEMV pair: every wave of the first owns a (u, v) row pair and writes silu(u) * v; the second is a plain GEMV
@@ -1180,8 +1256,8 @@ def lm_gated_pair(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, *, a
     if fp8 or B <= 2 or B > 64 or w_in.shape[0] % 32:
         u = lm_linear(x, w_in, prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, fp8=fp8, w8=w8_in)
         return lm_linear(u, w_out, prologue=PROLOGUE_SILU_GATE, res=res, bias=bias_out, fp8=fp8, w8=w8_out)
-    g = gemm_skinny(x, w_in, prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, gate_out=True)
-    return gemm_skinny(g, w_out, res=res, bias=bias_out)
+    g = _skinny_stored(x, w_in, w8_in, prologue=PROLOGUE_RMSNORM, alpha=alpha, eps=eps, bias=bias_in, gate_out=True)
+    return _skinny_stored(g, w_out, w8_out, res=res, bias=bias_out)
 
 
 @_on_tensor_device
@@ -1191,10 +1267,11 @@ def lm_linear(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE
     """Batch-size dispatch of one decode-step linear: weight-streaming GEMV for B <= 2, bf16-MFMA skinny GEMM above (the
     prologue then runs inside the activation-packing launch).  ``fp8``: the opt-in e4m3 path (any batch <= 64).
     ``w8 = (q, scale)``: an fp8 copy of ``w`` holding the SAME values (``quantize_rows_fp8`` of a weight that was overwritten with its
-    dequantised form): the GEMV route streams it instead of ``w``; every other route reads ``w``.  ``w8`` may instead be an ``Mxfp4Copy``
-    (``quantize_blocks_mxfp4``) under the same rule: the GEMV route then streams it with ``gemv_mxfp4w``."""
+    dequantised form): the GEMV route streams it instead of ``w``, and so does the skinny route (``gemm_skinny_fp8w``: K % 32 == 0,
+    rows above 64 in chunks of 64); the ``fp8=True`` path and unsupported shapes read ``w``.  ``w8`` may instead be an ``Mxfp4Copy``
+    (``quantize_blocks_mxfp4``): the GEMV route then streams it with ``gemv_mxfp4w``, every other route reads ``w``."""
     if isinstance(x, PackedAct):
-        return gemm_skinny(x, w, prologue=prologue, res=res, bias=bias)
+        return _skinny_stored(x, w, w8, prologue=prologue, res=res, bias=bias)
     if fp8 and x.shape[0] <= 64 and w.shape[1] % 32 == 0 and w.shape[1] <= 16384:
         return gemm_skinny_fp8(x, w, prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
     # the GEMV stages B x K fp32 activations in LDS: beyond two rows that footprint costs occupancy (fewer weight loads in
@@ -1202,10 +1279,10 @@ def lm_linear(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE
     if _gemv_route(x.shape[0], w.shape[1]):
         return _gemv_stored(x, w, w8, prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
     if x.shape[0] <= 64:
-        return gemm_skinny(x, w, prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
+        return _skinny_stored(x, w, w8, prologue=prologue, alpha=alpha, eps=eps, res=res, bias=bias)
     # more rows than one skinny tile set (prompt prefill): chunks of 64 rows, each streaming the weights once
-    return torch.cat([gemm_skinny(x[i:i + 64], w, prologue=prologue, alpha=alpha, eps=eps,
-                                  res=None if res is None else res[i:i + 64], bias=bias) for i in range(0, x.shape[0], 64)])
+    return torch.cat([_skinny_stored(x[i:i + 64], w, w8, prologue=prologue, alpha=alpha, eps=eps,
+                                     res=None if res is None else res[i:i + 64], bias=bias) for i in range(0, x.shape[0], 64)])
 
 
 @_on_tensor_device

@@ -268,7 +268,7 @@ def main(argv=None) -> None:
     p.add_argument("--lm-config", choices=["moshi7b", "tiny"], default="moshi7b")
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--lm-weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
-                   help="storage of the LM's streamed weights: fp8 = e4m3 weight-only copies for the batch-1 step, mxfp4 = OCP MXFP4 copies "
+                   help="storage of the LM's streamed weights: fp8 = e4m3 weight-only copies (GEMV at one or two streams, fp8 skinny GEMM above), mxfp4 = OCP MXFP4 copies "
                         "of the temporal stack's per-layer matrices with the heads at fp8 (LMModel.quantize_weights_; speech quality "
                         "under fp8 or mxfp4 weights has not been evaluated)")
     args = p.parse_args(argv)

@@ -1,6 +1,7 @@
 """`LMGen.prefill` against replaying the same frames through `LMGen.step`, at the Moshi-7B shape, batch 1, one process.
 
     python tools/bench_lm_prefill.py [--samples 60] [--repeats 5] [--lengths 64,256,1024] [--lm-config moshi7b|tiny] [--out profiles/lm_prefill.json]
+                                     [--fp8]
 
 Writes ONE JSON object (and prints it as one line):
 
@@ -9,7 +10,11 @@ Writes ONE JSON object (and prints it as one line):
     one warm-up call of the same length first, then ``--repeats`` timed calls in ONE session, so that the later ones run on a fuller ring
     than the baseline step ever sees; ``baseline_ms = T * step_ms`` is what replaying costs, never a number from the prefill path;
   * ``attention``: `ops.lm_attn_prefill` (its staging launch and its attention launch) and `ops.lm_ring_append` alone, per layer, at the
-    temporal shape (32 heads of 128, bf16 ring of 3000 slots), on an empty ring and on a full one.
+    temporal shape (32 heads of 128, bf16 ring of 3000 slots), on an empty ring and on a full one;
+  * ``--fp8``: ``prefill_fp8w[T]``, after everything above: the model is quantised (``quantize_weights_("fp8")``) and every length runs
+    twice as (fp8, bf16) -- the bf16 legs by switching the ``weight_dtype`` mark on the same model, so both stream the same values;
+    ``ratio_fp8_over_bf16`` compares the two medians of this process (the 64-row chunks run ``ops.gemm_skinny_fp8w`` against
+    ``ops.gemm_skinny``).
 
 Exit status 1 when a 256-frame prefill is not under 1/8 of its baseline: the linears then stream the temporal weights 4 times instead of
 256 times and the depth phase is gone, so missing that means a route is wrong, not slow."""
@@ -91,6 +96,7 @@ def main():
     ap.add_argument("--lengths", default="64,256,1024")
     ap.add_argument("--lm-config", choices=["moshi7b", "tiny"], default="moshi7b")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lm_prefill.json"))
+    ap.add_argument("--fp8", action="store_true", help="add the quantised legs (prefill_fp8w), fp8 / bf16 interleaved on the same model")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_lm_prefill.py measures on the GPU; none is visible")
@@ -118,6 +124,20 @@ def main():
     if a.lm_config == "moshi7b":
         for Tc, pos0 in ((64, 0), (256, 0), (64, 3000), (256, 3000)):
             out["attention"].append(attention_leg(cfg, dev, Tc, pos0, 20))
+    if a.fp8:
+        model.quantize_weights_("fp8")
+        out["prefill_fp8w"] = {}
+        for T in [int(x) for x in a.lengths.split(",")]:
+            ms = {"fp8": [], "bf16": []}
+            for _ in range(2):
+                for dtype in ("fp8", "bf16"):
+                    model.weight_dtype = model.transformer.weight_dtype = dtype
+                    bench._quiesce_host()
+                    ms[dtype].append(prefill_leg(cfg, model, dev, T, a.repeats)["ms"])
+            model.weight_dtype = model.transformer.weight_dtype = "fp8"
+            f8, b16 = statistics.median(ms["fp8"]), statistics.median(ms["bf16"])
+            out["prefill_fp8w"][str(T)] = {"frames": T, "fp8_ms": round(f8, 4), "bf16_ms": round(b16, 4), "ratio_fp8_over_bf16": round(f8 / b16, 4),
+                                           "fp8_legs_ms": ms["fp8"], "bf16_legs_ms": ms["bf16"]}
     gate = out["prefill"].get("256")
     if gate is not None:
         out["hard_condition"] = {"what": "prefill of 256 frames < 1/8 of 256 x step", "holds": bool(gate["ms"] < gate["baseline_ms"] / 8)}
