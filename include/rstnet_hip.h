@@ -484,6 +484,31 @@ int rst_gemm_skinny_fp8w_supported(int B, int N, int K);
 int rst_gemm_skinny_fp8w_f32(const uint16_t* xp, const uint8_t* qp, const float* sp, const float* res, const float* bias, float* y, int B,
                              int N, int K, int ldy, uint16_t* gate_out, int split_k, float* ws, uint32_t* counters, rst_stream_t stream);
 
+/* Weight-only MXFP4 form of rst_gemm_skinny_bf16_f32, for a model quantised with LMModel.quantize_weights_("mxfp4", batched=True) at
+ * 2 < B <= 64 rows and in prompt prefill (chunks of 64 rows): the per-layer call sites of rst_gemv_mxfp4w_f32 -- in_proj / out_proj
+ * (modules/transformer.py:376-423), gating linear_in / linear_out (modules/gating.py:12-51) -- on the stored (q, scale) of
+ * rst_quant_blocks_mxfp4.  Activations are the packed bf16 hi / lo planes xp of rst_skinny_pack_act_f32 (or of a producer), unchanged;
+ * every e2m1 code is decoded times its block scale 2^e to the bf16 operand inside the launch (v_cvt_scalef32_pk_f32_fp4; exact: two
+ * significant bits, e >= -125, |w| < 2^120) and runs on the same v_mfma_f32_32x32x16_bf16.  Nothing is applied to the accumulators, so
+ * with the shared launch plan y is what rst_gemm_skinny_bf16_f32 computes on the dequantised matrix, bit for bit.
+ *   rst_skinny_pack_weight_mxfp4w: q [N][K/2] code bytes (even k in the low nibble), scale [N][K/32] bytes e + 127 ->
+ *     qp [ceil(N/32)*32 * K/2] bytes in the order [tile of 32 rows][K/32][64 lanes = 32 * ((k / 8) % 2) + row % 32][8 B = the 4 code
+ *     bytes of the lane's 8 k of step 2p | of step 2p+1] (nibble order kept; an 8-byte lane load carries two MFMA steps = the lane's
+ *     share of one scale block; pad rows zero codes), i.e. byte ((((r/32) * (K/32) + k/32) * 64) + ((k/8)%2) * 32 + r%32) * 8 +
+ *     ((k/16)%2) * 4 + (k%8)/2 for packed row r, and sp [ceil(N/32)][K/32][32 rows] the scale bytes (pad rows 127); once per weight,
+ *     whatever B.  interleave_halves as rst_skinny_pack_weight_bf16 (N % 32 == 0), applied to code rows and scale bytes alike.
+ *     K % 32 == 0, q 4-byte and qp 8-byte aligned.
+ *   rst_gemm_skinny_mxfp4w_supported(B, N, K): 1 for exactly the served shapes, 1 <= B <= 64, N > 0, K % 32 == 0; callers take the
+ *     bf16 route (same values, four times the bytes) for the others.
+ *   rst_gemm_skinny_mxfp4w_f32: arguments as rst_gemm_skinny_fp8w_f32 with the scale bytes sp in place of the fp32 row scales: res /
+ *     bias optional, gate_out (qp packed with interleave_halves, no residual, y may be NULL), split_k =
+ *     rst_skinny_bf16_split_plan(B, N, K) with the same ws / counters scratch and protocol. */
+int rst_skinny_pack_weight_mxfp4w(const uint8_t* q, const uint8_t* scale, uint8_t* qp, uint8_t* sp, int N, int K, int interleave_halves,
+                                  rst_stream_t stream);
+int rst_gemm_skinny_mxfp4w_supported(int B, int N, int K);
+int rst_gemm_skinny_mxfp4w_f32(const uint16_t* xp, const uint8_t* qp, const uint8_t* sp, const float* res, const float* bias, float* y, int B,
+                               int N, int K, int ldy, uint16_t* gate_out, int split_k, float* ws, uint32_t* counters, rst_stream_t stream);
+
 /* Opt-in fp8 form of the three entry points above (BASELINE.json configs[4]: fp8 MFMA GEMMs on the temporal blocks at batch
  * 32): OCP e4m3 operands on v_mfma_f32_32x32x16_fp8_fp8, weights with one scale per row (amax / 448, quantised once),
  * activations with one dynamic scale per batch row (quantised by the prologue launch), y = scale_x[b] * scale_w[n] * acc.

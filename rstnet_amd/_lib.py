@@ -89,6 +89,9 @@ SIGNATURES = {
     "rst_skinny_pack_weight_fp8w": [_p, _p, _p, _p, _i, _i, _i, _p],
     "rst_gemm_skinny_fp8w_supported": [_i, _i, _i],
     "rst_gemm_skinny_fp8w_f32": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p],
+    "rst_skinny_pack_weight_mxfp4w": [_p, _p, _p, _p, _i, _i, _i, _p],
+    "rst_gemm_skinny_mxfp4w_supported": [_i, _i, _i],
+    "rst_gemm_skinny_mxfp4w_f32": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p],
     "rst_embed_sum_bf16": [_p, C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), _i, _p, _p, _i, _i, _i, _i, _p],
     "rst_rmsnorm_f32": [_p, _p, _p, _l, _i, _f, _p],
     "rst_lm_rope_append_f32": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p],

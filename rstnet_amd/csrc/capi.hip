@@ -24,7 +24,7 @@ int rst_check_launch(const char* what) {
 
 extern "C" {
 
-int rst_version(void) { return 124; }      // 124: + rst_skinny_pack_weight_fp8w, rst_gemm_skinny_fp8w_f32 / _supported (fp8 weight-only skinny GEMM); 123: + rst_quant_blocks_mxfp4, rst_gemv_mxfp4w_f32 / _supported (MXFP4 weight-only GEMV); 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
+int rst_version(void) { return 125; }      // 125: + rst_skinny_pack_weight_mxfp4w, rst_gemm_skinny_mxfp4w_f32 / _supported (MXFP4 weight-only skinny GEMM); 124: + rst_skinny_pack_weight_fp8w, rst_gemm_skinny_fp8w_f32 / _supported (fp8 weight-only skinny GEMM); 123: + rst_quant_blocks_mxfp4, rst_gemv_mxfp4w_f32 / _supported (MXFP4 weight-only GEMV); 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
                                            // rst_rvq_search_chain_f32, rst_embed_sum_bf16(add_stride); 105: round 4
 const char* rst_last_error(void) { return g_err; }
 
@@ -545,6 +545,24 @@ int rst_gemm_skinny_fp8w_f32(const uint16_t* xp, const uint8_t* qp, const float*
     RST_REQUIRE(rst_gemm_skinny_fp8w_supported_impl(B, N, K), "gemm_skinny_fp8w: need 1 <= B <= 64, N > 0 and K %% 32 == 0 (B=%d N=%d K=%d)", B, N, K);
     SkinnyParams p = {};
     p.xp = xp; p.w8 = qp; p.wscale = sp; p.res = res; p.bias = bias; p.y = y; p.B = B; p.N = N; p.K = K; p.ldy = ldy;
+    p.gate_out = gate_out; p.gate_plane = (long)((B + 31) / 32 * 32) * (N / 2);
+    p.split_k = split_k; p.ws = ws; p.counters = counters;
+    return rst_launch_gemm_skinny(p, (hipStream_t)stream);
+}
+
+int rst_skinny_pack_weight_mxfp4w(const uint8_t* q, const uint8_t* scale, uint8_t* qp, uint8_t* sp, int N, int K, int interleave_halves,
+                                  rst_stream_t stream) {
+    return rst_launch_skinny_pack_weight_mxfp4w(q, scale, qp, sp, N, K, interleave_halves, (hipStream_t)stream);
+}
+
+int rst_gemm_skinny_mxfp4w_supported(int B, int N, int K) { return rst_gemm_skinny_mxfp4w_supported_impl(B, N, K); }
+
+int rst_gemm_skinny_mxfp4w_f32(const uint16_t* xp, const uint8_t* qp, const uint8_t* sp, const float* res, const float* bias, float* y, int B,
+                               int N, int K, int ldy, uint16_t* gate_out, int split_k, float* ws, uint32_t* counters, rst_stream_t stream) {
+    RST_REQUIRE(xp && qp && sp, "gemm_skinny_mxfp4w: null packed activations, codes or scale bytes");
+    RST_REQUIRE(rst_gemm_skinny_mxfp4w_supported_impl(B, N, K), "gemm_skinny_mxfp4w: need 1 <= B <= 64, N > 0 and K %% 32 == 0 (B=%d N=%d K=%d)", B, N, K);
+    SkinnyParams p = {};
+    p.xp = xp; p.w4 = qp; p.w4scale = sp; p.res = res; p.bias = bias; p.y = y; p.B = B; p.N = N; p.K = K; p.ldy = ldy;
     p.gate_out = gate_out; p.gate_plane = (long)((B + 31) / 32 * 32) * (N / 2);
     p.split_k = split_k; p.ws = ws; p.counters = counters;
     return rst_launch_gemm_skinny(p, (hipStream_t)stream);

@@ -120,7 +120,33 @@ __device__ __forceinline__ void decode_fp8w_pair(const u32x4 q, bf16x8& e, bf16x
     o = __builtin_bit_cast(bf16x8, r[1]);
 }
 
-template <int NB, int CT, bool W8 = false>   // batch tiles of 32, weight-row tiles per workgroup, fp8 weight bytes + row scales
+// W4 (weight-only MXFP4, rst_gemm_skinny_mxfp4w_f32): the weights are OCP e2m1 codes in the order of mxfp4_packed_index below -- the
+// fp8 order at half the bytes, [tile of 32 rows][K/32][64 lanes][8 B = the 4 code bytes of the lane's 8 k of step 2p | of step 2p+1],
+// even k in the low nibble -- so an 8-byte lane load carries the operand of two steps = the lane's share of ONE 32-k scale block (a
+// wave-level load is 512 contiguous bytes), and one scale byte goes with it: sp [tile][K/32][32 rows] (pad rows 127), a byte load per
+// lane at lane % 32.  Decode: v_cvt_scalef32_pk_f32_fp4 with the block scale 2^e = uint_as_float(byte << 23) (the two codes of one byte
+// times 2^e, exact: the instruction of the batch <= 2 GEMV, lm_gemv_fp4.hip) and the upper halves of the two floats packed by
+// v_perm_b32 -- code * 2^e has 2 significant bits and is a normal number (e >= -125), so the truncation drops zeros only: 4 + 4 VALU
+// per dword = per step and column tile, as for fp8.  The operand IS the dequantised weight: nothing is applied to the accumulators,
+// and with the steps dealt as in the bf16 form (odd first step: as W8) the result equals the bf16 form's on the dequantised matrix bit
+// for bit, unconditionally.
+typedef unsigned u32x2w __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u32x4 decode_mxfp4w_step(const unsigned q, const float sc) {
+    const f32x2w w0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(q, sc, 0), w1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(q, sc, 1);
+    const f32x2w w2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(q, sc, 2), w3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(q, sc, 3);
+    return u32x4{__builtin_amdgcn_perm(__float_as_uint(w0[1]), __float_as_uint(w0[0]), 0x07060302u),
+                 __builtin_amdgcn_perm(__float_as_uint(w1[1]), __float_as_uint(w1[0]), 0x07060302u),
+                 __builtin_amdgcn_perm(__float_as_uint(w2[1]), __float_as_uint(w2[0]), 0x07060302u),
+                 __builtin_amdgcn_perm(__float_as_uint(w3[1]), __float_as_uint(w3[0]), 0x07060302u)};
+}
+__device__ __forceinline__ void decode_mxfp4w_pair(const u32x2w q, const unsigned sb, bf16x8& e, bf16x8& o) {
+    const float sc = __uint_as_float(sb << 23);
+    e = __builtin_bit_cast(bf16x8, decode_mxfp4w_step(q[0], sc));
+    o = __builtin_bit_cast(bf16x8, decode_mxfp4w_step(q[1], sc));
+}
+
+// batch tiles of 32, weight-row tiles per workgroup, fp8 weight bytes + row scales, MXFP4 codes + block scale bytes (at most one of the two)
+template <int NB, int CT, bool W8 = false, bool W4 = false>
 __global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_skinny_kernel(const SkinnyParams p) {
     __shared__ float red[SKINNY_WAVES][NB * 32][33];
     __shared__ float gtile[NB * 32 * 16];      // gated epilogue: silu(u) * v of a column tile
@@ -140,12 +166,15 @@ __global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_skinny_kernel(const Sk
     const unsigned short* wt[CT];
     const unsigned char* wq[CT];
     float wsc[CT];                  // W8: scale of weight row n = lane % 32 of each column tile (pad rows: 0)
+    const unsigned char* wsb[CT];   // W4: scale bytes of weight row n = lane % 32, one per pair of steps at a stride of 32
+    static_assert(!(W8 && W4), "one weight format per instantiation");
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
         const long tc = min(tile0 + c, tiles - 1);
-        wt[c] = W8 ? nullptr : p.w + (tc * steps * 64 + lane) * 8;
-        wq[c] = W8 ? p.w8 + (tc * (steps / 2) * 64 + lane) * 16 : nullptr;
+        wt[c] = W8 || W4 ? nullptr : p.w + (tc * steps * 64 + lane) * 8;
+        wq[c] = W8 ? p.w8 + (tc * (steps / 2) * 64 + lane) * 16 : (W4 ? p.w4 + (tc * (steps / 2) * 64 + lane) * 8 : nullptr);
         wsc[c] = W8 ? p.wscale[tc * 32 + (lane & 31)] : 1.f;
+        wsb[c] = W4 ? p.w4scale + tc * (steps / 2) * 32 + (lane & 31) : nullptr;
     }
     f32x16 acc[NB][CT];
 #pragma unroll
@@ -176,10 +205,13 @@ __global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_skinny_kernel(const Sk
     // (Measured and dropped, round 3: requesting the weights of 32 / 16 steps up front with the activations following 8 steps at a time --
     // one HBM round trip per 32 steps instead of per 8 -- is SLOWER: 7.32 vs 7.10 ms per frame at the Moshi-7B shape, batch 32, 3.64 vs
     // 3.62 ms for the GPT frame, A/B inside one session.)
-    static_assert(UN % 2 == 0, "W8: a lane load carries two steps");
-    for (int s = W8 ? (s0 & ~1) : s0; s < s1; s += UN) {      // W8: s stays even, a pair of steps per weight load
+    static_assert(UN % 2 == 0, "W8 / W4: a lane load carries two steps");
+    constexpr bool WQ = W8 || W4;
+    for (int s = WQ ? (s0 & ~1) : s0; s < s1; s += UN) {      // W8 / W4: s stays even, a pair of steps per weight load
         bf16x8 a[UN][CT], bh[UN][NB], bl[UN][NB];
         u32x4 aq[UN / 2][CT];
+        u32x2w a4[UN / 2][CT];
+        unsigned sb4[UN / 2][CT];
         if (W8) {
 #pragma unroll
             for (int u = 0; u < UN / 2; ++u)
@@ -187,11 +219,21 @@ __global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_skinny_kernel(const Sk
                 for (int c = 0; c < CT; ++c)
                     aq[u][c] = s + 2 * u < s1 ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wq[c] + (long)(s / 2 + u) * 1024)) : u32x4{0u, 0u, 0u, 0u};
         }
+        if (W4) {
+#pragma unroll
+            for (int u = 0; u < UN / 2; ++u)
+#pragma unroll
+                for (int c = 0; c < CT; ++c) {
+                    const bool okp = s + 2 * u < s1;        // pair s / 2 + u < steps / 2: inside the packed codes and scale bytes
+                    a4[u][c] = okp ? __builtin_nontemporal_load(reinterpret_cast<const u32x2w*>(wq[c] + (long)(s / 2 + u) * 512)) : u32x2w{0u, 0u};
+                    sb4[u][c] = okp ? wsb[c][(long)(s / 2 + u) * 32] : 127u;
+                }
+        }
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
-            const bool ok = (!W8 || s + u >= s0) && s + u < s1;
+            const bool ok = (!WQ || s + u >= s0) && s + u < s1;
             const long so = (long)(s + u) * 512;
-            if (!W8) {
+            if (!WQ) {
 #pragma unroll
                 for (int c = 0; c < CT; ++c)
                     a[u][c] = ok ? __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wt[c] + so)) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
@@ -207,6 +249,12 @@ __global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_skinny_kernel(const Sk
             for (int u = 0; u < UN / 2; ++u)
 #pragma unroll
                 for (int c = 0; c < CT; ++c) decode_fp8w_pair(aq[u][c], a[2 * u][c], a[2 * u + 1][c]);
+        }
+        if (W4) {
+#pragma unroll
+            for (int u = 0; u < UN / 2; ++u)
+#pragma unroll
+                for (int c = 0; c < CT; ++c) decode_mxfp4w_pair(a4[u][c], sb4[u][c], a[2 * u][c], a[2 * u + 1][c]);
         }
 #pragma unroll
         for (int u = 0; u < UN; ++u)
@@ -633,8 +681,10 @@ int rst_skinny_bf16_split_plan_impl(int B, int N, int K) {
 
 int rst_launch_gemm_skinny(const SkinnyParams& p, hipStream_t stream) {
     RST_REQUIRE(p.B >= 1 && p.B <= 64 && p.N > 0 && p.K > 0 && p.K % 16 == 0, "gemm_skinny: need 1 <= B <= 64 and K %% 16 == 0 (B=%d K=%d)", p.B, p.K);
-    RST_REQUIRE((p.xp || p.xf) && (p.w || p.w8) && (p.y || p.gate_out), "gemm_skinny: null pointer");
+    RST_REQUIRE((p.xp || p.xf) && (p.w || p.w8 || p.w4) && (p.y || p.gate_out), "gemm_skinny: null pointer");
     const bool xf = p.xp == nullptr;
+    RST_REQUIRE(!p.w4 || (!p.w && !p.w8 && !xf && p.w4scale && p.K % 32 == 0 && (uintptr_t)p.w4 % 8 == 0),
+                "gemm_skinny_mxfp4w: needs packed activations, block scale bytes, K %% 32 == 0 and 8-byte aligned codes (K=%d)", p.K);
     RST_REQUIRE(!p.w8 || (!p.w && !xf && p.wscale && p.K % 32 == 0 && (uintptr_t)p.w8 % 16 == 0),
                 "gemm_skinny_fp8w: needs packed activations, row scales, K %% 32 == 0 and 16-byte aligned weights (K=%d)", p.K);
     RST_REQUIRE(!xf || (p.K % 256 == 0 && p.ldx % 4 == 0 && p.ldx >= p.K && (uintptr_t)p.xf % 16 == 0 && (p.xmode == 0 || (p.xmode == 1 && p.alpha)) && p.split_k <= 1),
@@ -671,6 +721,19 @@ int rst_launch_gemm_skinny(const SkinnyParams& p, hipStream_t stream) {
             else hipLaunchKernelGGL((gemm_skinny_kernel<2, 1, true>), grid, dim3(threads), 0, stream, p);
         }
         return rst_check_launch("gemm_skinny_fp8w");
+    }
+    if (p.w4) {
+        if (p.B <= 32) {
+            if (ct == 4) hipLaunchKernelGGL((gemm_skinny_kernel<1, 4, false, true>), grid, dim3(threads), 0, stream, p);
+            else if (ct == 3) hipLaunchKernelGGL((gemm_skinny_kernel<1, 3, false, true>), grid, dim3(threads), 0, stream, p);
+            else if (ct == 2) hipLaunchKernelGGL((gemm_skinny_kernel<1, 2, false, true>), grid, dim3(threads), 0, stream, p);
+            else hipLaunchKernelGGL((gemm_skinny_kernel<1, 1, false, true>), grid, dim3(threads), 0, stream, p);
+        } else {
+            if (ct == 3) hipLaunchKernelGGL((gemm_skinny_kernel<2, 3, false, true>), grid, dim3(threads), 0, stream, p);
+            else if (ct == 2) hipLaunchKernelGGL((gemm_skinny_kernel<2, 2, false, true>), grid, dim3(threads), 0, stream, p);
+            else hipLaunchKernelGGL((gemm_skinny_kernel<2, 1, false, true>), grid, dim3(threads), 0, stream, p);
+        }
+        return rst_check_launch("gemm_skinny_mxfp4w");
     }
     if (p.B <= 32) {
         if (ct == 4) hipLaunchKernelGGL((gemm_skinny_kernel<1, 4>), grid, dim3(threads), 0, stream, p);
@@ -948,4 +1011,50 @@ int rst_launch_skinny_pack_weight_fp8w(const unsigned char* q, const float* scal
     hipLaunchKernelGGL(skinny_pack_weight_fp8w_kernel, dim3(cap_grid((total + 255) / 256, 8192)), dim3(256), 0, stream, q, scale, qp, sp, N, K,
                        interleave);
     return rst_check_launch("skinny_pack_weight_fp8w");
+}
+
+// ======================================================================================================================
+// Weight-only MXFP4 operand of gemm_skinny_kernel<NB, CT, false, true>: the stored (q [N][K/2], scale [N][K/32]) of
+// rst_quant_blocks_mxfp4 -> codes in the order of mxfp4_packed_index (fp8_packed_index at half the bytes; pad rows: zero codes) and
+// the scale bytes as [tile of 32 rows][K/32][32 rows] (pad rows: 127 = 2^0).  interleave: the row permutation of
+// skinny_pack_weight_kernel, applied to codes and scale bytes alike.  Nothing depends on B or on the unroll: one copy per weight.
+// ======================================================================================================================
+namespace {
+
+__device__ __forceinline__ long mxfp4_packed_index(int row, int k, int K) {     // byte offset of the code pair (k even, k + 1); even k: low nibble
+    return ((((long)(row >> 5) * (K >> 5) + (k >> 5)) * 64) + ((k >> 3) & 1) * 32 + (row & 31)) * 8 + ((k >> 4) & 1) * 4 + ((k & 7) >> 1);
+}
+
+__global__ __launch_bounds__(256) void skinny_pack_weight_mxfp4w_kernel(const unsigned char* __restrict__ q, const unsigned char* __restrict__ scale,
+                                                                       unsigned char* __restrict__ qp, unsigned char* __restrict__ sp, int N, int K,
+                                                                       int interleave) {
+    const long total = (long)((N + 31) / 32) * 32 * (K / 8);
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int row = (int)(idx / (K / 8)), k = (int)(idx % (K / 8)) * 8;
+        int src = row;
+        if (interleave) {
+            const int t = row >> 5, r = row & 31;
+            src = (r < 16 ? 0 : N / 2) + t * 16 + (r & 15);
+        }
+        unsigned v = 0u;                    // the 4 code bytes of 8 consecutive k
+        if (row < N) v = *reinterpret_cast<const unsigned*>(q + (long)src * (K / 2) + k / 2);
+        *reinterpret_cast<unsigned*>(qp + mxfp4_packed_index(row, k, K)) = v;
+        if (k % 32 == 0)
+            sp[((long)(row >> 5) * (K / 32) + k / 32) * 32 + (row & 31)] = row < N ? scale[(long)src * (K / 32) + k / 32] : (unsigned char)127;
+    }
+}
+
+}  // namespace
+
+int rst_gemm_skinny_mxfp4w_supported_impl(int B, int N, int K) { return B >= 1 && B <= 64 && N > 0 && K > 0 && K % 32 == 0; }
+
+int rst_launch_skinny_pack_weight_mxfp4w(const unsigned char* q, const unsigned char* scale, unsigned char* qp, unsigned char* sp, int N, int K,
+                                         int interleave, hipStream_t stream) {
+    RST_REQUIRE(q && scale && qp && sp && N > 0 && K > 0 && K % 32 == 0 && (uintptr_t)q % 4 == 0 && (uintptr_t)qp % 8 == 0,
+                "skinny_pack_weight_mxfp4w: bad arguments (K %% 32 == 0 and aligned buffers required, K=%d)", K);
+    RST_REQUIRE(!interleave || N % 32 == 0, "skinny_pack_weight_mxfp4w: interleaving the two halves needs N %% 32 == 0 (N=%d)", N);
+    const long total = (long)((N + 31) / 32) * 32 * (K / 8);
+    hipLaunchKernelGGL(skinny_pack_weight_mxfp4w_kernel, dim3(cap_grid((total + 255) / 256, 8192)), dim3(256), 0, stream, q, scale, qp, sp, N, K,
+                       interleave);
+    return rst_check_launch("skinny_pack_weight_mxfp4w");
 }

@@ -434,8 +434,14 @@ struct SkinnyParams {
     // weight-only fp8 form (w == nullptr, packed activations only): e4m3fn bytes decoded to the bf16 operand inside the launch
     const unsigned char* w8;    // packed weights [ceil(N/32)][K/32][64][16] (rst_launch_skinny_pack_weight_fp8w)
     const float* wscale;        // [ceil(N/32)*32] power-of-two row scales in packed row order, applied to the accumulators
+    // weight-only MXFP4 form (w == w8 == nullptr, packed activations only): e2m1 codes times their block scale = the bf16 operand
+    const unsigned char* w4;    // packed codes [ceil(N/32)][K/32][64][8] (rst_launch_skinny_pack_weight_mxfp4w)
+    const unsigned char* w4scale;   // [ceil(N/32)][K/32][32] scale bytes e + 127 of the 32-k blocks, pad rows 127
 };
 int rst_launch_gemm_skinny(const SkinnyParams& p, hipStream_t stream);
+int rst_gemm_skinny_mxfp4w_supported_impl(int B, int N, int K);
+int rst_launch_skinny_pack_weight_mxfp4w(const unsigned char* q, const unsigned char* scale, unsigned char* qp, unsigned char* sp, int N, int K,
+                                         int interleave, hipStream_t stream);
 int rst_gemm_skinny_fp8w_supported_impl(int B, int N, int K);
 int rst_launch_skinny_pack_weight_fp8w(const unsigned char* q, const float* scale, unsigned char* qp, float* sp, int N, int K, int interleave,
                                        hipStream_t stream);

@@ -17,11 +17,12 @@ _lm_kwargs = dict(dim=4096, text_card=32000, existing_text_padding_id=3, n_q=16,
 
 
 def get_moshi_lm(weights: Union[str, Path, Dict[str, torch.Tensor]], device: Union[torch.device, str] = "cuda",
-                 lm_kwargs: Optional[dict] = None, weight_dtype: str = "bf16") -> LMModel:
+                 lm_kwargs: Optional[dict] = None, weight_dtype: str = "bf16", batched: bool = False) -> LMModel:
     """``weights``: a ``.safetensors`` file, a ``torch.save``d package (``pkg["fsdp_best_state"]["model"]``, loaders.py:153-158) or a
     ``state_dict``.  Tensors are moved to ``device`` as bf16 and adopted without copying; ``lm_kwargs`` overrides the Moshi-7B
     hyper-parameters (e.g. a smaller model trained with the same code).  ``weight_dtype="fp8"`` / ``"mxfp4"``: the loaded model is quantised with
-    ``LMModel.quantize_weights_`` (weight-only e4m3 / MXFP4 copies; fp8 copies serve every batch size and prefill, MXFP4 the batch <= 2 step; bf16 is the default)."""
+    ``LMModel.quantize_weights_`` (weight-only e4m3 / MXFP4 copies; fp8 copies serve every batch size and prefill, MXFP4 the batch <= 2 step
+    and, with ``batched=True``, the rows above two and prefill as well -- ``ops.gemm_skinny_mxfp4w``; bf16 is the default)."""
     if isinstance(weights, dict):
         sd = weights
     elif Path(weights).suffix in (".safetensors", ".sft", ".sfts"):
@@ -30,4 +31,4 @@ def get_moshi_lm(weights: Union[str, Path, Dict[str, torch.Tensor]], device: Uni
     else:
         sd = torch.load(weights, map_location="cpu")["fsdp_best_state"]["model"]
     sd = {k: v.to(device=device, dtype=torch.bfloat16) for k, v in sd.items()}
-    return LMModel.from_state_dict(sd, dict(lm_kwargs or _lm_kwargs), weight_dtype=weight_dtype)
+    return LMModel.from_state_dict(sd, dict(lm_kwargs or _lm_kwargs), weight_dtype=weight_dtype, batched=batched)

@@ -55,21 +55,23 @@ def _w8(mod: nn.Module, name: str = "weight") -> Optional[tuple]:
     return _wq(mod, name, "8")
 
 
-def _w4(mod: nn.Module, name: str = "weight") -> Optional[tuple]:
+def _w4(mod: nn.Module, name: str = "weight", batched: bool = False) -> Optional[tuple]:
     """The MXFP4 copy (``ops.Mxfp4Copy``) of parameter ``name`` of ``mod`` (``LMModel.quantize_weights_("mxfp4")``), or None; dropped
-    like the fp8 copy of ``_w8`` when the bf16 parameter was replaced or written since."""
+    like the fp8 copy of ``_w8`` when the bf16 parameter was replaced or written since.  ``batched``: the model opted in to the batched
+    route, so the copy is handed out as an ``ops.Mxfp4BatchedCopy`` (same fields; ``ops.lm_linear`` streams it above two rows too)."""
     c = _wq(mod, name, "4")
-    return None if c is None else ops.Mxfp4Copy(*c)
+    return None if c is None else (ops.Mxfp4BatchedCopy if batched else ops.Mxfp4Copy)(*c)
 
 
-def _wcopy(mod: nn.Module, name: str, weight_dtype: str) -> Optional[tuple]:
+def _wcopy(mod: nn.Module, name: str, weight_dtype: str, batched: bool = False) -> Optional[tuple]:
     """The stored copy of a quantised model's matrix that ``ops.lm_linear`` / ``ops.lm_gated_pair`` stream instead of the bf16 parameter:
-    under ``"mxfp4"`` the MXFP4 copy where the matrix has one (batch <= 2 GEMV route only; above two rows that matrix is read as bf16),
-    else the fp8 copy (heads; K no multiple of 32); under ``"fp8"`` the fp8 copy, which serves the batch <= 2 GEMVs and, above two rows
-    and in prefill, the weight-only fp8 skinny GEMM (``ops.gemm_skinny_fp8w``); None for bf16."""
+    under ``"mxfp4"`` the MXFP4 copy where the matrix has one (batch <= 2 GEMV route; above two rows that matrix is read as bf16 unless
+    ``batched`` -- the model's ``mxfp4_batched`` -- hands the copy out as an ``ops.Mxfp4BatchedCopy``, which the weight-only MXFP4 skinny
+    GEMM ``ops.gemm_skinny_mxfp4w`` streams there and in prefill), else the fp8 copy (heads; K no multiple of 32); under ``"fp8"`` the
+    fp8 copy, which serves the batch <= 2 GEMVs and, above two rows and in prefill, the weight-only fp8 skinny GEMM (``ops.gemm_skinny_fp8w``); None for bf16."""
     if weight_dtype == "bf16":
         return None
-    return (_w4(mod, name) if weight_dtype == "mxfp4" else None) or _w8(mod, name)
+    return (_w4(mod, name, batched) if weight_dtype == "mxfp4" else None) or _w8(mod, name)
 
 
 def _attach_copy(mod: nn.Module, name: str, tag: str, q: torch.Tensor, scale: torch.Tensor) -> None:
@@ -185,6 +187,7 @@ class StreamingTransformer(StreamingModule[_StepState]):
         self.d_model, self.num_heads, self.context = d_model, num_heads, context
         self.rope, self.max_period, self.weights_per_step = positional_embedding == "rope", max_period, weights_per_step
         self.weight_dtype = "bf16"        # "fp8" / "mxfp4": LMModel.quantize_weights_ left copies on the layers; the chain route streams them
+        self.mxfp4_batched = False        # "mxfp4" only: the MXFP4 copies are streamed above two rows too (quantize_weights_(..., batched=True))
         self.layers = nn.ModuleList([_Layer(d_model, dim_feedforward, weights_per_step, device=device, dtype=dtype)
                                      for _ in range(num_layers)])
 
@@ -209,16 +212,16 @@ class StreamingTransformer(StreamingModule[_StepState]):
         """The layers as ``stack.run_layers`` reads them: with per-step weights the matrices of step ``k_idx``; of a quantised model also the
         fp8 / MXFP4 copies (never the depth transformer: its weights are not covered)."""
         E, Q = self.d_model, self.weights_per_step
-        wd = "bf16" if Q else self.weight_dtype
+        wd, bt = "bf16" if Q else self.weight_dtype, self.mxfp4_batched
 
         def view(layer):
             att, gate = layer.self_attn, layer.gating[k_idx] if Q else layer.gating
             w_in, w_out = att.in_proj_weight, att.out_proj.weight
             if Q:
                 w_in, w_out = w_in.view(Q, 3 * E, E)[k_idx], w_out.view(Q, E, E)[k_idx]
-            return LayerView(LinearView(w_in, w8=_wcopy(att, "in_proj_weight", wd)), LinearView(w_out, w8=_wcopy(att.out_proj, "weight", wd)),
-                             LinearView(gate.linear_in.weight, w8=_wcopy(gate.linear_in, "weight", wd)),
-                             LinearView(gate.linear_out.weight, w8=_wcopy(gate.linear_out, "weight", wd)),
+            return LayerView(LinearView(w_in, w8=_wcopy(att, "in_proj_weight", wd, bt)), LinearView(w_out, w8=_wcopy(att.out_proj, "weight", wd, bt)),
+                             LinearView(gate.linear_in.weight, w8=_wcopy(gate.linear_in, "weight", wd, bt)),
+                             LinearView(gate.linear_out.weight, w8=_wcopy(gate.linear_out, "weight", wd, bt)),
                              (layer.norm1.alpha_f32(), layer.norm1.eps), (layer.norm2.alpha_f32(), layer.norm2.eps))
         return [view(layer) for layer in self.layers]
 
@@ -345,6 +348,7 @@ class LMModel(StreamingContainer):
         self.config = ModelConfig(model_type="lora")
         self._in_cat8 = _PackedCache()
         self.weight_dtype = "bf16"
+        self.mxfp4_batched = False        # quantize_weights_("mxfp4", batched=True): the MXFP4 copies also serve the routes above two rows
         # the depth phase of a frame (lm.depth_frame.DepthDecoder; LMGen._depth and the methods below delegate to it)
         self.depth_decoder = DepthDecoder(self.depformer, self.depformer_in, [self.depformer_text_emb, *self.depformer_emb], self.linears)
 
@@ -383,7 +387,7 @@ class LMModel(StreamingContainer):
             yield m, "weight"
 
     @torch.no_grad()
-    def quantize_weights_(self, weight_dtype: str = "fp8") -> "LMModel":
+    def quantize_weights_(self, weight_dtype: str = "fp8", batched: bool = False) -> "LMModel":
         """Weight-only fp8 storage for the decode step at every batch size and for prefill, in place; returns ``self``.  Idempotent.
 
         Every COVERED matrix -- the temporal transformer's ``in_proj_weight``, ``out_proj.weight``, ``gating.linear_in.weight``,
@@ -406,13 +410,24 @@ class LMModel(StreamingContainer):
 
         ``weight_dtype="mxfp4"``: the four per-layer matrices of the temporal stack (6.6 of those GB) are stored as OCP MXFP4 instead
         -- e2m1 codes in blocks of 32 along K with one power-of-two scale byte per block (``ops.quantize_blocks_mxfp4``, buffers
-        ``<name>_q4`` / ``<name>_s4``, streamed by ``ops.gemv_mxfp4w`` at batch <= 2; above two rows these matrices are read as bf16),
+        ``<name>_q4`` / ``<name>_s4``, streamed by ``ops.gemv_mxfp4w`` at batch <= 2; above two rows these matrices are read as bf16 unless ``batched``, below),
         again with the bf16 parameter overwritten by the exactly representable dequantised values; a per-layer matrix whose K is no
         multiple of 32 is stored as fp8.  The two output-facing matrices, ``text_linear`` and the ``depformer_in[k]``, stay at fp8 (and
         take the fp8 skinny GEMM above two rows).  Round-to-nearest MXFP4 has an rms relative weight
         error of 11.5 % on Gaussian rows (fp8: 2.7 %) and speech quality under it has not been evaluated.  Weights with
         ``|w| >= 2^120`` are refused.  A model quantised to one format cannot be quantised to the other: its parameters have
-        already been rounded once (``ValueError``)."""
+        already been rounded once (``ValueError``).
+
+        ``batched=True`` (``"mxfp4"`` only; opt-in, off by default): the MXFP4 copies are streamed above two rows as well -- the batched
+        step, the many-stream server and pipeline, ``LMGen.prefill`` / ``forward_text(S > 1)`` in 64-row chunks -- by the weight-only
+        MXFP4 skinny GEMM (``ops.gemm_skinny_mxfp4w``: the codes decoded to the bf16 operand inside the launch, bit for bit what the bf16
+        route returns on these parameters, from a quarter of the bytes), and the MFMA-ordered bf16 copies of the batched bf16 route are
+        not built for these matrices.  ``mxfp4_batched`` says which route the model takes.  On a model already at ``"mxfp4"`` the call
+        only switches the route on (nothing is quantised again; the route stays on once asked for).  With ``"fp8"`` it raises
+        ``ValueError``: fp8 copies already serve every batch size."""
+        if batched and weight_dtype != "mxfp4":
+            raise ValueError(f"batched=True selects the batched route of MXFP4 copies; {weight_dtype!r} copies "
+                             + ("already serve every batch size" if weight_dtype == "fp8" else "have none"))
         if weight_dtype == "bf16":
             if self.weight_dtype != "bf16":
                 raise ValueError("a quantised model cannot return to bf16: the bf16 parameters already hold the rounded values")
@@ -452,6 +467,7 @@ class LMModel(StreamingContainer):
                 w.copy_(ops.dequantize_rows_fp8(q, scale))
                 _attach_copy(mod, name, "8", q, scale)
         self.weight_dtype = self.transformer.weight_dtype = weight_dtype
+        self.mxfp4_batched = self.transformer.mxfp4_batched = self.mxfp4_batched or bool(batched)
         return self
 
     # ---- token-id conventions (models/model.py:226-277)
@@ -569,15 +585,16 @@ class LMModel(StreamingContainer):
 
     @classmethod
     def from_state_dict(cls, sd: Dict[str, torch.Tensor], cfg: dict, kv_dtype: torch.dtype = torch.bfloat16,
-                        weight_dtype: str = "bf16") -> "LMModel":
+                        weight_dtype: str = "bf16", batched: bool = False) -> "LMModel":
         """Model for ``cfg`` (keys of ``rstnet_amd.synth.LM_*``) with weights taken from ``sd`` WITHOUT copying them
         (a 7.7 B-parameter state dict stays a single 15 GB allocation).  ``kv_dtype``: precision of the temporal KV rings.
-        ``weight_dtype="fp8"`` / ``"mxfp4"``: ``quantize_weights_`` on the loaded model (it rewrites the covered tensors of ``sd`` in place)."""
+        ``weight_dtype="fp8"`` / ``"mxfp4"``: ``quantize_weights_`` on the loaded model (it rewrites the covered tensors of ``sd`` in place);
+        ``batched``: its keyword (``"mxfp4"`` only: the MXFP4 copies also serve the routes above two rows)."""
         model = cls(kv_dtype=kv_dtype, causal=True, layer_scale=None, gating="silu", norm="rms_norm_f32", positional_embedding="rope",
                     depformer_causal=True, depformer_layer_scale=None, depformer_multi_linear=True, depformer_context=8,
                     depformer_gating="silu", depformer_pos_emb="none", depformer_weights_per_step=True, device="meta", **cfg)
         adopt_state_dict(model, sd)
-        return model.eval().quantize_weights_(weight_dtype)
+        return model.eval().quantize_weights_(weight_dtype, batched=batched)
 
 
 def prefill_token_plan(cache: torch.Tensor, offset: int, user: torch.Tensor, own: torch.Tensor, delays: List[int], initial: torch.Tensor):

@@ -111,7 +111,7 @@ class Geometry(NamedTuple):
 class LinearView(NamedTuple):
     w: torch.Tensor
     bias: Optional[torch.Tensor] = None
-    w8: Optional[tuple] = None        # stored fp8 / MXFP4 copy of ``w``: streamed by the batch <= 2 GEMV route; an fp8 pair also by the skinny GEMM above
+    w8: Optional[tuple] = None        # stored fp8 / MXFP4 copy of ``w``: streamed by the batch <= 2 GEMV route; an fp8 pair and an ``ops.Mxfp4BatchedCopy`` also by the skinny GEMM above
     lora: Optional[tuple] = None      # unmerged adapter ``(A, B, post_scale)`` in kernel form
 
 

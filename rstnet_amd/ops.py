@@ -906,6 +906,13 @@ class Mxfp4Copy(NamedTuple):
     scale: torch.Tensor
 
 
+class Mxfp4BatchedCopy(Mxfp4Copy):
+    """An ``Mxfp4Copy`` whose owner opted in to the batched route (``LMModel.quantize_weights_("mxfp4", batched=True)``): the same two
+    fields, and ``lm_linear`` / ``lm_gated_pair`` stream it above two rows too (``gemm_skinny_mxfp4w``) instead of reading the bf16
+    weight there."""
+    __slots__ = ()
+
+
 @_on_tensor_device
 def quantize_blocks_mxfp4(w: torch.Tensor) -> "Mxfp4Copy":
     """bf16 ``[N, K]``, ``K % 32 == 0`` -> (``q`` uint8 ``[N, K/2]``: OCP e2m1 codes, two per byte, even ``k`` in the low nibble;
@@ -1170,6 +1177,71 @@ def gemm_skinny_fp8w(x, q: torch.Tensor, scale: torch.Tensor, *, prologue: int =
     return PackedAct(gp, B, N // 2) if gate_out else out
 
 
+_skinny_weights_mxfp4w = _PackedWeights()
+_skinny_weights_mxfp4w_gated = _PackedWeights()
+
+
+def gemm_skinny_mxfp4w_supported(B: int, N: int, K: int) -> bool:
+    """Shapes ``gemm_skinny_mxfp4w`` serves (``1 <= B <= 64``, ``K % 32 == 0``, any ``N``); others take the bf16 weight."""
+    return bool(_lib.lib().rst_gemm_skinny_mxfp4w_supported(B, N, K))
+
+
+@_on_tensor_device
+def skinny_pack_weight_mxfp4w(q: torch.Tensor, scale: torch.Tensor, interleave_halves: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(q, scale)`` of ``quantize_blocks_mxfp4`` -> (``qp`` uint8 ``[ceil(N/32)*32, K/2]``: the code bytes in the MFMA order of
+    rst_skinny_pack_weight_mxfp4w, pad rows zero; ``sp`` uint8 ``[ceil(N/32), K/32, 32]``: the scale bytes per tile, block and row, pad
+    rows 127), cached per ``q`` storage (the row-major ``q`` stays: the batch <= 2 GEMV streams that one).  One copy serves every
+    batch size.  ``interleave_halves``: the layout of gated layers, as ``skinny_pack_weight``."""
+    _chk(q, "q", torch.uint8)
+    _chk(scale, "scale", torch.uint8)
+    N, K = q.shape[0], 2 * q.shape[1]
+    if K % 32:
+        raise ValueError(f"rstnet_amd.ops.skinny_pack_weight_mxfp4w: K = {K} is not a multiple of 32")
+    assert scale.shape == (N, K // 32), (tuple(q.shape), tuple(scale.shape))
+
+    def build():
+        t32 = (N + 31) // 32
+        qp = torch.empty(t32 * 32, K // 2, device=q.device, dtype=torch.uint8)
+        sp = torch.empty(t32, K // 32, 32, device=q.device, dtype=torch.uint8)
+        _lib.check(_lib.lib().rst_skinny_pack_weight_mxfp4w(_ptr(q), _ptr(scale), _ptr(qp), _ptr(sp), N, K, int(interleave_halves), _stream()))
+        return qp, sp
+    return (_skinny_weights_mxfp4w_gated if interleave_halves else _skinny_weights_mxfp4w).get(q, build, also=(scale,))
+
+
+@_on_tensor_device
+def gemm_skinny_mxfp4w(x, q: torch.Tensor, scale: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Optional[torch.Tensor] = None,
+                       eps: float = 1e-8, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, gate_out: bool = False):
+    """``gemm_skinny`` on MXFP4 weight storage: ``y[B,N] = (res +) (bias +) P(x) @ dequantize_blocks_mxfp4(q, scale).T`` for
+    1 <= B <= 64, ``q`` packed e2m1 codes ``[N,K/2]`` with one scale byte per 32 ``k`` (``quantize_blocks_mxfp4``).  ``x``: fp32 rows
+    (packed into bf16 hi / lo planes by one small launch, with the prologue) or a ``PackedAct``; the codes are decoded times their block
+    scale to the bf16 operand inside rst_gemm_skinny_mxfp4w_f32 (exact), so the values are those of ``gemm_skinny`` on the dequantised
+    matrix, bit for bit, from a quarter of the weight bytes.  ``gate_out``: as ``gemm_skinny`` (returns a ``PackedAct``)."""
+    _chk(res, "res")
+    _chk(bias, "bias")
+    N, K = q.shape[0], 2 * q.shape[1]
+    B = x.B if isinstance(x, PackedAct) else x.shape[0]
+    if not gemm_skinny_mxfp4w_supported(B, N, K):
+        raise ValueError(f"rstnet_amd.ops.gemm_skinny_mxfp4w: no MXFP4 weight-only skinny GEMM for B = {B}, N = {N}, K = {K} "
+                         "(1 <= B <= 64 and K % 32 == 0 required)")
+    gate_out = gate_out and N % 32 == 0 and res is None
+    qp, sp = skinny_pack_weight_mxfp4w(q, scale, interleave_halves=gate_out)
+    if isinstance(x, PackedAct):
+        assert prologue == PROLOGUE_NONE and x.K == K
+        xp = x = x.xp
+    else:
+        xp = skinny_pack_act(x, prologue=prologue, alpha=alpha, eps=eps)
+    assert xp.shape[2] == K, (tuple(x.shape), N, K, prologue)
+    out = None if gate_out else torch.empty(B, N, device=xp.device, dtype=torch.float32)
+    gp = _packed_buffer(xp.device, B, N // 2, "gate") if gate_out else None
+    with _profiled("gemm_skinny_mxfp4w", 2.0 * B * N * K, N * K // 2 + N * K // 32 + 4 * (x.numel() + B * N), (B, N, K)):
+        # the launch plan and its scratch are the bf16 route's (same shape key: launches on one stream are ordered)
+        sc = _split_scratch(xp.device, ("skinny_bf16", B, N, K), lambda: _lib.lib().rst_skinny_bf16_split_plan(B, N, K),
+                            (B + 31) // 32 * 32, N, lambda: (N + 31) // 32)
+        _lib.check(_lib.lib().rst_gemm_skinny_mxfp4w_f32(_ptr(xp), _ptr(qp), _ptr(sp), _ptr(res), _ptr(bias), _ptr(out), B, N, K, N, _ptr(gp),
+                                                        sc[0], _ptr(sc[1]), _ptr(sc[2]), _stream()))
+    return PackedAct(gp, B, N // 2) if gate_out else out
+
+
 _skinny_weights_fp8 = _PackedWeights()
 
 
@@ -1230,9 +1302,13 @@ def _gemv_stored(x: torch.Tensor, w: torch.Tensor, copy, **kw) -> torch.Tensor:
 
 def _skinny_stored(x, w: torch.Tensor, copy, **kw):
     """One skinny GEMM (<= 64 rows) on the cheapest stored form of ``w`` that serves it: a plain ``(q, scale)`` fp8 pair and
-    ``gemm_skinny_fp8w_supported``, else the bf16 ``w`` itself (an ``Mxfp4Copy`` has no batched form)."""
+    ``gemm_skinny_fp8w_supported``; an opted-in ``Mxfp4BatchedCopy`` and ``gemm_skinny_mxfp4w_supported``; else the bf16 ``w`` itself
+    (a plain ``Mxfp4Copy`` keeps the bf16 route above two rows: the batched MXFP4 route is opt-in)."""
     B, (N, K) = x.B if isinstance(x, PackedAct) else x.shape[0], w.shape
-    if copy is not None and not isinstance(copy, Mxfp4Copy) and gemm_skinny_fp8w_supported(B, N, K):
+    if isinstance(copy, Mxfp4BatchedCopy):
+        if gemm_skinny_mxfp4w_supported(B, N, K):
+            return gemm_skinny_mxfp4w(x, copy.q, copy.scale, **kw)
+    elif copy is not None and not isinstance(copy, Mxfp4Copy) and gemm_skinny_fp8w_supported(B, N, K):
         return gemm_skinny_fp8w(x, copy[0], copy[1], **kw)
     return gemm_skinny(x, w, **kw)
 
@@ -1247,7 +1323,7 @@ def lm_gated_pair(x: torch.Tensor, w_in: torch.Tensor, w_out: torch.Tensor, *, a
     ``w8_in`` / ``w8_out``: ``(q, scale)`` fp8 copies of the two weights (``quantize_rows_fp8``): the GEMV pair streams them, and so
     does the skinny pair above two rows (``gemm_skinny_fp8w``, the gate in the first epilogue as for bf16).
     Either may instead be an ``Mxfp4Copy`` (``quantize_blocks_mxfp4``): streamed by ``gemv_mxfp4w`` at batch <= 2 only; above, that
-    weight is read as bf16."""
+    weight is read as bf16 -- unless the copy is an ``Mxfp4BatchedCopy``, which the skinny pair streams too (``gemm_skinny_mxfp4w``)."""
     B = x.shape[0]
     if not fp8 and B <= 2 and B * max(w_out.shape[1], w_in.shape[1]) <= 32768 and w_in.shape[0] % 2 == 0:
         # GEMV pair: every wave of the first owns a (u, v) row pair and writes silu(u) * v; the second is a plain GEMV
@@ -1269,7 +1345,8 @@ def lm_linear(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE
     ``w8 = (q, scale)``: an fp8 copy of ``w`` holding the SAME values (``quantize_rows_fp8`` of a weight that was overwritten with its
     dequantised form): the GEMV route streams it instead of ``w``, and so does the skinny route (``gemm_skinny_fp8w``: K % 32 == 0,
     rows above 64 in chunks of 64); the ``fp8=True`` path and unsupported shapes read ``w``.  ``w8`` may instead be an ``Mxfp4Copy``
-    (``quantize_blocks_mxfp4``): the GEMV route then streams it with ``gemv_mxfp4w``, every other route reads ``w``."""
+    (``quantize_blocks_mxfp4``): the GEMV route then streams it with ``gemv_mxfp4w``, every other route reads ``w``; an
+    ``Mxfp4BatchedCopy`` is streamed by the skinny route as well (``gemm_skinny_mxfp4w``, same shapes and chunking as fp8)."""
     if isinstance(x, PackedAct):
         return _skinny_stored(x, w, w8, prologue=prologue, res=res, bias=bias)
     if fp8 and x.shape[0] <= 64 and w.shape[1] % 32 == 0 and w.shape[1] <= 16384:

@@ -47,8 +47,9 @@ class StreamingPipeline:
     def _frame_fn(self, pcm: torch.Tensor) -> torch.Tensor:
         """The three stages of a frame back to back on the device (the function the fused graph captures): no host-side slicing,
         cloning or re-staging of the codes / tokens between them.  (A quantised LM -- ``LMModel.quantize_weights_`` -- runs its fp8 routes
-        here as in ``LMGen.step``, the GEMV at one or two streams and the weight-only fp8 skinny GEMM above: the route is chosen inside
-        ``_frame`` from the model's ``weight_dtype``.)"""
+        here as in ``LMGen.step``, the GEMV at one or two streams and the weight-only fp8 skinny GEMM above; an MXFP4 model reads its
+        per-layer matrices as bf16 above two streams unless it opted in to the batched route (``mxfp4_batched``: the weight-only MXFP4
+        skinny GEMM): the route is chosen inside ``_frame`` from the model's ``weight_dtype`` and that flag.)"""
         B = self.batch_size
         codes = self.mimi.quantizer.encode_nlc(self.mimi.encode_latent(pcm))          # [B, K, 1]
         self.last_codes = codes         # (inside the graph: a static buffer every replay refills)

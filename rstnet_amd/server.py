@@ -246,7 +246,8 @@ def build_state(args, log_fn: Callable[[str, str], None] = log) -> ServerState:
         from .lm.loaders import load_lm_state_dict
         mimi = get_mimi(args.mimi_weight, device=device)
         sd = load_lm_state_dict(args.moshi_weight, device=device)
-    lm = LMModel.from_state_dict(sd, cfg, weight_dtype=getattr(args, "lm_weights", "bf16"))
+    lm = LMModel.from_state_dict(sd, cfg, weight_dtype=getattr(args, "lm_weights", "bf16"),
+                                 batched=getattr(args, "lm_mxfp4_batched", False))
     tok = None
     if args.tokenizer:
         import sentencepiece
@@ -271,7 +272,12 @@ def main(argv=None) -> None:
                    help="storage of the LM's streamed weights: fp8 = e4m3 weight-only copies (GEMV at one or two streams, fp8 skinny GEMM above), mxfp4 = OCP MXFP4 copies "
                         "of the temporal stack's per-layer matrices with the heads at fp8 (LMModel.quantize_weights_; speech quality "
                         "under fp8 or mxfp4 weights has not been evaluated)")
+    p.add_argument("--lm-mxfp4-batched", action="store_true",
+                   help="with --lm-weights mxfp4: stream the MXFP4 copies above two streams too (weight-only MXFP4 skinny GEMM) instead of "
+                        "reading those matrices as bf16 there; same values, a quarter of the bytes, no packed bf16 copies (opt-in)")
     args = p.parse_args(argv)
+    if args.lm_mxfp4_batched and args.lm_weights != "mxfp4":
+        p.error("--lm-mxfp4-batched needs --lm-weights mxfp4")
     if not args.synthetic and not (args.moshi_weight and args.mimi_weight):
         p.error("give --moshi-weight and --mimi-weight, or --synthetic")
     torch.manual_seed(42424242)

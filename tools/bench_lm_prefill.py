@@ -1,7 +1,7 @@
 """`LMGen.prefill` against replaying the same frames through `LMGen.step`, at the Moshi-7B shape, batch 1, one process.
 
     python tools/bench_lm_prefill.py [--samples 60] [--repeats 5] [--lengths 64,256,1024] [--lm-config moshi7b|tiny] [--out profiles/lm_prefill.json]
-                                     [--fp8]
+                                     [--fp8 | --mxfp4]
 
 Writes ONE JSON object (and prints it as one line):
 
@@ -14,7 +14,12 @@ Writes ONE JSON object (and prints it as one line):
   * ``--fp8``: ``prefill_fp8w[T]``, after everything above: the model is quantised (``quantize_weights_("fp8")``) and every length runs
     twice as (fp8, bf16) -- the bf16 legs by switching the ``weight_dtype`` mark on the same model, so both stream the same values;
     ``ratio_fp8_over_bf16`` compares the two medians of this process (the 64-row chunks run ``ops.gemm_skinny_fp8w`` against
-    ``ops.gemm_skinny``).
+    ``ops.gemm_skinny``);
+  * ``--mxfp4`` (instead of ``--fp8``: a model is quantised to one format): ``prefill_mxfp4w[T]``, after everything above: the model is
+    quantised (``quantize_weights_("mxfp4")``), its per-layer matrices also get fp8 copies of the rounded values (tools/bench_lm_mxfp4.py)
+    and every length runs twice as (mxfp4_batched, mxfp4, fp8, bf16) by switching the model's marks: ``mxfp4_batched`` streams the MXFP4
+    copies in the 64-row chunks (``ops.gemm_skinny_mxfp4w``), ``mxfp4`` reads those matrices as bf16 there (the route without the opt-in);
+    ratios of the first against each of the others.
 
 Exit status 1 when a 256-frame prefill is not under 1/8 of its baseline: the linears then stream the temporal weights 4 times instead of
 256 times and the depth phase is gone, so missing that means a route is wrong, not slow."""
@@ -97,7 +102,10 @@ def main():
     ap.add_argument("--lm-config", choices=["moshi7b", "tiny"], default="moshi7b")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lm_prefill.json"))
     ap.add_argument("--fp8", action="store_true", help="add the quantised legs (prefill_fp8w), fp8 / bf16 interleaved on the same model")
+    ap.add_argument("--mxfp4", action="store_true", help="add the MXFP4 legs (prefill_mxfp4w): batched route / bf16 batched route / fp8 / bf16 interleaved on one model")
     a = ap.parse_args()
+    if a.fp8 and a.mxfp4:
+        ap.error("--fp8 and --mxfp4 exclude each other: a model is quantised to one format")
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_lm_prefill.py measures on the GPU; none is visible")
     dev = torch.device("cuda:0")
@@ -138,6 +146,31 @@ def main():
             f8, b16 = statistics.median(ms["fp8"]), statistics.median(ms["bf16"])
             out["prefill_fp8w"][str(T)] = {"frames": T, "fp8_ms": round(f8, 4), "bf16_ms": round(b16, 4), "ratio_fp8_over_bf16": round(f8 / b16, 4),
                                            "fp8_legs_ms": ms["fp8"], "bf16_legs_ms": ms["bf16"]}
+    if a.mxfp4:
+        from rstnet_amd.lm.model import _attach_copy, _w8
+        model.quantize_weights_("mxfp4", batched=True)
+        with torch.no_grad():
+            for mod, name in model._layer_weights():          # fp8 copies next to the MXFP4 ones, for the fp8 legs only
+                if _w8(mod, name) is None:
+                    _attach_copy(mod, name, "8", *ops.quantize_rows_fp8(getattr(mod, name).detach()))
+
+        def mark(leg):
+            model.weight_dtype = model.transformer.weight_dtype = leg.split("_")[0]
+            model.mxfp4_batched = model.transformer.mxfp4_batched = leg == "mxfp4_batched"
+        order = ("mxfp4_batched", "mxfp4", "fp8", "bf16")
+        out["prefill_mxfp4w"] = {}
+        for T in [int(x) for x in a.lengths.split(",")]:
+            ms = {leg: [] for leg in order}
+            for _ in range(2):
+                for leg in order:
+                    mark(leg)
+                    bench._quiesce_host()
+                    ms[leg].append(prefill_leg(cfg, model, dev, T, a.repeats)["ms"])
+            mark("mxfp4_batched")
+            med = {leg: statistics.median(ms[leg]) for leg in order}
+            out["prefill_mxfp4w"][str(T)] = {"frames": T, **{leg + "_ms": round(med[leg], 4) for leg in order},
+                                             **{"ratio_mxfp4_batched_over_" + leg: round(med["mxfp4_batched"] / med[leg], 4) for leg in order[1:]},
+                                             **{leg + "_legs_ms": ms[leg] for leg in order}}
     gate = out["prefill"].get("256")
     if gate is not None:
         out["hard_condition"] = {"what": "prefill of 256 frames < 1/8 of 256 x step", "holds": bool(gate["ms"] < gate["baseline_ms"] / 8)}
