@@ -943,6 +943,284 @@ __global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2)
     }
 }
 
+// ---- window-sharing form of the three-plane kernel (convolutions of R = 2 / 3 taps) ---------------------------------------------
+// In the kernel above every tile row stages its own window, so with K = R * G (G = S * C floats per group, left padding (R - 1) * S
+// frames: every strided / k3 / transposed convolution of the codec) each input element of a tile is loaded, ELU'd, peeled into three
+// planes and written to LDS R times -- rows t and t + 1 share all but one group.  Here a tile stages 128 GROUPS once (b3_common.h:
+// slab row r = group t0 + r - (R - 1) of the utterance) and a stage multiplies the staged k-tile R times, the activation fragments
+// read at row offset + h for tap h against the weights of packed k-tile kt + h * (G / 16).  The staging pass is the one of the kernel
+// above -- the same 128 row slots, a_dst, b3_row permutation and RA -- so no wave stages more than before and its cost per matrix
+// instruction drops to 1 / R; one barrier serves 24 * R matrix instructions.  The price: the last R - 1 accumulator rows of a tile
+// have no complete window (their slab rows i + h fall on the cleared LDS rows 128 .. 128 + R - 2), are never stored, and the next
+// tile, placed 128 - (R - 1) rows on, computes them -- 1 / 128 or 2 / 128 of the matrix work.  Tiles do not cross utterances.
+// Weights: the stream of units (kt, h) goes through the same two register sets; unit u = R * kt + h sits in set u % 2 and each plane is
+// re-requested for unit u + 2 right after its last product.  Activations: always the masked form (every launch has padding groups in
+// front of each utterance), the range of a row being k-tiles 0 .. kn - 1 of its group.
+// Epilogue of a window-sharing tile whose columns all exist: every tile has dead rows (and the last tile of an utterance ends early), so
+// the rows are limited WITHOUT predicates -- the output (and the residual) are addressed through a buffer resource that starts at the
+// tile's first row and is `rows` rows long: a store past it is dropped by the address unit, a load past it returns 0.  (Routed through
+// the per-element-predicated form of gw_epilogue the compiler branches around every store, on half the waves of every tile.)
+// rw: first row of the wave inside the tile.
+template <int TM, int TN>
+__device__ __forceinline__ void gw_epilogue_rows(const GemmWinParams& p, const f32x16 (&acc)[TM][TN], long m0, int rows, int rw, int n0w, int lane) {
+    const bool has_res = p.res != nullptr;
+    const unsigned bytes = (unsigned)rows * (unsigned)p.ldy * 4u;
+    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y + m0 * p.ldy, 0, bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(has_res ? p.res + m0 * p.ldy : p.y), 0, has_res ? bytes : 0u, 0x00020000);
+    const unsigned row_bytes = (unsigned)p.ldy * 4u;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int n = n0w + j * 32 + (lane & 31);
+        const float bias = p.bias ? p.bias[n] : 0.0f;
+        const float scale = p.scale ? p.scale[n] : 1.0f;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const unsigned o = (unsigned)(rw + i * 32 + 4 * (lane >> 5)) * row_bytes + (unsigned)n * 4u;
+            float r[16];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const unsigned dm = (e & 3) + 8 * (e >> 2);
+                r[e] = has_res ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_r, o + dm * row_bytes, 0, 0)) : 0.0f;
+            }
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const unsigned dm = (e & 3) + 8 * (e >> 2);
+                float v = acc[i][j][e] + bias;
+                if (p.act_out == 1) v = rst_gelu(v);
+                if (has_res) v = r[e] + scale * v;
+                if (p.act_out == 2) v = rst_elu(v);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs_y, o + dm * row_bytes, 0, 0);
+            }
+        }
+    }
+}
+
+template <bool ELU, int NWN, int R>
+__global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_win_b3_stream_shared_kernel(const GemmWinParams p, const int tiles) {
+    constexpr int TM = 2, TN = 2;
+    constexpr int NT = 128 * NWN;
+    constexpr int BN = 64 * NWN;
+    constexpr int RA = 512 / NT;
+    constexpr int A_PLANE = (B3_SH_ROWS + R - 1) * B3_RS;        // shorts per plane in LDS: the slab rows + the cleared ones
+    constexpr int BUF = 3 * A_PLANE;
+    constexpr int NSA = B3_SETS_A;
+    static_assert(NSA == 4 && B3_SETS_B == 2, "the rotation below is written out for four activation sets and two weight sets");
+    static_assert(R == 2 || R == 3, "two or three taps");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    short* const lds = reinterpret_cast<short*>(smem);
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int wm = wave / NWN, wn = wave % NWN;
+    const int lrow = b3_row(tid >> 2);
+    const int lk = (tid & 3) * 4;
+    const int frag_row = lane & 31;
+    const int frag_k = (lane >> 5) * 8;
+
+    const int G = p.S * p.C;
+    const int TC = p.T_in * p.C;
+    const int tiles_n = (p.N + BN - 1) / BN;
+    const int nkg = G / B3_KB;                     // k-tiles of a group: a multiple of 4 (G % 64 == 0, checked by the launcher)
+    const int nk = R * nkg;                        // k-tiles of the packed weights (= K / 16)
+
+    const int xcd = blockIdx.x & 7;
+    const int first = gw_xcd_first(tiles, xcd);
+    const int count = gw_xcd_first(tiles, xcd + 1) - first;
+    const int stride = ((int)gridDim.x + 7 - xcd) >> 3;
+    int l = blockIdx.x >> 3;
+    if (l >= count) return;
+
+    struct Ctx {
+        B3SharedRow row[RA];         // this thread's slab rows: byte offset of the group from p.x, k-tiles inside the utterance
+    };
+    auto setup = [&](const int tile, Ctx& c) {
+        const B3SharedTile ti = b3_shared_tile(tile / tiles_n, R, p.T_out);
+#pragma unroll
+        for (int j = 0; j < RA; ++j) c.row[j] = b3_shared_row(ti, lrow + (NT / 4) * j, R, G, TC, p.x_bstride, lk);
+    };
+    auto w_tile = [&](int n0) { return (unsigned)(n0 / 32) * (unsigned)nk * 3072u; };      // bytes, uniform
+    const unsigned wo = (unsigned)(wn * TN) * (unsigned)nk * 3072u + (unsigned)lane * 16u;
+    const unsigned wo_blk = (unsigned)nk * 3072u;
+
+    f32x4 ra[NSA][RA];
+    int rm[NSA][RA];
+    u32x4 rw[2][TN][3];
+    const int a_dst = lrow * B3_RS + lk;
+    const int a_frag = (wm * TM * 32 + frag_row) * B3_RS + frag_k;
+
+    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, 0xffffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<short*>(p.w3), 0, 0xffffffff, 0x00020000);
+    // k-tile kt of the thread's slab rows; a k-tile outside a row's range is loaded from k-tile 0 of the same row (parked rows: from the
+    // first bytes of x) and cleared when it is consumed
+    auto load_a = [&](const Ctx& c, const int kt, f32x4 (&dst)[RA], int (&mask)[RA]) {
+#pragma unroll
+        for (int j = 0; j < RA; ++j) {
+            bool ok;
+            const unsigned vo = b3_shared_load_offset(c.row[j], kt, ok);
+            mask[j] = ok ? -1 : 0;
+            dst[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, vo, 0, 0));
+        }
+    };
+    // plane q of the wave's TN column blocks of packed k-tile pk (relative to the tile's base wb) into set u
+    auto load_wq = [&](const int u, const int q, const unsigned wb, const int pk) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const unsigned so = wb + (unsigned)pk * 3072u + q * 1024u;
+            rw[u][j][q] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, wo + j * wo_blk, so, 0);
+        }
+    };
+    auto take_a = [&](const f32x4 src, const int mask, f32x2 (&v)[2]) {
+        typedef int i32x4 __attribute__((ext_vector_type(4)));
+        f32x4 x = __builtin_bit_cast(f32x4, __builtin_bit_cast(i32x4, src) & mask);
+        if (ELU) {
+            x[0] = rst_elu(x[0]); x[1] = rst_elu(x[1]); x[2] = rst_elu(x[2]); x[3] = rst_elu(x[3]);
+        }
+        v[0] = f32x2{x[0], x[1]};
+        v[1] = f32x2{x[2], x[3]};
+    };
+
+    f32x16 acc[TM][TN];
+    auto clear = [&]() {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+    };
+
+    // one stage: group k-tile kt of LDS buffer `buf` into the accumulators, once per tap; register set S -- the k-tile after it -- into
+    // buffer buf ^ 1; the activation request four k-tiles ahead (context c, k-tile kta) into the set just freed; the weight units two
+    // ahead (this tile's base bp, or the next tile's bpn once the unit stream has crossed) into the planes as they are released
+    auto stage = [&](auto SS, const Ctx& c, const int kta, const unsigned bp, const unsigned bpn, const int kt, const int buf) {
+        constexpr int S = decltype(SS)::value;
+        constexpr int F = (S + 3) % 4;
+        load_a(c, kta, ra[F], rm[F]);
+        bf16x8 fa[TM][3];
+        const short* rd = lds + buf * BUF + a_frag;
+        short* wr = lds + (buf ^ 1) * BUF + a_dst;
+        // products of a tap: the three of weight plane 0 first, then plane 2, then plane 1 (as in the kernel above)
+        constexpr int QA[6] = {2, 1, 0, 0, 1, 0};
+        constexpr int QB[6] = {0, 0, 0, 2, 1, 1};
+#pragma unroll
+        for (int q = 2; q >= 0; --q)
+#pragma unroll
+            for (int i = 0; i < TM; ++i) fa[i][q] = *reinterpret_cast<const bf16x8*>(rd + q * A_PLANE + i * 32 * B3_RS);
+        __builtin_amdgcn_sched_barrier(0);
+
+        f32x2 v[RA][2];
+        u32x2 hh[RA];
+        // side work -- per plane 2 * RA half-row peels (4 VALU each) and the plane's LDS write -- one piece every SP-th slot: the
+        // amount of the kernel above, spread over R times the matrix instructions
+        constexpr int PB = 2 * RA + 1, NOPS = 3 * PB, SP = R * (RA == 2 ? 1 : 2);
+#pragma unroll
+        for (int mm = 0; mm < 24 * R; ++mm) {
+            const int h = mm / 24, m = mm % 24;
+            const int t = m >> 2, i = (m >> 1) & 1, j = m & 1;
+            const int u = (R * S + h) & 1;           // unit R * kt + h (kt = S mod 4)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][QA[t]], __builtin_bit_cast(bf16x8, rw[u][j][QB[t]]), acc[i][j], 0, 0, 0);
+            if (m == 11 || m == 15 || m == 23) {
+                // a weight plane's last product of this unit has issued: its registers take the plane of unit + 2 (same set)
+                const int h2 = (h + 2) % R, dk = (h + 2) / R;
+                const bool over = dk != 0 && kt + dk == nkg;
+                load_wq(u, m == 11 ? 0 : (m == 15 ? 2 : 1), over ? bpn : bp, (over ? 0 : kt + dk) + h2 * nkg);
+            }
+            if (h + 1 < R && (m == 3 || m == 19 || m == 23)) {
+                // an activation plane's last product of this tap has issued: its registers take the fragments of the next tap, one row on
+                const int q = m == 3 ? 2 : (m == 19 ? 1 : 0);
+#pragma unroll
+                for (int ii = 0; ii < TM; ++ii) fa[ii][q] = *reinterpret_cast<const bf16x8*>(rd + (h + 1) * B3_RS + q * A_PLANE + ii * 32 * B3_RS);
+            }
+            if (mm == 0) {
+#pragma unroll
+                for (int r = 0; r < RA; ++r) take_a(ra[S][r], rm[S][r], v[r]);
+            }
+            const int op = (mm >= 1 && (mm - 1) % SP == 0) ? (mm - 1) / SP : -1;
+            if (op >= 0 && op < NOPS) {
+                const int q = op / PB, w = op % PB;
+                if (w < 2 * RA) {
+                    hh[w >> 1][w & 1] = b3_peel(v[w >> 1][w & 1]);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < RA; ++r) *reinterpret_cast<u32x2*>(wr + q * A_PLANE + r * (NT / 4) * B3_RS) = hh[r];
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();
+    };
+
+    // the rows behind the slab (read by taps 1 .. R - 1 of the last accumulator rows, which are never stored) are cleared once
+    if (tid < 2 * 3 * (R - 1) * 3) {
+        const int piece = tid % 3, row = tid / 3;                   // 16-byte pieces of the 48-byte rows
+        const int b = row / (3 * (R - 1)), q = (row / (R - 1)) % 3, e = row % (R - 1);
+        *reinterpret_cast<u32x4*>(lds + b * BUF + q * A_PLANE + (B3_SH_ROWS + e) * B3_RS + piece * 8) = u32x4{0u, 0u, 0u, 0u};
+    }
+
+    Ctx c;
+    int tile = first + l;
+    int n0 = (tile % tiles_n) * BN;
+    setup(tile, c);
+    unsigned bp = w_tile(n0);
+    unsigned bpn = bp;               // weights of the tile the activation cursor has already moved on to
+    // start of the run: k-tile 0 of the first tile to LDS, activations of k-tiles 1 .. 3 to sets 0 .. 2, weight units 0 and 1 to sets 0 and 1
+    {
+        f32x4 xa[RA];
+        int xm[RA];
+        load_a(c, 0, xa, xm);
+#pragma unroll
+        for (int j = 0; j < RA; ++j) {
+            f32x2 v[2];
+            take_a(xa[j], xm[j], v);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                u32x2 hh;
+                hh[0] = b3_peel(v[0]);
+                hh[1] = b3_peel(v[1]);
+                *reinterpret_cast<u32x2*>(lds + a_dst + q * A_PLANE + j * (NT / 4) * B3_RS) = hh;
+            }
+        }
+        load_wq(0, 0, bp, 0); load_wq(0, 2, bp, 0); load_wq(0, 1, bp, 0);
+        load_wq(1, 0, bp, nkg); load_wq(1, 2, bp, nkg); load_wq(1, 1, bp, nkg);
+#pragma unroll
+        for (int g = 1; g < 4; ++g) load_a(c, g, ra[g - 1], rm[g - 1]);
+        __syncthreads();
+    }
+    for (;;) {
+        const int ln = l + stride;
+        const bool has_next = ln < count;
+        const int tile_n = first + ln;
+        const B3SharedTile ti = b3_shared_tile(tile / tiles_n, R, p.T_out);
+        clear();
+        // the activation request cursor crosses into the next tile four k-tiles before the end (at the end of the run: harmless re-loads
+        // of this tile's first k-tiles), the weight unit stream on the last stage
+        int kf = 4;
+        for (int kt = 0; kt < nkg; kt += 4) {
+            if (kf == nkg) {
+                kf = 0;
+                if (has_next) {
+                    setup(tile_n, c);
+                    bpn = w_tile((tile_n % tiles_n) * BN);
+                }
+            }
+            stage(b3_int<0>{}, c, kf, bp, bpn, kt, 0);
+            stage(b3_int<1>{}, c, kf + 1, bp, bpn, kt + 1, 1);
+            stage(b3_int<2>{}, c, kf + 2, bp, bpn, kt + 2, 0);
+            stage(b3_int<3>{}, c, kf + 3, bp, bpn, kt + 3, 1);
+            kf += 4;
+        }
+        bp = bpn;
+        // rows [m0, mlim) of the tile are stored (a ragged last column tile: the per-element predicates of the general epilogue)
+        if (n0 + BN <= p.N) gw_epilogue_rows<TM, TN>(p, acc, ti.m0, (int)(ti.mlim - ti.m0), wm * TM * 32, n0 + wn * TN * 32, lane);
+        else gw_epilogue<TM, TN, false>(p, acc, (int)ti.m0 + wm * TM * 32, n0 + wn * TN * 32, (int)ti.mlim, lane);
+        if (!has_next) break;
+        l = ln;
+        tile = tile_n;
+        n0 = (tile % tiles_n) * BN;
+    }
+}
+
 // w fp32 [N][K] -> the three bf16 planes in staging order (rows past N: zeros); one thread per four k of one row
 // DIRW: operand order [32-row block][k-tile][plane][64 lanes][8] instead -- lane (n % 32) + 32 * (k % 16 / 8) of the block holds k % 8 ..
 template <bool DIRW>
@@ -1044,6 +1322,33 @@ int launch_stream(const GemmWinParams& p, long tiles, hipStream_t stream) {
     return rst_check_launch("gemm_win");
 }
 
+// Taps of the window-sharing form, or 0 when the launch is not one of its convolutions: K = R groups of S * C floats with R = 2 / 3, the
+// causal left padding (R - 1) * S that conv1d and conv_transpose1d pass, and groups that are whole rotations of the four activation
+// sets (every tile starts on set 0).  Everything else rst_gemm_win_b3_shape_ok has already checked.
+static int b3_shared_taps(const GemmWinParams& p) {
+    const long G = (long)p.S * p.C;
+    if (G % 64 != 0 || p.K % G != 0) return 0;
+    const long R = p.K / G;
+    if ((R != 2 && R != 3) || p.P != (R - 1) * p.S) return 0;
+    return (int)R;
+}
+
+template <int NWN, int R>
+int launch_shared_b3_cfg(const GemmWinParams& p, hipStream_t stream) {
+    constexpr int BN = 64 * NWN;
+    const long tiles = (long)p.B * b3_shared_tiles_per_utt(p.T_out, R) * ((p.N + BN - 1) / BN);
+    if (tiles > 0x7fffffffL) {
+        rst_set_error("gemm_win: too many tiles (%ld)", tiles);
+        return RST_ERR_UNSUPPORTED;
+    }
+    const size_t lds = 2 * 3 * (B3_SH_ROWS + R - 1) * B3_RS * sizeof(short);      // 37 152 / 37 440 bytes
+    const long resident = (long)(NWN == 2 ? 2 : 1) * gw_cu_count();
+    const unsigned grid = (unsigned)(tiles < resident ? tiles : resident);
+    if (p.act_in == 1) hipLaunchKernelGGL((gemm_win_b3_stream_shared_kernel<true, NWN, R>), dim3(grid), dim3(128 * NWN), lds, stream, p, (int)tiles);
+    else hipLaunchKernelGGL((gemm_win_b3_stream_shared_kernel<false, NWN, R>), dim3(grid), dim3(128 * NWN), lds, stream, p, (int)tiles);
+    return rst_check_launch("gemm_win_b3");
+}
+
 template <int NWN>
 int launch_stream_b3_cfg(const GemmWinParams& p, hipStream_t stream) {
     constexpr int BN = 64 * NWN;
@@ -1102,6 +1407,13 @@ int launch_stream_b3_cfg(const GemmWinParams& p, hipStream_t stream) {
         return rst_check_launch("gemm_win_b3");
     }
 #endif
+    // convolutions of two / three taps: every staged group serves all taps of the tile (tools build: RST_B3_SHARE=0 keeps the form below)
+    static const int share = rst_knob("RST_B3_SHARE", 1);
+    if (share) {
+        const int taps = b3_shared_taps(p);
+        if (taps == 2) return launch_shared_b3_cfg<NWN, 2>(p, stream);
+        if (taps == 3) return launch_shared_b3_cfg<NWN, 3>(p, stream);
+    }
     if (p.act_in == 1) {
         if (lean) go(gemm_win_b3_stream_kernel<true, false, NWN, 0, true, true>);
         else go(gemm_win_b3_stream_kernel<true, true, NWN, 0, true, true>);
