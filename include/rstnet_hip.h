@@ -258,6 +258,30 @@ int rst_transpose_f32(const float* x, float* y, int B, int R, int C, rst_stream_
  * (modules/resample.py:14-65) -- so the rows past an utterance's length must hold exactly that when a strided layer reads them. */
 int rst_mask_tail_f32(float* x, const int32_t* lengths, int B, int T, int C, int mode, rst_stream_t stream);
 
+/* Polyphase sinc sample-rate conversion of a ragged batch in one launch (torchaudio.transforms.Resample at mimi_tokenizer.py:66-67;
+ * the same entry converts one frame of a live stream over a history + chunk buffer with lead = 0).  The rates are orig : new = o : n
+ * in lowest terms; filt is the table of codec/audio_resample.py: sinc_kernel(o, n) stored TAP-MAJOR, filt[k][p] for tap k < L and
+ * output phase p < n (L = 2 * width + o), so that consecutive outputs read consecutive floats.  x is [B] rows of T_in samples,
+ * x_row_stride elements apart, fp32 (x_dtype 0) or int16 (x_dtype 1: a sample is (float)v * 2^-15, exact); y is [B] rows of T_out
+ * floats, y_row_stride apart.  For row b and 0 <= i < T_out, with p = i mod n and j = i div n:
+ *     y[b][i] = sum over k = 0 .. L-1, IN THIS ORDER, of filt[k][p] * X_b[j * o + k - lead]      for i <  out_lengths[b]
+ *     y[b][i] = 0                                                                              for i >= out_lengths[b]
+ *     X_b[t]  = x[b][t] for 0 <= t < min(in_lengths[b], T_in), else 0
+ * in_lengths NULL = T_in for every row, out_lengths NULL = T_out (both are clamped to [0, T_in] / [0, T_out]: no length read from
+ * the device can move an access out of a row).  The kernel writes the zero tail itself: y needs no fill.
+ * ARITHMETIC: one fp32 accumulator per output, started at 0 and updated by one fused multiply-add per tap in the order above --
+ * always FMA, never re-associated.  An output's bits therefore do not depend on the tile, row, batch or chunk it is computed in, nor
+ * on whether its inputs were staged in LDS: a stream converted frame by frame equals the whole-signal conversion bit for bit.
+ * filt may be NULL at o = n = L = 1 only: y = X (the s16 -> f32 conversion and the zero tail alone).
+ * < 0 (rst_last_error): o, n or L < 1, lead < 0, a negative size, a row stride below its row, a null pointer, an index past 2^31. */
+int rst_resample_sinc(const void* x, int x_dtype, int64_t x_row_stride, int T_in, const int32_t* in_lengths, const float* filt, int o,
+                      int n, int L, int lead, float* y, int64_t y_row_stride, const int32_t* out_lengths, int B, int T_out,
+                      rst_stream_t stream);
+
+/* -> outputs per workgroup of rst_resample_sinc (a tile: consecutive outputs of one row); *slab_bytes (optional) receives the LDS
+ * bytes a tile of these rates stages its inputs in, or 0 when the span is too long and the kernel reads them from global memory. */
+int rst_resample_plan(int o, int n, int L, int* slab_bytes);
+
 /* Streaming history roll: hist_out [P_out steps] = last P_out steps of concat(hist_in [P_in steps], x [T_in steps])
  * (the `previous` buffer of RawStreamingConv1d, modules/streaming.py:224-236; conv-transpose keeps its input history the
  * same way instead of the reference's `partial` output buffer).  hist_out == hist_in (in-place roll, what a graph-replayed

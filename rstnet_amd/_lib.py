@@ -59,6 +59,8 @@ SIGNATURES = {
     "rst_gemm_skinny_f32": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p],
     "rst_linear_few_rows_f32": [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p],
     "rst_mask_tail_f32": [_p, _p, _i, _i, _i, _i, _p],
+    "rst_resample_sinc": [_p, _i, _l, _i, _p, _p, _i, _i, _i, _i, _p, _l, _p, _i, _i, _p],
+    "rst_resample_plan": [_i, _i, _i, C.POINTER(_i)],
     "rst_codec_transformer_workspace_bytes": [_i, _i, _i],
     "rst_codec_transformer_supported": [_i, _i, _i, _i, _i, _i, _i],
     "rst_codec_transformer_frame": [C.POINTER(_p)] * 12 + [_p, _p, _p, _p, _p] + [_i] * 9 + [_f, _f, _p],

@@ -15,7 +15,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from .audio_resample import resample
+from .audio_resample import reduce_rates, resample, resample_device
 from .mimi import MimiCodec
 
 FRAME_HOP = 1920
@@ -65,9 +65,16 @@ class MimiTokenizer:
 
     # ---- batched offline tokenization
     @torch.no_grad()
-    def tokenize_batch(self, wavs: Sequence[torch.Tensor], sample_rate: int = 24000, max_batch_seconds: float = 1920.0) -> List[torch.Tensor]:
+    def tokenize_batch(self, wavs: Sequence[torch.Tensor], sample_rate: int = 24000, max_batch_seconds: float = 1920.0,
+                       resample: str = "host") -> List[torch.Tensor]:
         """Mono waveforms (1-D ``[T_i]`` or ``[1, T_i]``) -> list of int16 codes ``[8, ceil(T_i/1920)]`` in input order.  Utterances are
-        sorted by length and packed into zero-padded batches of at most ``max_batch_seconds`` of padded audio."""
+        sorted by length and packed into zero-padded batches of at most ``max_batch_seconds`` of padded audio.
+        ``resample="device"`` (opt-in): the rows -- fp32, or int16 PCM as a 16-bit file holds it -- are packed and uploaded at
+        ``sample_rate`` and converted to 24 kHz there in one launch per batch (``audio_resample.resample_device``)."""
+        if resample == "device":
+            return self._tokenize_batch_device(wavs, int(sample_rate), max_batch_seconds)
+        if resample != "host":
+            raise ValueError(f"resample must be 'host' or 'device', got {resample!r}")
         flat = [self._to_codec_rate(w.reshape(-1).float(), sample_rate) for w in wavs]
         order = sorted(range(len(flat)), key=lambda i: flat[i].numel())
         out: List[Optional[torch.Tensor]] = [None] * len(flat)
@@ -85,6 +92,38 @@ class MimiTokenizer:
             codes = self.model.encode(batch.to(self.device), lengths=lens).cpu()
             for r, idx in enumerate(order[i:j]):
                 frames = -(-flat[idx].numel() // FRAME_HOP)
+                out[idx] = codes[r, :, :frames].to(torch.int16).contiguous()
+            i = j
+        return out  # type: ignore[return-value]
+
+    def _tokenize_batch_device(self, wavs: Sequence[torch.Tensor], sample_rate: int, max_batch_seconds: float) -> List[torch.Tensor]:
+        """``tokenize_batch`` with the rate conversion (and the int16 -> fp32 conversion) on the device: same sorting and packing,
+        the batch budget counted in 24 kHz samples; what crosses the bus is the padded raw batch and its lengths."""
+        o, n = reduce_rates(sample_rate, self.sr)
+        flat = [w.reshape(-1) for w in wavs]
+        dtypes = {w.dtype for w in flat}
+        if not dtypes <= {torch.int16} and not dtypes <= {torch.float32}:
+            raise TypeError(f"resample='device' takes rows that are all float32 or all int16, got {sorted(map(str, dtypes))}")
+        dtype = torch.int16 if dtypes == {torch.int16} else torch.float32
+        out_len = [-(-n * w.numel() // o) for w in flat]            # samples at 24 kHz
+        order = sorted(range(len(flat)), key=lambda i: flat[i].numel())
+        out: List[Optional[torch.Tensor]] = [None] * len(flat)
+        budget = int(max_batch_seconds * self.sr)
+        i = 0
+        while i < len(order):
+            j, longest = i, 0
+            while j < len(order) and max(longest, out_len[order[j]]) * (j - i + 1) <= max(budget, out_len[order[j]]):
+                longest = max(longest, out_len[order[j]])
+                j += 1
+            rows = order[i:j]
+            batch = torch.zeros(j - i, flat[rows[-1]].numel(), dtype=dtype)
+            for r, idx in enumerate(rows):
+                batch[r, :flat[idx].numel()] = flat[idx]
+            lens = torch.tensor([flat[idx].numel() for idx in rows], dtype=torch.int32)
+            wav24, lens24 = resample_device(batch.to(self.device), lens.to(self.device), sample_rate, self.sr)
+            codes = self.model.encode(wav24, lengths=lens24).cpu()
+            for r, idx in enumerate(rows):
+                frames = -(-out_len[idx] // FRAME_HOP)
                 out[idx] = codes[r, :, :frames].to(torch.int16).contiguous()
             i = j
         return out  # type: ignore[return-value]

@@ -24,7 +24,7 @@ int rst_check_launch(const char* what) {
 
 extern "C" {
 
-int rst_version(void) { return 125; }      // 125: + rst_skinny_pack_weight_mxfp4w, rst_gemm_skinny_mxfp4w_f32 / _supported (MXFP4 weight-only skinny GEMM); 124: + rst_skinny_pack_weight_fp8w, rst_gemm_skinny_fp8w_f32 / _supported (fp8 weight-only skinny GEMM); 123: + rst_quant_blocks_mxfp4, rst_gemv_mxfp4w_f32 / _supported (MXFP4 weight-only GEMV); 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
+int rst_version(void) { return 126; }      // 126: + rst_resample_sinc, rst_resample_plan (sample-rate conversion of ragged batches and streams); 125: + rst_skinny_pack_weight_mxfp4w, rst_gemm_skinny_mxfp4w_f32 / _supported (MXFP4 weight-only skinny GEMM); 124: + rst_skinny_pack_weight_fp8w, rst_gemm_skinny_fp8w_f32 / _supported (fp8 weight-only skinny GEMM); 123: + rst_quant_blocks_mxfp4, rst_gemv_mxfp4w_f32 / _supported (MXFP4 weight-only GEMV); 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
                                            // rst_rvq_search_chain_f32, rst_embed_sum_bf16(add_stride); 105: round 4
 const char* rst_last_error(void) { return g_err; }
 
@@ -323,6 +323,19 @@ int rst_hist_update_batch_f32(const float* const* x, float* const* hist, const i
 
 int rst_mask_tail_f32(float* x, const int32_t* lengths, int B, int T, int C, int mode, rst_stream_t stream) {
     return rst_launch_mask_tail(x, lengths, B, T, C, mode, (hipStream_t)stream);
+}
+
+int rst_resample_sinc(const void* x, int x_dtype, int64_t x_row_stride, int T_in, const int32_t* in_lengths, const float* filt, int o,
+                      int n, int L, int lead, float* y, int64_t y_row_stride, const int32_t* out_lengths, int B, int T_out,
+                      rst_stream_t stream) {
+    return rst_launch_resample_sinc(x, x_dtype, (long)x_row_stride, T_in, in_lengths, filt, o, n, L, lead, y, (long)y_row_stride,
+                                    out_lengths, B, T_out, (hipStream_t)stream);
+}
+
+int rst_resample_plan(int o, int n, int L, int* slab_bytes) {
+    RST_REQUIRE(o >= 1 && n >= 1 && L >= 1, "resample_plan: o, n, L >= 1 required (o=%d n=%d L=%d)", o, n, L);
+    if (slab_bytes) *slab_bytes = rst_resample_slab_bytes(o, n, L);
+    return RST_RESAMPLE_TILE;
 }
 
 int rst_hist_update_f32(const float* x, const float* hist_in, float* hist_out, int B, int T_in, int P_in, int P_out,

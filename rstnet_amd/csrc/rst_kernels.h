@@ -138,6 +138,14 @@ int rst_launch_hist_update_batch(const HistBatchParams& p, hipStream_t stream);
 int rst_launch_act(const float* x, float* y, long n, int act, hipStream_t stream);  // 1: ELU, 2: GELU
 int rst_launch_mask_tail(float* x, const int* lengths, int B, int T, int C, int mode, hipStream_t stream);
 
+// ---- resample.hip -----------------------------------------------------------------------------
+#define RST_RESAMPLE_TILE 256     // outputs per workgroup
+// polyphase sinc conversion of a ragged batch, contract at rst_resample_sinc (include/rstnet_hip.h); x_dtype 0 = f32, 1 = s16
+int rst_launch_resample_sinc(const void* x, int x_dtype, long x_row_stride, int T_in, const int* in_lengths, const float* filt, int o,
+                             int n, int L, int lead, float* y, long y_row_stride, const int* out_lengths, int B, int T_out,
+                             hipStream_t stream);
+int rst_resample_slab_bytes(int o, int n, int L);   // LDS bytes a tile stages its inputs in; 0 = read from global (span too long)
+
 // ---- attention.hip ----------------------------------------------------------------------------
 struct RopeSplitParams {
     const float* qkv;   // [B][T][3][H][D]

@@ -756,6 +756,61 @@ def mask_tail(x: torch.Tensor, lengths: torch.Tensor, replicate: bool = False) -
     return x
 
 
+RESAMPLE_TILE = 256     # outputs per workgroup of rst_resample_sinc (checked against the library on the first call)
+
+
+def resample_staged(o: int, n: int, L: int) -> bool:
+    """Whether a tile of these rates stages its inputs in LDS (False: the span is too long, the kernel reads them from global)."""
+    slab = C.c_int(0)
+    tile = _lib.lib().rst_resample_plan(o, n, L, C.byref(slab))
+    assert tile == RESAMPLE_TILE, (tile, RESAMPLE_TILE)
+    return slab.value > 0
+
+
+@_on_tensor_device
+def resample_sinc(x: torch.Tensor, in_lengths: Optional[torch.Tensor], filt: Optional[torch.Tensor], o: int, n: int, lead: int,
+                  T_out: int, out_lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Polyphase sinc rate conversion ``o : n`` of the rows of ``x [B, T_in]`` (fp32 or int16, any row stride, unit sample stride) in
+    one launch -> ``y [B, T_out]`` fp32: ``y[b, i] = sum_k filt[k, i % n] * X_b[(i // n) * o + k - lead]`` for ``i < out_lengths[b]``,
+    exactly 0 behind it; ``X_b`` is row ``b`` inside ``in_lengths[b]`` and zero outside (``None``: the whole row / every output).
+    ``filt [L, n]`` is the TAP-MAJOR table (``audio_resample.device_table``); ``None`` at ``o == n == 1`` converts s16 -> f32 only.
+    One fp32 FMA chain per output in tap order: the bits of an output do not depend on where in a batch, tile or chunk it falls
+    (contract: ``rst_resample_sinc``, include/rstnet_hip.h).  Refusals raise ``RstError`` with the library's message."""
+    if x.dtype not in (torch.float32, torch.int16):
+        raise TypeError(f"rstnet_amd.ops: `x` must be float32 or int16, got {x.dtype}")
+    _chk(x, "x", x.dtype, contiguous=False)
+    _chk(in_lengths, "in_lengths", torch.int32)
+    _chk(out_lengths, "out_lengths", torch.int32)
+    _chk(filt, "filt")
+    if x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        raise ValueError("rstnet_amd.ops: `x` must be [B, T_in] rows of unit sample stride")
+    B, T_in = x.shape
+    for t, name in ((in_lengths, "in_lengths"), (out_lengths, "out_lengths"), (filt, "filt"), (out, "out")):
+        if t is not None and t.device != x.device:
+            raise ValueError(f"rstnet_amd.ops: `{name}` is on {t.device}, `x` on {x.device}")
+    for t, name in ((in_lengths, "in_lengths"), (out_lengths, "out_lengths")):
+        if t is not None and tuple(t.shape) != (B,):
+            raise ValueError(f"rstnet_amd.ops: `{name}` must be [{B}]")
+    if filt is not None and (filt.dim() != 2 or filt.shape[1] != n):
+        raise ValueError(f"rstnet_amd.ops: `filt` must be the tap-major table [L, n = {n}], got {tuple(filt.shape)}")
+    L = filt.shape[0] if filt is not None else 1
+    T_out = int(T_out)
+    if out is None:
+        out = torch.empty(B, max(T_out, 0), device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, "out", contiguous=False)
+        if out.dim() != 2 or tuple(out.shape) != (B, T_out) or (T_out > 1 and out.stride(1) != 1) or (B > 1 and out.stride(0) < T_out):
+            raise ValueError(f"rstnet_amd.ops: `out` must be [{B}, {T_out}] rows of unit sample stride")
+    x_stride = x.stride(0) if B > 1 else T_in
+    y_stride = out.stride(0) if B > 1 else max(T_out, 0)
+    with _profiled("resample_sinc", 2.0 * B * max(T_out, 0) * L, x.element_size() * B * T_in + 4 * B * max(T_out, 0), (B, T_in, T_out, o, n, L)):
+        rc = _lib.lib().rst_resample_sinc(_ptr(x), int(x.dtype == torch.int16), x_stride, T_in, _ptr(in_lengths), _ptr(filt), int(o), int(n), L,
+                                          int(lead), _ptr(out), y_stride, _ptr(out_lengths), B, T_out, _stream())
+    if rc != 0:
+        raise _lib.RstError(f"librstnet_hip error {rc}: {_lib.lib().rst_last_error().decode('utf-8', 'replace')}")
+    return out
+
+
 _hist_pending: Optional[list] = None      # deferred in-place rolls of the enclosing `hist_batch()` block
 HIST_BATCH_MAX = 32
 

@@ -11,16 +11,25 @@ from typing import Optional
 
 import torch
 
+from .codec.audio_resample import StreamResampler, stream_pair_geometry
 from .codec.mimi import MimiCodec
 from .graphs import Graphed, RecaptureGate
 from .lm.model import LMGen
 
+CODEC_RATE = 24000
+
 
 class StreamingPipeline:
-    def __init__(self, mimi: MimiCodec, lm_gen: LMGen, batch_size: int):
+    def __init__(self, mimi: MimiCodec, lm_gen: LMGen, batch_size: int, client_rate: Optional[int] = None):
         assert mimi.quantizer.n_q >= lm_gen.lm_model.dep_q
         self.mimi, self.lm_gen, self.batch_size = mimi, lm_gen, batch_size
         self.frame_size = mimi.frame_hop
+        # a client at another sample rate: ``step`` takes and returns ``client_frame`` samples at ``client_rate``; the two conversions
+        # (codec/audio_resample.py: StreamResampler, created per session) are part of the frame.  ValueError here, before any streaming
+        # context is entered, for a rate the resamplers do not serve (stream_pair_geometry: no whole-sample frame, too low, too high)
+        self.client_rate = None if client_rate is None else int(client_rate)
+        self.client_frame = self.frame_size if client_rate is None else stream_pair_geometry(client_rate, CODEC_RATE, self.frame_size)
+        self._rs_in = self._rs_out = None
         self.n_user = lm_gen.lm_model.num_codebooks - lm_gen.lm_model.dep_q - 1
         self._dec = None
         from . import ops
@@ -36,10 +45,15 @@ class StreamingPipeline:
         self._lm_ctx.__enter__()
         self._fused, self.last_codes = None, None     # a graph of an earlier session points at that session's states
         self._gate = RecaptureGate(self.lm_gen.lm_model.device, every_frame=True)
+        if self.client_rate is not None:
+            dev = self.lm_gen.lm_model.device
+            self._rs_in = StreamResampler(self.client_rate, CODEC_RATE, self.frame_size, self.batch_size, dev)
+            self._rs_out = StreamResampler(CODEC_RATE, self.client_rate, self.client_frame, self.batch_size, dev)
         return self
 
     def __exit__(self, *exc):
         self._fused, self.last_codes = None, None        # (the captured frame keeps the session's state tensors alive)
+        self._rs_in = self._rs_out = None
         self._lm_ctx.__exit__(*exc)
         self._mimi_ctx.__exit__(*exc)
         return False
@@ -56,6 +70,10 @@ class StreamingPipeline:
         out, _ = self.lm_gen._frame(codes[:, :self.n_user, 0].contiguous())            # [B, 1 + dep_q]
         return self.mimi._decode(out[:, 1:].reshape(B, -1, 1))
 
+    def _frame_fn_rate(self, pcm: torch.Tensor) -> torch.Tensor:
+        """``_frame_fn`` between the session's two rate conversions: client rate -> 24 kHz -> client rate, still one graph."""
+        return self._rs_out.step(self._frame_fn(self._rs_in.step(pcm)))
+
     @torch.no_grad()
     def step(self, pcm: torch.Tensor) -> Optional[torch.Tensor]:
         """pcm fp32 ``[B, 1, 1920]`` -> generated pcm ``[B, 1, 1920]`` (or ``None`` during the first ``max_delay`` frames).
@@ -63,8 +81,10 @@ class StreamingPipeline:
         Once the delay line is full and every module has run its two eager frames (streaming buffers allocated, in-place from then
         on) a frame is ONE captured graph -- encode, LM frame,
         decode -- fed by one copy of the PCM and read by one clone of the result; before that, and on CPU tensors, under
-        ``NO_CUDA_GRAPH=1`` or with ``LMGen(check=True)``, the three module calls run as the reference's loop does (server.py:122-136)."""
-        assert pcm.shape == (self.batch_size, 1, self.frame_size), tuple(pcm.shape)
+        ``NO_CUDA_GRAPH=1`` or with ``LMGen(check=True)``, the three module calls run as the reference's loop does (server.py:122-136).
+        With a ``client_rate`` the frames are ``[B, 1, client_frame]`` at that rate in both directions."""
+        rated = self.client_rate is not None        # (client_frame == frame_size without a client rate)
+        assert pcm.shape == (self.batch_size, 1, self.client_frame), tuple(pcm.shape)
         gen = self.lm_gen
         state = gen._streaming_state
         fused_ok = (self.fuse and pcm.is_cuda and state is not None and state.offset >= gen.max_delay + 2 and not gen.check
@@ -74,14 +94,17 @@ class StreamingPipeline:
                 # the first capture follows the modules' own eager frames (the delay line: max_delay + 2 of them).  A RE-capture after the
                 # device's persistent launches were retired takes launch-per-op paths that have not run in this session yet: one eager
                 # frame first, so that their lazily created state and scratch exist before the capture
-                self._fused = Graphed(self._frame_fn, warmup=0 if self._fused is None else 1)
+                self._fused = Graphed(self._frame_fn_rate if rated else self._frame_fn, warmup=0 if self._fused is None else 1)
             if not self._fused.disable:
                 wav = self._fused(pcm.contiguous())
                 state.offset += 1
                 return wav.clone()
+        if rated:
+            pcm = self._rs_in.step(pcm)
         codes = self.mimi.encode(pcm)                                   # [B, 8, 1]
         self.last_codes = codes
         tokens = self.lm_gen.step(codes[:, :self.n_user].contiguous())  # [B, 1 + dep_q, 1] or None
         if tokens is None:
             return None
-        return self.mimi.decode(tokens[:, 1:].contiguous())
+        wav = self.mimi.decode(tokens[:, 1:].contiguous())
+        return self._rs_out.step(wav).clone() if rated else wav         # (no output, and no outgoing conversion, during the delay)

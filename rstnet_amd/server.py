@@ -10,7 +10,9 @@ What differs, and why: the reference moves audio as Opus pages through ``sphn`` 
 little-endian mono samples at the codec rate, ``f32`` (default) or ``s16`` (``/api/chat?pcm=s16``), in both directions.  The
 message kinds, the handshake, the framing and the locking are the reference's; a client only swaps its Opus codec for a
 memcpy.  ``/api/chat?pcm=opus`` selects ``OpusFramer`` -- the reference's ``sphn`` reader / writer at the same seam -- which needs the
-``sphn`` package and says so when it is missing.
+``sphn`` package and says so when it is missing.  ``/api/chat?sr=<rate>`` (default: the codec's rate) lets a raw-PCM client send and receive
+at its own sample rate -- a browser's 48 kHz, telephony's 8 or 16 kHz -- in frames of ``client_geometry`` samples: the two conversions run on the
+device (``codec/audio_resample.py``: ``StreamResampler``), which is what the Opus library does for the reference's clients.
 """
 from __future__ import annotations
 
@@ -99,6 +101,30 @@ def make_framer(frame_size: int, fmt: str, sample_rate: int):
     return OpusFramer(frame_size, sample_rate) if fmt == "opus" else PcmFramer(frame_size, fmt)
 
 
+def client_geometry(sr: Optional[str], codec_rate: int, frame_size: int):
+    """The ``?sr=`` parameter of ``/api/chat`` -> ``(client rate, samples per frame at that rate)``.  Absent or equal to the codec's
+    rate: ``(codec_rate, frame_size)``, the plain session.  ``ValueError`` -- answered with 400 before the upgrade -- for a value that is
+    not a positive integer, or a rate the stream resamplers do not serve (``audio_resample.stream_pair_geometry``: a codec frame that is
+    not a whole number of samples -- refused, not approximated --, a rate so low that the filter's history outgrows a frame, one above
+    16 x the codec's, or a ratio whose filter table is out of proportion).  Host arithmetic only: nothing is built or allocated."""
+    if sr is None or sr == "":
+        return int(codec_rate), int(frame_size)
+    try:
+        rate = int(sr)
+    except ValueError:
+        raise ValueError(f"unknown sample rate {sr!r}: ?sr= takes a positive integer (Hz)") from None
+    if rate <= 0:
+        raise ValueError(f"unknown sample rate {sr!r}: ?sr= takes a positive integer (Hz)")
+    if rate == int(codec_rate):
+        return rate, int(frame_size)
+    from .codec.audio_resample import stream_pair_geometry
+    try:
+        frame_in = stream_pair_geometry(rate, codec_rate, frame_size)
+    except ValueError as e:
+        raise ValueError(f"sample rate {rate} cannot be served: {e}") from None
+    return rate, frame_in
+
+
 class ServerState:
     """``ServerState`` of server.py:44-166 over ``rstnet_amd``'s ``MimiModel`` / ``LMGen`` (or anything with the same three
     calls -- the CPU test drives it with stand-ins)."""
@@ -108,6 +134,8 @@ class ServerState:
         self.mimi, self.text_tokenizer, self.device = mimi, text_tokenizer, device
         self.lm_gen = lm_gen if lm_gen is not None else LMGen(lm, **lm_gen_kwargs)
         self.frame_size = int(round(mimi.sample_rate / mimi.frame_rate)) if hasattr(mimi, "frame_rate") else mimi.frame_hop
+        self.codec_rate = int(getattr(mimi, "sample_rate", 24000))
+        self._session_pair = None        # (client rate, StreamResampler in, StreamResampler out) of the current session's rate: one at a time
         self.lock = asyncio.Lock()
         self.mimi.streaming_forever(1)
         self.lm_gen.streaming_forever(1)
@@ -123,10 +151,35 @@ class ServerState:
             self.frame(chunk)
         self._sync()
 
-    def frame(self, chunk: torch.Tensor):
+    def rate_pair(self, sr: Optional[int]):
+        """The two stream resamplers of a client at ``sr`` Hz (client -> codec, codec -> client), or ``None`` at the codec's own rate."""
+        if sr is None or int(sr) == self.codec_rate:
+            return None
+        if self._session_pair is None or self._session_pair[0] != int(sr):
+            from .codec.audio_resample import StreamResampler, stream_pair_geometry
+            client_frame = stream_pair_geometry(int(sr), self.codec_rate, self.frame_size)         # ValueError before anything is built
+            self._session_pair = None                                                                # (the last rate's buffers go first)
+            self._session_pair = (int(sr), StreamResampler(int(sr), self.codec_rate, self.frame_size, 1, self.device),
+                                  StreamResampler(self.codec_rate, int(sr), client_frame, 1, self.device))
+        return self._session_pair[1:]
+
+    def reset_session(self, sr: Optional[int] = None) -> None:
+        """States as a new session finds them (server.py:160-161), the client's two resamplers included."""
+        self.mimi.reset_streaming()
+        self.lm_gen.reset_streaming()
+        pair = self.rate_pair(sr)
+        if pair is not None:
+            pair[0].reset()
+            pair[1].reset()
+
+    def frame(self, chunk: torch.Tensor, sr: Optional[int] = None):
         """One 80 ms frame: pcm ``[1, 1, frame_size]`` -> list of (pcm float32 numpy ``[frame_size]``, text token id) -- empty while
-        ``LMGen.step`` still returns ``None`` (the first ``max_delay`` frames), server.py:126-136."""
+        ``LMGen.step`` still returns ``None`` (the first ``max_delay`` frames), server.py:126-136.  With ``sr`` (a client at another
+        rate) the frame comes in and goes out at that rate, ``client_geometry`` samples long."""
         out = []
+        pair = self.rate_pair(sr)
+        if pair is not None:
+            chunk = pair[0].step(chunk)
         codes = self.mimi.encode(chunk)
         for c in range(codes.shape[-1]):
             tokens = self.lm_gen.step(codes[:, :self._n_user(), c:c + 1].contiguous())
@@ -134,6 +187,8 @@ class ServerState:
                 continue
             assert tokens.shape[1] == self.lm_gen.lm_model.dep_q + 1
             main_pcm = self.mimi.decode(tokens[:, 1:].contiguous())
+            if pair is not None:
+                main_pcm = pair[1].step(main_pcm)
             out.append((main_pcm[0, 0].detach().float().cpu().numpy(), int(tokens[0, 0, 0].item())))
         return out
 
@@ -153,8 +208,10 @@ class ServerState:
         from aiohttp import WSMsgType, web
         # the transport is settled BEFORE the upgrade: an unknown ?pcm= value, or pcm=opus without `sphn`, is answered with 400 and the
         # reason (after ws.prepare() the client would only see an abrupt 1011 close)
+        # so is the client's sample rate (?sr=, default the codec's): PCM comes in and goes out at that rate, in frames of client_frame samples
         try:
-            framer = make_framer(self.frame_size, request.query.get("pcm", "f32"), int(getattr(self.mimi, "sample_rate", 24000)))
+            rate, client_frame = client_geometry(request.query.get("sr"), self.codec_rate, self.frame_size)
+            framer = make_framer(client_frame, request.query.get("pcm", "f32"), rate)
         except (ValueError, RuntimeError) as e:
             raise web.HTTPBadRequest(text=str(e))
         ws = web.WebSocketResponse()
@@ -192,7 +249,7 @@ class ServerState:
                 for pcm in framer.frames():
                     be = time.time()
                     chunk = torch.from_numpy(pcm).to(self.device)[None, None]
-                    for out_pcm, text_token in self.frame(chunk):
+                    for out_pcm, text_token in self.frame(chunk, rate):
                         payload = framer.encode(out_pcm)
                         if len(payload) > 0:            # (an Opus writer hands out whole pages: nothing yet is not a message)
                             await outbox.put(bytes([KIND_AUDIO]) + payload)
@@ -214,8 +271,7 @@ class ServerState:
 
         log("info", "accepted connection")
         async with self.lock:       # one session at a time (server.py:157)
-            self.mimi.reset_streaming()
-            self.lm_gen.reset_streaming()
+            self.reset_session(rate)
             await ws.send_bytes(bytes([KIND_HANDSHAKE]))
             await asyncio.gather(frame_loop(), recv_loop(), send_loop())
         log("info", "done with connection")

@@ -29,6 +29,9 @@ def get_parser():
     p.add_argument("--chunk-size", type=int, default=256, help="utterances read before sorting into batches")
     p.add_argument("--strict", action="store_true", help="exit with status 1 when any listed utterance produced no codes "
                    "(default: log and skip it, as the reference does)")
+    p.add_argument("--resample", choices=["host", "device"], default="host",
+                   help="where files at other rates are converted to 24 kHz: host = torch CPU, file by file; device = one launch per "
+                        "batch on the GPU, 16-bit mono .wav uploaded as int16")
     return p
 
 
@@ -45,7 +48,8 @@ def main(argv=None):
     items = offline.read_list(args.input_file or args.wav_scp)
     t0 = time.time()
     skipped = []
-    data = offline.tokenize_list(tokenizer, items, chunk_size=args.chunk_size, max_batch_seconds=args.batch_seconds, skipped=skipped)
+    data = offline.tokenize_list(tokenizer, items, chunk_size=args.chunk_size, max_batch_seconds=args.batch_seconds, skipped=skipped,
+                                 resample=args.resample)
     torch.save(data, args.output_file)
     frames = sum(v.shape[1] for v in data.values())
     logging.info(f"processed {len(data)} / {len(items)} examples, {frames} frames in {time.time() - t0:.1f} s")
