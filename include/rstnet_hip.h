@@ -375,6 +375,30 @@ int rst_gemv_mxfp4w_supported(int B, int N, int K);
 int rst_gemv_mxfp4w_f32(const float* x, const float* alpha, const uint8_t* q, const uint8_t* scale, const float* res, const float* bias,
                         float* y, int B, int N, int K, int ldx, int ldy, int prologue, float eps, int gate_out, rst_stream_t stream);
 
+/* Per-row LoRA adapters from a device-resident bank (csrc/lm_lora_bank.hip): the unmerged LoRA branch y += B (scale * (A P(x)))
+ * (models/llama_streaming.py:136-143) behind an adapted linear, every row of the call with the adapter its stream selected.
+ *   id(row) = ids[row / rows_per_id], ids int32 [n_ids] on the device, n_ids = rows / rows_per_id (a T-position call lays its rows
+ *   out as b * T + t: rows_per_id = T).  A row whose id fails the ONE test (unsigned)id < n_adapters -- -1 and every other negative
+ *   id included -- is a base-model row: shrink writes zeros for it, expand leaves y[row] untouched, nothing is read from the bank.
+ * rst_lora_bank_shrink_f32:  a[row][0:r] = post_scale * A_bank[id(row)] . P(x[row]);  x fp32 rows ldx apart (K wide, 2K = [u | v] for
+ *   the gate), A_bank bf16 [n_adapters][r][K], a fp32 [rows][r]; prologue 0 none, 1 RMSNorm(alpha, eps), 2 SiLU gate, the arithmetic
+ *   of rst_gemv_bf16_f32's prologues.
+ * rst_lora_bank_expand_f32:  y[row][0:N] += B_bank[id(row)] . a[row], in place; B_bank bf16 [n_adapters][N][r], y fp32 rows ldy apart.
+ * ARITHMETIC: bf16 weights widened exactly, activations fp32, every multiply-add an FMA.  Shrink: lane l of a wave multiplies
+ *   k = 8 l + 512 c .. + 7 of every 512-wide chunk c, ascending, into one accumulator started at 0; the 64 accumulators meet in the
+ *   xor butterfly (offsets 32, 16, .. 1); the sum is multiplied by post_scale.  Expand: one accumulator per output, started at 0,
+ *   j = 0 .. r-1 ascending, then one addition into y.  No atomics; the schedule depends on (K, r, N) only, so a row's result is
+ *   bit-identical whatever batch, row index or neighbours it has.
+ * SHAPES (rst_lora_bank_supported(K, r, N), host arithmetic): K % 8 == 0, 8 <= K <= 16384; r % 16 == 0, 16 <= r <= 256; N >= 1; any
+ *   rows >= 1.  < 0 (rst_last_error): an unsupported shape, a null pointer, a bank not 16-byte aligned, rows not n_ids groups of
+ *   rows_per_id, n_adapters < 1, a row stride below its row, an unknown prologue, a grid past 2^31 - 1 workgroups. */
+int rst_lora_bank_supported(int K, int r, int N);
+int rst_lora_bank_shrink_f32(const float* x, const float* alpha, const uint16_t* A_bank, const int32_t* ids, float* a, int rows,
+                             int rows_per_id, int n_ids, int n_adapters, int r, int K, int ldx, int prologue, float eps, float post_scale,
+                             rst_stream_t stream);
+int rst_lora_bank_expand_f32(const float* a, const uint16_t* B_bank, const int32_t* ids, float* y, int rows, int rows_per_id, int n_ids,
+                             int n_adapters, int N, int r, int ldy, rst_stream_t stream);
+
 /* Two fused forms of the batch <= 2 GEMV for the depth transformer ("depformer", models/model.py:392-428,564-597;
  * "codecformer", models/llama_streaming.py:727-749), whose 8 steps x 6 layers are a chain of ~5 us launches:
  *

@@ -72,6 +72,9 @@ SIGNATURES = {
     "rst_quant_blocks_mxfp4": [_p, _p, _p, _i, _i, _p],
     "rst_gemv_mxfp4w_supported": [_i, _i, _i],
     "rst_gemv_mxfp4w_f32": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p],
+    "rst_lora_bank_supported": [_i, _i, _i],
+    "rst_lora_bank_shrink_f32": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p],
+    "rst_lora_bank_expand_f32": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "rst_gemv_attn_bf16_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "rst_gemv_embed_bf16_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
     "rst_depth_frame_workspace_bytes": [_i, _i, _i, _i],

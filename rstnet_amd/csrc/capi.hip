@@ -24,7 +24,7 @@ int rst_check_launch(const char* what) {
 
 extern "C" {
 
-int rst_version(void) { return 126; }      // 126: + rst_resample_sinc, rst_resample_plan (sample-rate conversion of ragged batches and streams); 125: + rst_skinny_pack_weight_mxfp4w, rst_gemm_skinny_mxfp4w_f32 / _supported (MXFP4 weight-only skinny GEMM); 124: + rst_skinny_pack_weight_fp8w, rst_gemm_skinny_fp8w_f32 / _supported (fp8 weight-only skinny GEMM); 123: + rst_quant_blocks_mxfp4, rst_gemv_mxfp4w_f32 / _supported (MXFP4 weight-only GEMV); 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
+int rst_version(void) { return 127; }      // 127: + rst_lora_bank_shrink_f32, rst_lora_bank_expand_f32, rst_lora_bank_supported (per-row LoRA adapters from a device-resident bank); 126: + rst_resample_sinc, rst_resample_plan (sample-rate conversion of ragged batches and streams); 125: + rst_skinny_pack_weight_mxfp4w, rst_gemm_skinny_mxfp4w_f32 / _supported (MXFP4 weight-only skinny GEMM); 124: + rst_skinny_pack_weight_fp8w, rst_gemm_skinny_fp8w_f32 / _supported (fp8 weight-only skinny GEMM); 123: + rst_quant_blocks_mxfp4, rst_gemv_mxfp4w_f32 / _supported (MXFP4 weight-only GEMV); 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
                                            // rst_rvq_search_chain_f32, rst_embed_sum_bf16(add_stride); 105: round 4
 const char* rst_last_error(void) { return g_err; }
 
@@ -389,6 +389,25 @@ int rst_gemv_mxfp4w_supported(int B, int N, int K) { return rst_gemv_mxfp4w_supp
 int rst_gemv_mxfp4w_f32(const float* x, const float* alpha, const uint8_t* q, const uint8_t* scale, const float* res, const float* bias,
                         float* y, int B, int N, int K, int ldx, int ldy, int prologue, float eps, int gate_out, rst_stream_t stream) {
     return rst_launch_gemv_mxfp4w(gemv_quant_params(x, alpha, q, scale, res, bias, y, B, N, K, ldx, ldy, prologue, eps, gate_out), (hipStream_t)stream);
+}
+
+int rst_lora_bank_supported(int K, int r, int N) { return rst_lora_bank_supported_impl(K, r, N); }
+
+int rst_lora_bank_shrink_f32(const float* x, const float* alpha, const uint16_t* A_bank, const int32_t* ids, float* a, int rows,
+                             int rows_per_id, int n_ids, int n_adapters, int r, int K, int ldx, int prologue, float eps, float post_scale,
+                             rst_stream_t stream) {
+    LoraBankShrinkParams p;
+    p.x = x; p.alpha = alpha; p.A = A_bank; p.ids = ids; p.a = a; p.rows = rows; p.rows_per_id = rows_per_id; p.n_adapters = n_adapters;
+    p.r = r; p.K = K; p.ldx = ldx; p.prologue = prologue; p.eps = eps; p.post_scale = post_scale;
+    return rst_launch_lora_bank_shrink(p, n_ids, (hipStream_t)stream);
+}
+
+int rst_lora_bank_expand_f32(const float* a, const uint16_t* B_bank, const int32_t* ids, float* y, int rows, int rows_per_id, int n_ids,
+                             int n_adapters, int N, int r, int ldy, rst_stream_t stream) {
+    LoraBankExpandParams p;
+    p.a = a; p.B = B_bank; p.ids = ids; p.y = y; p.rows = rows; p.rows_per_id = rows_per_id; p.n_adapters = n_adapters; p.N = N; p.r = r;
+    p.ldy = ldy; p.nblk = 0;
+    return rst_launch_lora_bank_expand(p, n_ids, (hipStream_t)stream);
 }
 
 int rst_gemv_attn_bf16_f32(const float* qkv, float* k_cache, float* v_cache, const int64_t* pos_dev, const uint16_t* w,

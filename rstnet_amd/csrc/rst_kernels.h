@@ -146,6 +146,21 @@ int rst_launch_resample_sinc(const void* x, int x_dtype, long x_row_stride, int 
                              hipStream_t stream);
 int rst_resample_slab_bytes(int o, int n, int L);   // LDS bytes a tile stages its inputs in; 0 = read from global (span too long)
 
+// ---- lm_lora_bank.hip ---------------------------------------------------------------------------
+// per-row LoRA adapters from a bank, contract at rst_lora_bank_shrink_f32 / _expand_f32 (include/rstnet_hip.h)
+struct LoraBankShrinkParams {
+    const float* x; const float* alpha; const unsigned short* A; const int* ids; float* a;
+    long rows; int rows_per_id, n_adapters, r, K, ldx, prologue;
+    float eps, post_scale;
+};
+struct LoraBankExpandParams {
+    const float* a; const unsigned short* B; const int* ids; float* y;
+    long rows; int rows_per_id, n_adapters, N, r, ldy, nblk;     // nblk: filled by the launcher
+};
+int rst_lora_bank_supported_impl(int K, int r, int N);
+int rst_launch_lora_bank_shrink(const LoraBankShrinkParams& p, int n_ids, hipStream_t stream);
+int rst_launch_lora_bank_expand(LoraBankExpandParams p, int n_ids, hipStream_t stream);
+
 // ---- attention.hip ----------------------------------------------------------------------------
 struct RopeSplitParams {
     const float* qkv;   // [B][T][3][H][D]

@@ -67,12 +67,17 @@ class GPTGen:
         self._regime = None
         self.B = 0
 
-    def begin(self, batch_size: int, kv_dtype: Optional[torch.dtype] = None) -> None:
-        """Open a session of ``batch_size`` streams.  ``kv_dtype``: precision of the global KV rings (None = the model's ``kv_dtype``)."""
+    def begin(self, batch_size: int, kv_dtype: Optional[torch.dtype] = None, adapter_ids=None) -> None:
+        """Open a session of ``batch_size`` streams.  ``kv_dtype``: precision of the global KV rings (None = the model's ``kv_dtype``).
+        ``adapter_ids``: the adapter set of every stream (``GPT.set_adapter_ids``; needs ``GPT.load_adapter_bank``) -- they may change
+        during the session through ``set_adapter_ids``, the captured graphs read them from the device."""
         m = self.model
         cfg, dev = m.config, m.device
         eager = self.noise is not None or dev.type != "cuda"
         ring = m.transformer._make_state(batch_size, cfg.context + 1, kv_dtype)      # (refuses an unserved kv_dtype before anything changes)
+        if adapter_ids is not None:
+            m.set_adapter_ids(adapter_ids)
+        m._bank_rows(batch_size)      # (a loaded bank: one id per stream, in place before a step is captured)
         self._saved = (m.transformer._streaming_state, m._streaming_state, m.codecformer._streaming_state)
         m.transformer._streaming_state = ring
         m._streaming_state = _GPTState(_Graphed(m._global_step, disable=eager))

@@ -14,6 +14,8 @@ Execution (csrc/lm_step.hip, lm_attn.hip, lm_skinny.hip): bf16 weights, fp32 act
     ``from_state_dict(..., merge_lora=False)`` keeps them apart instead, as ``LoRALinear.forward`` / ``LoRAQKVLinear.forward`` run
     them (:136-143, :373-406): every adapted linear is followed by two thin GEMMs, ``y += B_full (scaling * (A x))`` (same prologue as
     the dense product; the fused-QKV / stacked-gate B is laid out block-diagonally in the kernels' row order, rank padded to 16).
+    On such a model ``load_adapter_bank`` / ``set_adapter_ids`` serve one adapter set PER STREAM of a batch from a device-resident bank
+    (csrc/lm_lora_bank.hip: two launches per adapted linear, every row with its own adapter, bit-identical whatever it is batched with).
   * The fused QKV rows are re-ordered once from the GQA-interleaved ``[group: q.. k v]`` layout to ``[Q | K | V]`` and, inside
     every q / k head, from rotate-half pairing ``(i, i + n/2)`` to interleaved pairing ``(2i, 2i+1)`` -- a permutation applied to
     q and k alike leaves q.k unchanged -- so the ring-attention kernels of the Moshi path serve this model too.
@@ -38,7 +40,7 @@ from . import model as _lm_model       # PREFILL_CHUNK is read at call time
 from .model import RMSNorm as _AlphaNorm  # noqa: F401  (key layout of the codecformer norms)
 from .model import ScaledEmbedding, StreamingTransformer, _Weight, adopt_state_dict
 from .stack import KV_DTYPES, ROUTE_APPEND_FIRST, ROUTE_PREFILL, prefill_route, prefill_window  # noqa: F401  (the route rules, under the names callers know)
-from .stack import ROUTE_DECODE, Geometry, LayerView, LinearView, _lora_add, _StepState, check_kv_dtype, counted_step, prefill_chunks, run_chunks
+from .stack import ROUTE_DECODE, Geometry, LayerView, LinearView, LoraBank, _lora_add, _StepState, check_kv_dtype, counted_step, prefill_chunks, run_chunks
 
 
 @dataclass
@@ -267,6 +269,39 @@ def _pad_rank(A: torch.Tensor, Bm: torch.Tensor, scale: float):
     return Ap.contiguous(), Bp.contiguous(), (1.0 if fold else float(scale))
 
 
+def _qkv_adapter_form(c: Config, A: torch.Tensor, Bm: torch.Tensor, scale: float):
+    """The fused-QKV adapter ``(lora_A, lora_B)`` in kernel form: ``B_full [rows of packed_qkv, r * enabled]`` holds each adapted
+    projection's B block in its own r columns (LoRAQKVLinear.conv1d, :310-354), on the rows ``zero_pad`` sends them to (:259-308, incl.
+    its 'as is' return when q, k and v are all adapted), then in the [Q | K | V] / interleaved-rotary row order of ``packed_qkv``."""
+    enable = (c.lora_query, c.lora_key, c.lora_value)
+    sizes = [n for n, e in zip((c.head_size * c.n_head, c.head_size * c.n_query_groups, c.head_size * c.n_query_groups), enable) if e]
+    r = c.lora_r
+    Bm = Bm.detach()
+    rows = _qkv_lora_rows(c, enable)
+    rows = torch.arange(Bm.shape[0]) if rows is None else rows
+    full = torch.zeros((c.n_head + 2 * c.n_query_groups) * c.head_size, r * len(sizes), device=Bm.device, dtype=Bm.dtype)
+    row = 0
+    for i, n in enumerate(sizes):
+        full[rows[row:row + n].to(Bm.device), i * r:(i + 1) * r] = Bm[row:row + n]
+        row += n
+    full = full.index_select(0, _qkv_row_order(c).to(Bm.device))
+    return _pad_rank(A, full, scale)
+
+
+def _fc_adapter_form(I: int, pairs, scale: float):
+    """Adapters of fc_1 | fc_2 in kernel form for the stacked product: ``pairs = [(A, B) of fc_1 or None, (A, B) of fc_2 or None]``
+    (at least one present), A's stacked, B's block-diagonal over the ``2 I`` stacked rows."""
+    present = [(i, ab[0].detach(), ab[1].detach()) for i, ab in enumerate(pairs) if ab is not None]
+    A0 = present[0][1]
+    full = torch.zeros(2 * I, sum(A.shape[0] for _, A, _ in present), device=A0.device, dtype=A0.dtype)
+    col = 0
+    for i, A, Bm in present:
+        r = A.shape[0]
+        full[i * I:(i + 1) * I, col:col + r] = Bm
+        col += r
+    return _pad_rank(torch.cat([A for _, A, _ in present]), full, scale)
+
+
 # ----------------------------------------------------------------------------------------------------------------- modules
 class _Linear(nn.Module):
     """``<name>.linear.{weight,bias}`` holder (a merged LoRALinear)."""
@@ -356,28 +391,11 @@ class CausalSelfAttention(nn.Module):
         return self._packed.get((w,) if b is None else (w, b), build)
 
     def packed_qkv_adapter(self):
-        """The fused-QKV adapter in kernel form: ``B_full [rows of packed_qkv, r * enabled]`` holds each adapted projection's B block
-        in its own r columns (LoRAQKVLinear.conv1d, :310-354), on the rows ``zero_pad`` sends them to (:259-308, incl. its 'as is'
-        return when q, k and v are all adapted), then in the [Q | K | V] / interleaved-rotary row order of ``packed_qkv``."""
+        """The fused-QKV adapter in kernel form (``_qkv_adapter_form``), or None without unmerged adapters."""
         lin, c = self.attn, self.config
         if lin.lora_A is None:
             return None
-
-        def build():
-            enable = (c.lora_query, c.lora_key, c.lora_value)
-            sizes = [n for n, e in zip((c.head_size * c.n_head, c.head_size * c.n_query_groups, c.head_size * c.n_query_groups), enable) if e]
-            r = c.lora_r
-            Bm = lin.lora_B.detach()
-            rows = _qkv_lora_rows(c, enable)
-            rows = torch.arange(Bm.shape[0]) if rows is None else rows
-            full = torch.zeros(lin.linear.weight.shape[0], r * len(sizes), device=Bm.device, dtype=Bm.dtype)
-            row = 0
-            for i, n in enumerate(sizes):
-                full[rows[row:row + n].to(Bm.device), i * r:(i + 1) * r] = Bm[row:row + n]
-                row += n
-            full = full.index_select(0, _qkv_row_order(c).to(Bm.device))
-            return _pad_rank(lin.lora_A, full, lin.lora_scale)
-        return self._packed_ad.get((lin.lora_A, lin.lora_B), build)
+        return self._packed_ad.get((lin.lora_A, lin.lora_B), lambda: _qkv_adapter_form(c, lin.lora_A, lin.lora_B, lin.lora_scale))
 
 
 class LLaMAMLP(nn.Module):
@@ -408,20 +426,9 @@ class LLaMAMLP(nn.Module):
         if l1.lora_A is None and l2.lora_A is None:
             return None
         present = [l for l in (l1, l2) if l.lora_A is not None]
-
-        def build():
-            I = l1.linear.weight.shape[0]
-            scale = present[0].lora_scale
-            As = [l.lora_A.detach() for l in present]
-            full = torch.zeros(2 * I, sum(a.shape[0] for a in As), device=As[0].device, dtype=As[0].dtype)
-            col = 0
-            for l in present:
-                r = l.lora_A.shape[0]
-                o = 0 if l is l1 else I
-                full[o:o + I, col:col + r] = l.lora_B.detach()
-                col += r
-            return _pad_rank(torch.cat(As), full, scale)
-        return self._packed_ad.get(tuple(p for l in present for p in (l.lora_A, l.lora_B)), build)
+        pairs = [None if l.lora_A is None else (l.lora_A, l.lora_B) for l in (l1, l2)]
+        return self._packed_ad.get(tuple(p for l in present for p in (l.lora_A, l.lora_B)),
+                                   lambda: _fc_adapter_form(l1.linear.weight.shape[0], pairs, present[0].lora_scale))
 
 
 class Block(nn.Module):
@@ -434,13 +441,19 @@ class Block(nn.Module):
         self.attn = CausalSelfAttention(config, **fk)
         self.norm_2 = _LitNorm(config.n_embd, config.norm_eps, **fk)
         self.mlp = LLaMAMLP(config, **fk)
+        self.bank: Optional[Dict[str, LoraBank]] = None      # GPT.load_adapter_bank: {"qkv" / "out" / "fc" / "proj": LoraBank}
 
     def view(self) -> LayerView:
-        """The block as ``stack.run_layers`` reads it: packed weights and biases, unmerged adapters in kernel form."""
+        """The block as ``stack.run_layers`` reads it: packed weights and biases, unmerged adapters in kernel form -- the model's single
+        set, or while an adapter bank is loaded the bank's (a linear no set of the bank adapts runs without a LoRA branch)."""
         att, mlp = self.attn, self.mlp
         (wqkv, bqkv), (wfc, bfc) = att.packed_qkv(), mlp.packed_fc()
-        return LayerView(LinearView(wqkv, bqkv, lora=att.packed_qkv_adapter()), LinearView(att.proj.weight, att.proj.bias_f32(), lora=att.proj.adapter()),
-                         LinearView(wfc, bfc, lora=mlp.packed_fc_adapter()), LinearView(mlp.proj.weight, mlp.proj.bias_f32(), lora=mlp.proj.adapter()),
+        if self.bank is not None:
+            ads = [self.bank.get(k) for k in ("qkv", "out", "fc", "proj")]
+        else:
+            ads = [att.packed_qkv_adapter(), att.proj.adapter(), mlp.packed_fc_adapter(), mlp.proj.adapter()]
+        return LayerView(LinearView(wqkv, bqkv, lora=ads[0]), LinearView(att.proj.weight, att.proj.bias_f32(), lora=ads[1]),
+                         LinearView(wfc, bfc, lora=ads[2]), LinearView(mlp.proj.weight, mlp.proj.bias_f32(), lora=ads[3]),
                          (self.norm_1.gain_f32(), self.norm_1.eps), (self.norm_2.gain_f32(), self.norm_2.eps))
 
 
@@ -500,6 +513,12 @@ class GPT(StreamingModule[_GPTState]):
         self.lm_head = _Linear(config.n_embd, config.padded_vocab_size, config.lm_head_bias, **fk)
         self._lora_base: Optional[Dict[str, torch.Tensor]] = None      # from_state_dict(..., keep_lora_base=True)
         self._unmerged = False                                         # from_state_dict(..., merge_lora=False)
+        self._keep_unmerged = False                                    # ... whether or not that state dict carried adapters (load_adapter_bank)
+        self._bank: Optional[Dict[str, tuple]] = None                  # load_adapter_bank: {linear: (A_bank, B_bank, post_scale)}
+        self._bank_sets = 0
+        self._bank_ids: Optional[torch.Tensor] = None                  # the ONE int32 device vector every LoraBank view holds
+        self._bank_ids_given = False                                   # set_adapter_ids was called (else: every row -1)
+        self._head_bank: Optional[LoraBank] = None
         self.dep_q = config.dep_q
         self.transformer = LLAMAStreamingTransformer(config, **fk)
         self.max_seq_length = config.block_size
@@ -574,6 +593,7 @@ class GPT(StreamingModule[_GPTState]):
 
     # ---- streaming state
     def _init_streaming_state(self, batch_size: int) -> _GPTState:
+        self._bank_rows(batch_size)      # (the default ids exist before a step is captured)
         disable = self.device.type != "cuda"
         return _GPTState(_Graphed(self._global_step, disable=disable))
 
@@ -584,11 +604,13 @@ class GPT(StreamingModule[_GPTState]):
         return ops.embed_sum(toks, tables, list(range(1, K)) + [0])       # audio streams first, then text, as :680-686
 
     def _head(self, h: torch.Tensor) -> torch.Tensor:
-        return _lora_add(ops.lm_linear(h, self.lm_head.weight, bias=self.lm_head.bias_f32()), h, self.lm_head.adapter())
+        ad = self._head_bank if self._bank is not None else self.lm_head.adapter()
+        return _lora_add(ops.lm_linear(h, self.lm_head.weight, bias=self.lm_head.bias_f32()), h, ad)
 
     def _global_step(self, toks: torch.Tensor):
         """One streamed position: toks int64 ``[B, n_q+1]`` -> (hidden ``[B, n_embd]``, text logits ``[B, V]``)."""
         st = self.transformer._streaming_state
+        self._bank_rows(toks.shape[0])
         h = self.transformer.run(self._embed(toks), toks.shape[0], 1, st)
         return h, self._head(h)
 
@@ -602,6 +624,7 @@ class GPT(StreamingModule[_GPTState]):
         if self.max_seq_length < T:
             raise ValueError(f"Cannot forward sequence of length {T}, max seq length is only {self.max_seq_length}.")
         c = self.config
+        self._bank_rows(B)
         st = self.transformer._streaming_state
         if st is not None and T == 1 and self._streaming_state is not None:
             h, logits = counted_step(st, self._streaming_state.graphed_global, sequence.reshape(B, K).contiguous())
@@ -680,7 +703,7 @@ class GPT(StreamingModule[_GPTState]):
             if not merge_lora:
                 is_ad = lambda k: k.endswith((".lora_A", ".lora_B"))
                 model = cls._from_merged({k: v for k, v in sd.items() if not is_ad(k)}, config)
-                model._unmerged = True
+                model._unmerged = model._keep_unmerged = True
                 model.kv_dtype = kv_dtype
                 model._set_adapters({k: v for k, v in sd.items() if is_ad(k)})
                 return model
@@ -689,6 +712,7 @@ class GPT(StreamingModule[_GPTState]):
             sd = merge_lora_state_dict(sd, config)
         model = cls._from_merged(sd, config)
         model._lora_base = bases
+        model._keep_unmerged = not merge_lora
         model.kv_dtype = kv_dtype
         return model
 
@@ -751,20 +775,142 @@ class GPT(StreamingModule[_GPTState]):
             if name not in names:
                 m.set_adapter(None, None, 0.0)
                 continue
-            if f"{name}.lora_A" not in adapters or f"{name}.lora_B" not in adapters:
-                raise RuntimeError(f"{name}: lora_A and lora_B come as a pair")
-            A, Bm = adapters[f"{name}.lora_A"], adapters[f"{name}.lora_B"]
-            n_en = sum((c.lora_query, c.lora_key, c.lora_value)) if name.endswith(".attn.attn") else 1
-            out_f = m.linear.weight.shape[0]
-            if name.endswith(".attn.attn"):
-                out_f = sum(n for n, e in zip((c.head_size * c.n_head, c.head_size * c.n_query_groups, c.head_size * c.n_query_groups),
-                                              (c.lora_query, c.lora_key, c.lora_value)) if e)
-            if tuple(A.shape) != (c.lora_r * n_en, m.linear.weight.shape[1]) or tuple(Bm.shape) != (out_f, c.lora_r):
-                raise RuntimeError(f"{name}: adapter shapes {tuple(A.shape)} / {tuple(Bm.shape)} do not fit r={c.lora_r}")
+            A, Bm = self._checked_pair(adapters, name, m)
             m.set_adapter(A.to(dev), Bm.to(dev), c.lora_alpha / c.lora_r)
         for blk in self.transformer.h:      # kernel-side forms are rebuilt from the new tensors
             blk.attn.adapters_changed()
             blk.mlp.adapters_changed()
+
+    def _adapter_shapes(self, name: str, m: "_Linear") -> Tuple[tuple, tuple]:
+        """Shapes of ``<name>.lora_A`` / ``<name>.lora_B`` as the reference allocates them (:107-110, :205-221)."""
+        c = self.config
+        n_en = sum((c.lora_query, c.lora_key, c.lora_value)) if name.endswith(".attn.attn") else 1
+        out_f = m.linear.weight.shape[0]
+        if name.endswith(".attn.attn"):
+            out_f = sum(n for n, e in zip((c.head_size * c.n_head, c.head_size * c.n_query_groups, c.head_size * c.n_query_groups),
+                                          (c.lora_query, c.lora_key, c.lora_value)) if e)
+        return (c.lora_r * n_en, m.linear.weight.shape[1]), (out_f, c.lora_r)
+
+    def _checked_pair(self, adapters: Dict[str, torch.Tensor], name: str, m: "_Linear") -> Tuple[torch.Tensor, torch.Tensor]:
+        if f"{name}.lora_A" not in adapters or f"{name}.lora_B" not in adapters:
+            raise RuntimeError(f"{name}: lora_A and lora_B come as a pair")
+        A, Bm = adapters[f"{name}.lora_A"], adapters[f"{name}.lora_B"]
+        if (tuple(A.shape), tuple(Bm.shape)) != self._adapter_shapes(name, m):
+            raise RuntimeError(f"{name}: adapter shapes {tuple(A.shape)} / {tuple(Bm.shape)} do not fit r={self.config.lora_r}")
+        return A, Bm
+
+    # ---- adapter bank: one set of adapters per stream
+    def load_adapter_bank(self, sets) -> None:
+        """Serve several LoRA adapter sets from ONE copy of the base weights, every stream of a batch with the set ``set_adapter_ids``
+        gives it (``-1``: the plain base model).  ``sets``: a list of 1 to 256 dicts of ``<name>.lora_A`` / ``<name>.lora_B`` (the keys and
+        shapes ``load_adapters`` takes); for every linear a set adapts, ``lm_head`` included, the kernel-form pairs of all sets are stacked
+        on the device (``[n_sets, r', in]`` / ``[n_sets, out, r']``; a set that lacks the linear contributes zeros) and the LoRA branch runs
+        as ``ops.lora_bank_shrink`` + ``ops.lora_bank_expand``.  Needs ``from_state_dict(..., merge_lora=False)`` (with or without adapters
+        of the model's own: those rest while a bank is loaded) and, like ``load_adapters``, happens between sessions.
+        ``load_adapter_bank(None)`` drops the bank: the model is again what it was before."""
+        if not self._keep_unmerged:
+            raise RuntimeError("load_adapter_bank needs a model built with from_state_dict(..., merge_lora=False)")
+        if self._streaming_state is not None or self.transformer._streaming_state is not None:
+            raise RuntimeError("load_adapter_bank: load or drop a bank between sessions, not inside streaming()")
+        if sets is None:
+            self._bank, self._bank_sets, self._bank_ids, self._bank_ids_given = None, 0, None, False
+            self._bind_bank()
+            return
+        sets = [{k: v for k, v in s.items() if k.endswith((".lora_A", ".lora_B"))} for s in sets]
+        if not 1 <= len(sets) <= 256:
+            raise ValueError(f"load_adapter_bank: {len(sets)} adapter sets (1 to 256)")
+        c, lin = self.config, self._adapted_linears()
+        present = []
+        for s in sets:
+            names = {k[: -len(".lora_A")] for k in s}      # (both suffixes are 7 characters long)
+            unknown = sorted(n for n in names if n not in lin)
+            if unknown:
+                raise RuntimeError(f"adapters for linears the config does not adapt: {unknown[:3]}")
+            for n in sorted(names):
+                self._checked_pair(s, n, lin[n])
+            present.append(names)
+        adapted = set().union(*present)
+        # the launches' shapes, by host arithmetic, before any tensor is built: {bank key: (members, K, r', N)}
+        groups: Dict[str, tuple] = {}
+        pad = lambda r: (r + 15) // 16 * 16
+        for name in sorted(adapted):
+            m = lin[name]
+            N, K = m.linear.weight.shape
+            if name.endswith((".mlp.fc_1", ".mlp.fc_2")):
+                groups[name[: -2]] = ((name[: -1] + "1", name[: -1] + "2"), K, pad(2 * c.lora_r), 2 * N)
+            else:
+                groups[name] = ((name,), K, pad(self._adapter_shapes(name, m)[0][0]), N)
+        for key, (_, K, rp, N) in groups.items():
+            if not ops.lora_bank_supported(K, rp, N):
+                raise ValueError(f"load_adapter_bank: {key} (in {K}, padded rank {rp}, out {N}) is outside the adapter-bank kernels "
+                                 "(in % 8 == 0, in <= 16384, rank <= 256)")
+        dev, scale = self.lm_head.weight.device, c.lora_alpha / c.lora_r
+        bank: Dict[str, tuple] = {}
+        for key, (members, K, rp, N) in groups.items():
+            forms = []
+            for s in sets:
+                pairs = []
+                for name in members:      # a set that lacks the linear: zero blocks of the same shape
+                    shp_a, shp_b = self._adapter_shapes(name, lin[name])
+                    pairs.append((s[f"{name}.lora_A"].to(dev), s[f"{name}.lora_B"].to(dev)) if f"{name}.lora_A" in s else
+                                 (torch.zeros(shp_a, device=dev, dtype=self.lm_head.weight.dtype), torch.zeros(shp_b, device=dev, dtype=self.lm_head.weight.dtype)))
+                if len(members) == 2:
+                    forms.append(_fc_adapter_form(N // 2, pairs, scale))
+                elif key.endswith(".attn.attn"):
+                    forms.append(_qkv_adapter_form(c, pairs[0][0], pairs[0][1], scale))
+                else:
+                    forms.append(_pad_rank(pairs[0][0], pairs[0][1], scale))
+            bank[key] = (torch.stack([f[0] for f in forms]).contiguous(), torch.stack([f[1] for f in forms]).contiguous(), forms[0][2])
+        self._bank, self._bank_sets, self._bank_ids, self._bank_ids_given = bank, len(sets), None, False
+        self._bind_bank()
+
+    def adapter_bank(self) -> Optional[Dict[str, tuple]]:
+        """``{linear: (A_bank, B_bank, post_scale)}`` of the loaded bank (``...attn.attn``, ``...attn.proj``, ``...mlp.fc`` = fc_1 | fc_2
+        stacked, ``...mlp.proj``, ``lm_head``), or None."""
+        return self._bank
+
+    def _bind_bank(self) -> None:
+        """Hand every block (and the head) its ``LoraBank`` views, all on the current id vector."""
+        bank, ids = self._bank, self._bank_ids
+        view = lambda key: None if bank is None or ids is None or key not in bank else LoraBank(*bank[key], ids)
+        self._head_bank = view("lm_head")
+        for l, blk in enumerate(self.transformer.h):
+            p = f"transformer.h.{l}"
+            blk.bank = None if bank is None else {"qkv": view(f"{p}.attn.attn"), "out": view(f"{p}.attn.proj"), "fc": view(f"{p}.mlp.fc"),
+                                                  "proj": view(f"{p}.mlp.proj")}
+
+    def set_adapter_ids(self, ids) -> None:
+        """Adapter set of every stream: ``ids`` a list or integer tensor of length ``B`` with values in ``[-1, n_sets)``, ``-1`` = no adapter
+        (checked on the host for a list or a CPU tensor; a device tensor is taken as it is, without a synchronisation -- the kernels treat
+        every id outside ``[0, n_sets)`` as ``-1``).  With the same ``B`` as before the ids are copied IN PLACE into the model's one id
+        vector, so captured steps see them on their next replay; another ``B`` takes a new vector, between sessions only."""
+        if self._bank is None:
+            raise RuntimeError("set_adapter_ids: no adapter bank loaded (load_adapter_bank)")
+        dev = self.lm_head.weight.device
+        t = ids if isinstance(ids, torch.Tensor) else torch.tensor(list(ids), dtype=torch.int64)
+        if t.dim() != 1 or t.numel() < 1 or t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError(f"set_adapter_ids: ids must be a vector of integers, got {tuple(t.shape)} {t.dtype}")
+        if not t.is_cuda and (int(t.min()) < -1 or int(t.max()) >= self._bank_sets):
+            raise ValueError(f"set_adapter_ids: ids must lie in [-1, {self._bank_sets}), got {t.tolist()}")
+        if self._bank_ids is not None and self._bank_ids.numel() == t.numel():
+            self._bank_ids.copy_(t.to(torch.int32))
+        else:
+            if self._streaming_state is not None or self.transformer._streaming_state is not None:
+                raise RuntimeError(f"set_adapter_ids: {t.numel()} ids inside a session of another batch size")
+            self._bank_ids = t.to(device=dev, dtype=torch.int32).contiguous().clone()
+            self._bind_bank()
+        self._bank_ids_given = True
+
+    def _bank_rows(self, B: int) -> None:
+        """While a bank is loaded every call carries one row group per id; without ``set_adapter_ids`` every row is ``-1``."""
+        if self._bank is None:
+            return
+        if self._bank_ids is not None and self._bank_ids.numel() == B:
+            return
+        if self._bank_ids_given:
+            raise ValueError(f"adapter bank: batch size {B} differs from the {self._bank_ids.numel()} ids of set_adapter_ids")
+        self._bank_ids = torch.full((B,), -1, device=self.lm_head.weight.device, dtype=torch.int32)
+        self._bind_bank()
 
     @classmethod
     def _from_merged(cls, sd: Dict[str, torch.Tensor], config: Config) -> "GPT":

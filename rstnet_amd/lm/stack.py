@@ -108,11 +108,21 @@ class Geometry(NamedTuple):
     litgpt_freqs: bool = False    # the prefill kernels rotate by ops.gpt_rope_freqs (the table litgpt evaluates), not by the Moshi table inside ops
 
 
+class LoraBank(NamedTuple):
+    """Unmerged adapters of one linear for several adapter sets at once, in kernel form (``GPT.load_adapter_bank``): row ``b`` of a call
+    takes set ``ids[b]``, or none where the id is outside ``[0, n_sets)``.  ``ids`` is the model's ONE int32 device vector, shared by
+    every view (``GPT.set_adapter_ids`` writes it in place, so captured graphs see new ids on their next replay)."""
+    A_bank: torch.Tensor          # bf16 [n_sets, r', in]
+    B_bank: torch.Tensor          # bf16 [n_sets, out, r']
+    post_scale: float
+    ids: torch.Tensor             # int32 [B]
+
+
 class LinearView(NamedTuple):
     w: torch.Tensor
     bias: Optional[torch.Tensor] = None
     w8: Optional[tuple] = None        # stored fp8 / MXFP4 copy of ``w``: streamed by the batch <= 2 GEMV route; an fp8 pair and an ``ops.Mxfp4BatchedCopy`` also by the skinny GEMM above
-    lora: Optional[tuple] = None      # unmerged adapter ``(A, B, post_scale)`` in kernel form
+    lora: Optional[tuple] = None      # unmerged adapter ``(A, B, post_scale)`` in kernel form, or a ``LoraBank``
 
 
 class LayerView(NamedTuple):
@@ -127,9 +137,17 @@ class LayerView(NamedTuple):
 
 
 def _lora_add(y: torch.Tensor, x, ad, **prologue) -> torch.Tensor:
-    """``y + B (scaling * (A P(x)))`` -- the unmerged LoRA branch (llama_streaming.py:136-143) as two thin products."""
+    """``y + B (scaling * (A P(x)))`` -- the unmerged LoRA branch (llama_streaming.py:136-143) as two thin products; with a ``LoraBank``
+    every row takes its stream's adapter (rows ``b * T + t``: ``T`` rows per id), the update going into ``y`` in place."""
     if ad is None:
         return y
+    if isinstance(ad, LoraBank):
+        B = ad.ids.numel()
+        if x.shape[0] % B:
+            raise ValueError(f"adapter bank: {x.shape[0]} rows do not divide over the {B} streams of set_adapter_ids")
+        T = x.shape[0] // B
+        a = ops.lora_bank_shrink(x, ad.A_bank, ad.ids, rows_per_id=T, post_scale=ad.post_scale, **prologue)
+        return ops.lora_bank_expand(a, ad.B_bank, ad.ids, y, rows_per_id=T)
     A, Bm, scale = ad
     a = ops.lm_linear(x, A, **prologue)
     if scale != 1.0:
@@ -175,7 +193,8 @@ def run_layers(x: Optional[torch.Tensor], T: int, st: _StepState, route: str, ge
             x = ops.gemv_attn(qkv, k, v, pos_t, ly.out.w, context=geo.context, res=x)
         else:
             if route == ROUTE_DECODE:
-                a = ops.lm_attn_decode(qkv, k, v, pos_t, context=geo.context, scratch=st.scratch, heads=geo.heads, packed=B > 2 and not fp8,
+                a = ops.lm_attn_decode(qkv, k, v, pos_t, context=geo.context, scratch=st.scratch, heads=geo.heads,
+                                       packed=B > 2 and not fp8 and not isinstance(ly.out.lora, LoraBank),      # (the bank's shrink reads fp32 rows)
                                        rope_table=rope_table, **rot)
             elif route == ROUTE_PREFILL:
                 q3 = qkv.view(B, T, -1)

@@ -1417,6 +1417,60 @@ def lm_linear(x: torch.Tensor, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE
                                      res=None if res is None else res[i:i + 64], bias=bias) for i in range(0, x.shape[0], 64)])
 
 
+def lora_bank_supported(K: int, r: int, N: int) -> bool:
+    """Shapes the adapter-bank launches serve (``K % 8 == 0``, ``K <= 16384``, ``r % 16 == 0``, ``r <= 256``, ``N >= 1``); there is no
+    other route: ``GPT.load_adapter_bank`` refuses a linear outside them."""
+    return bool(_lib.lib().rst_lora_bank_supported(K, r, N))
+
+
+def _bank_ids(ids: torch.Tensor, rows: int, rows_per_id: int) -> int:
+    _chk(ids, "ids", torch.int32)
+    if rows_per_id < 1 or rows % rows_per_id or ids.dim() != 1 or ids.numel() != rows // rows_per_id:
+        raise ValueError(f"rstnet_amd.ops: {rows} rows are not {ids.numel()} ids x rows_per_id = {rows_per_id}")
+    return ids.numel()
+
+
+@_on_tensor_device
+def lora_bank_shrink(x: torch.Tensor, A_bank: torch.Tensor, ids: torch.Tensor, *, rows_per_id: int = 1, prologue: int = PROLOGUE_NONE,
+                     alpha: Optional[torch.Tensor] = None, eps: float = 1e-8, post_scale: float = 1.0) -> torch.Tensor:
+    """``a[row] = post_scale * A_bank[ids[row // rows_per_id]] @ P(x[row])`` (rst_lora_bank_shrink_f32): ``x`` fp32 ``[rows, K]``
+    (``[rows, 2K]`` for the SiLU-gate prologue), ``A_bank`` bf16 ``[n_adapters, r, K]``, ``ids`` int32 ``[rows / rows_per_id]`` on the
+    device -> fp32 ``[rows, r]``.  A row whose id is not in ``[0, n_adapters)`` gets zeros.  One summation schedule per element,
+    independent of the batch: a row's result does not depend on what it is batched with."""
+    _chk(x, "x")
+    _chk(A_bank, "A_bank", torch.bfloat16)
+    _chk(alpha, "alpha")
+    assert x.dim() == 2 and A_bank.dim() == 3, (tuple(x.shape), tuple(A_bank.shape))
+    rows = x.shape[0]
+    n_ad, r, K = A_bank.shape
+    assert x.shape[1] == (2 * K if prologue == PROLOGUE_SILU_GATE else K), (tuple(x.shape), tuple(A_bank.shape), prologue)
+    assert alpha is None or alpha.numel() == K, (tuple(alpha.shape), K)
+    n_ids = _bank_ids(ids, rows, rows_per_id)
+    a = torch.empty(rows, r, device=x.device, dtype=torch.float32)
+    with _profiled("lora_bank_shrink", 2.0 * rows * r * K, 2 * min(rows, n_ad) * r * K + 4 * (x.numel() + a.numel()), (rows, r, K)):
+        _lib.check(_lib.lib().rst_lora_bank_shrink_f32(_ptr(x), _ptr(alpha), _ptr(A_bank), _ptr(ids), _ptr(a), rows, rows_per_id, n_ids, n_ad,
+                                                      r, K, x.shape[1], prologue, eps, post_scale, _stream()))
+    return a
+
+
+@_on_tensor_device
+def lora_bank_expand(a: torch.Tensor, B_bank: torch.Tensor, ids: torch.Tensor, y: torch.Tensor, *, rows_per_id: int = 1) -> torch.Tensor:
+    """``y[row] += B_bank[ids[row // rows_per_id]] @ a[row]`` IN PLACE (rst_lora_bank_expand_f32): ``a`` fp32 ``[rows, r]``, ``B_bank``
+    bf16 ``[n_adapters, N, r]``, ``y`` fp32 ``[rows, N]``; returns ``y``.  A row whose id is not in ``[0, n_adapters)`` keeps its bits."""
+    _chk(a, "a")
+    _chk(B_bank, "B_bank", torch.bfloat16)
+    _chk(y, "y")
+    assert a.dim() == 2 and B_bank.dim() == 3 and y.dim() == 2, (tuple(a.shape), tuple(B_bank.shape), tuple(y.shape))
+    rows = a.shape[0]
+    n_ad, N, r = B_bank.shape
+    assert a.shape[1] == r and tuple(y.shape) == (rows, N), (tuple(a.shape), tuple(B_bank.shape), tuple(y.shape))
+    n_ids = _bank_ids(ids, rows, rows_per_id)
+    with _profiled("lora_bank_expand", 2.0 * rows * r * N, 2 * min(rows, n_ad) * r * N + 4 * (a.numel() + 2 * y.numel()), (rows, N, r)):
+        _lib.check(_lib.lib().rst_lora_bank_expand_f32(_ptr(a), _ptr(B_bank), _ptr(ids), _ptr(y), rows, rows_per_id, n_ids, n_ad, N, r, N,
+                                                      _stream()))
+    return y
+
+
 @_on_tensor_device
 def embed_sum(tokens: torch.Tensor, tables: Sequence[torch.Tensor], tok_index: Sequence[int],
               add: Optional[torch.Tensor] = None) -> torch.Tensor:
