@@ -455,6 +455,15 @@ int rst_depth_decode_frame(const uint16_t* const* in_proj, const uint16_t* const
                            uint32_t* status, int B, int E, int H, int Hd, int card, int dep_q, int L, int ld_h, int tok_stride,
                            int noise_stride, int top_k, int use_sampling, float temp, float eps, int context, int ring_cap,
                            rst_stream_t stream);
+/* The same with one row of id limits per stream: v_limit_dev is a device int [B][v_limit_stride >= dep_q] and step k of row b never
+ * draws ids >= v_limit_dev[b * v_limit_stride + k].  v_limit_stride == 0 is rst_depth_decode_frame, which forwards here. */
+int rst_depth_decode_frame_rows(const uint16_t* const* in_proj, const uint16_t* const* out_proj, const float* const* norm1,
+                                const float* const* norm2, const uint16_t* const* gate_in, const uint16_t* const* gate_out,
+                                const uint16_t* const* heads, const float* const* head_bias, const uint16_t* const* emb, const int* emb_rows,
+                                const float* h_all, int64_t* tokens, const float* noise, const int* v_limit_dev, int v_limit_stride,
+                                void* workspace, uint32_t* status, int B, int E, int H, int Hd, int card, int dep_q, int L, int ld_h,
+                                int tok_stride, int noise_stride, int top_k, int use_sampling, float temp, float eps, int context,
+                                int ring_cap, rst_stream_t stream);
 
 /* rst_temporal_decode_frame -- ALL layers of the temporal transformer of one batch-1 LM step as ONE persistent launch:
  * LMModel.forward_text's `self.transformer(input_)` at T = 1 in streaming mode (models/model.py:364-389), i.e. L x
@@ -647,6 +656,33 @@ int rst_lm_attn_prefill_gqa_f32(const float* qkv, const void* k, const void* v, 
 int rst_lm_ring_append_gqa(const float* qkv, void* k, void* v, const int64_t* pos_dev, int B, int Tc, int H, int G, int D, int cap, int ldqkv,
                            int rope, float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream);
 
+/* Per-stream ring positions: the ring calls of the GPT global transformer with ONE POSITION PER STREAM, so that a batch can hold streams
+ * that have consumed different numbers of positions.  pos_dev is int64 and stream b reads pos_dev[b * pos_stride]; pos_stride is 0 (one
+ * shared word: the launches, values and bytes of the calls above, which forward here with 0) or 1 (int64 [B]).  The load is one
+ * unconditional scalar load per workgroup either way.  A stream at position p gets exactly the arithmetic the shared-position call gives
+ * at p: no padding, no shifted positions.
+ *   rst_lm_rope_table_ps_f32: B tables, table [B][D/2][2], table b at position pos_dev[b].
+ *   rst_lm_attn_decode_ps_f32: rst_lm_attn_decode_f32 with stream b's step at position pos_dev[b * pos_stride] (short- and long-ring form);
+ *     with pos_stride == 1, rope_table (optional) is the [B][D/2][2] table of rst_lm_rope_table_ps_f32 and stream b reads table b.
+ *   rst_lm_attn_prefill_ps_f32: rst_lm_attn_prefill_gqa_f32 with the chunk of stream b starting at position pos_dev[b * pos_stride].
+ *     It takes no lengths: a query t only sees chunk keys u <= t, so the rows of a stream that lie below its length never read a
+ *     row past it; the outputs of rows past the length are unspecified, their reads and writes in bounds.
+ *   rst_lm_ring_append_ps: rst_lm_ring_append_gqa at per-stream positions and, with lengths (optional, device int32 [B]) and the offset t0
+ *     of this chunk inside the call the lengths count from, PER-STREAM LENGTHS: stream b appends rows t < clamp(lengths[b] - t0, 0, Tc)
+ *     and no ring slot of a row past that is written; a length of 0 takes nothing from the call.  The caller advances its positions
+ *     by the same clamp. */
+int rst_lm_rope_table_ps_f32(const int64_t* pos_dev, float* table, int B, int D, int rope_dims, float rope_coef, rst_stream_t stream);
+int rst_lm_attn_decode_ps_f32(const float* qkv, void* k, void* v, float* ws, uint32_t* counters, float* out,
+                              const int64_t* pos_dev, int pos_stride, int B, int H, int D, int cap, int context, int splits, int ldqkv,
+                              int rope, float rope_coef, int kv_heads, int rope_dims, uint16_t* out_packed, int kv_bf16,
+                              const float* rope_table, rst_stream_t stream);
+int rst_lm_attn_prefill_ps_f32(const float* qkv, const void* k, const void* v, void* workspace, int64_t workspace_bytes, float* out,
+                               const int64_t* pos_dev, int pos_stride, int B, int Tc, int H, int G, int D, int cap, int window, int ldqkv,
+                               int rope, float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream);
+int rst_lm_ring_append_ps(const float* qkv, void* k, void* v, const int64_t* pos_dev, int pos_stride, const int32_t* lengths, int t0, int B,
+                          int Tc, int H, int G, int D, int cap, int ldqkv, int rope, float rope_coef, int rope_dims, int kv_bf16,
+                          const float* rope_freqs, rst_stream_t stream);
+
 /* The few-query form of rst_attention_f32(ring = 1) for streaming steps of the codec transformers (T <= a few new steps per
  * call): q [B][H][T][D] already rotated and k / v already appended by rst_rope_split_f32; every (b, t, h) query is split
  * over the occupied ring slots like rst_lm_attn_decode_f32 (same mask / slot map with end_offset = *pos_dev + T).
@@ -684,6 +720,11 @@ int rst_lm_sample_workspace_bytes(int B, int V, int top_k, int top_p_mode);
 int rst_lm_sample_f32(const float* logits, const float* noise, int64_t* tokens, int B, int V, int ld, int top_k,
                       int noise_stride, int tok_stride, int use_sampling, float temp, int v_limit, const int32_t* v_limit_dev,
                       float top_p, void* workspace, int64_t workspace_bytes, rst_stream_t stream);
+/* The same with one id limit per row: row b reads v_limit_dev[b * v_limit_stride] (int32 elements; a column of a [B][n] table has stride
+ * n).  v_limit_stride == 0 is rst_lm_sample_f32, which forwards here. */
+int rst_lm_sample_rows_f32(const float* logits, const float* noise, int64_t* tokens, int B, int V, int ld, int top_k,
+                           int noise_stride, int tok_stride, int use_sampling, float temp, int v_limit, const int32_t* v_limit_dev,
+                           int v_limit_stride, float top_p, void* workspace, int64_t workspace_bytes, rst_stream_t stream);
 
 /* LMGen.step's token ring and delay pattern (models/model.py:506-562) on the device.  cache int64 [B][K][CT] (CT = max_delay
  * + 2), delays int32 [K] and the frame counter offset_dev (int64 scalar) stay in HBM, so that a frame is one captured graph.

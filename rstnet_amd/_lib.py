@@ -80,6 +80,7 @@ SIGNATURES = {
     "rst_depth_frame_workspace_bytes": [_i, _i, _i, _i],
     "rst_depth_frame_supported": [_i, _i, _i, _i, _i, _i, _i, _i],
     "rst_depth_decode_frame": [C.POINTER(_p)] * 9 + [C.POINTER(_i), _p, _p, _p, _p, _p, _p] + [_i] * 12 + [_f, _f, _i, _i, _p],
+    "rst_depth_decode_frame_rows": [C.POINTER(_p)] * 9 + [C.POINTER(_i), _p, _p, _p, _p, _i, _p, _p] + [_i] * 12 + [_f, _f, _i, _i, _p],
     "rst_temporal_frame_workspace_bytes": [_i, _i, _i],
     "rst_temporal_frame_supported": [_i, _i, _i, _i, _i, _i],
     "rst_temporal_decode_frame": [_p] * 7 + [_i] * 7 + [_f, _p],
@@ -108,11 +109,16 @@ SIGNATURES = {
     "rst_lm_attn_prefill_gqa_workspace_bytes": [_i, _i, _i, _i, _i, _i],
     "rst_lm_attn_prefill_gqa_f32": [_p, _p, _p, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _p],
     "rst_lm_ring_append_gqa": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _p],
+    "rst_lm_rope_table_ps_f32": [_p, _p, _i, _i, _i, _f, _p],
+    "rst_lm_attn_decode_ps_f32": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _i, _p, _p],
+    "rst_lm_attn_prefill_ps_f32": [_p, _p, _p, _p, _l, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _p],
+    "rst_lm_ring_append_ps": [_p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _p],
     "rst_attn_decode_multi_f32":[_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "rst_attention_step_supported": [_i, _i, _i],
     "rst_attention_step_f32": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p],
     "rst_lm_sample_workspace_bytes": [_i, _i, _i, _i],
     "rst_lm_sample_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p, _f, _p, _l, _p],
+    "rst_lm_sample_rows_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p, _i, _f, _p, _l, _p],
     "rst_lm_ring_begin_i64": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "rst_lm_ring_commit_i64": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
 }

@@ -24,7 +24,7 @@ int rst_check_launch(const char* what) {
 
 extern "C" {
 
-int rst_version(void) { return 127; }      // 127: + rst_lora_bank_shrink_f32, rst_lora_bank_expand_f32, rst_lora_bank_supported (per-row LoRA adapters from a device-resident bank); 126: + rst_resample_sinc, rst_resample_plan (sample-rate conversion of ragged batches and streams); 125: + rst_skinny_pack_weight_mxfp4w, rst_gemm_skinny_mxfp4w_f32 / _supported (MXFP4 weight-only skinny GEMM); 124: + rst_skinny_pack_weight_fp8w, rst_gemm_skinny_fp8w_f32 / _supported (fp8 weight-only skinny GEMM); 123: + rst_quant_blocks_mxfp4, rst_gemv_mxfp4w_f32 / _supported (MXFP4 weight-only GEMV); 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
+int rst_version(void) { return 128; }      // 128: + rst_lm_attn_decode_ps_f32, rst_lm_rope_table_ps_f32, rst_lm_attn_prefill_ps_f32, rst_lm_ring_append_ps (per-stream ring positions, ragged append), rst_lm_sample_rows_f32, rst_depth_decode_frame_rows (per-row id limits); 127: + rst_lora_bank_shrink_f32, rst_lora_bank_expand_f32, rst_lora_bank_supported (per-row LoRA adapters from a device-resident bank); 126: + rst_resample_sinc, rst_resample_plan (sample-rate conversion of ragged batches and streams); 125: + rst_skinny_pack_weight_mxfp4w, rst_gemm_skinny_mxfp4w_f32 / _supported (MXFP4 weight-only skinny GEMM); 124: + rst_skinny_pack_weight_fp8w, rst_gemm_skinny_fp8w_f32 / _supported (fp8 weight-only skinny GEMM); 123: + rst_quant_blocks_mxfp4, rst_gemv_mxfp4w_f32 / _supported (MXFP4 weight-only GEMV); 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
                                            // rst_rvq_search_chain_f32, rst_embed_sum_bf16(add_stride); 105: round 4
 const char* rst_last_error(void) { return g_err; }
 
@@ -443,13 +443,15 @@ int rst_depth_frame_supported(int B, int E, int H, int Hd, int card, int dep_q, 
     return rst_depth_frame_grid(p);
 }
 
-int rst_depth_decode_frame(const uint16_t* const* in_proj, const uint16_t* const* out_proj, const float* const* norm1,
-                           const float* const* norm2, const uint16_t* const* gate_in, const uint16_t* const* gate_out,
-                           const uint16_t* const* heads, const float* const* head_bias, const uint16_t* const* emb, const int* emb_rows,
-                           const float* h_all, int64_t* tokens, const float* noise, const int* v_limit_dev, void* workspace,
-                           uint32_t* status, int B, int E, int H, int Hd, int card, int dep_q, int L, int ld_h, int tok_stride,
-                           int noise_stride, int top_k, int use_sampling, float temp, float eps, int context, int ring_cap,
-                           rst_stream_t stream) {
+int rst_depth_decode_frame_rows(const uint16_t* const* in_proj, const uint16_t* const* out_proj, const float* const* norm1,
+                                const float* const* norm2, const uint16_t* const* gate_in, const uint16_t* const* gate_out,
+                                const uint16_t* const* heads, const float* const* head_bias, const uint16_t* const* emb, const int* emb_rows,
+                                const float* h_all, int64_t* tokens, const float* noise, const int* v_limit_dev, int v_limit_stride,
+                                void* workspace, uint32_t* status, int B, int E, int H, int Hd, int card, int dep_q, int L, int ld_h,
+                                int tok_stride, int noise_stride, int top_k, int use_sampling, float temp, float eps, int context,
+                                int ring_cap, rst_stream_t stream) {
+    RST_REQUIRE(v_limit_stride == 0 || (v_limit_dev && v_limit_stride >= dep_q), "depth_decode_frame: limit row stride %d for %d steps",
+                v_limit_stride, dep_q);
     RST_REQUIRE(ring_cap >= dep_q, "depth_decode_frame: a ring of %d slots cannot hold the %d steps of a frame", ring_cap, dep_q);
     RST_REQUIRE(in_proj && out_proj && norm1 && norm2 && gate_in && gate_out && heads && emb && emb_rows, "depth_decode_frame: null table");
     RST_REQUIRE(L >= 1 && L <= RST_DEPTH_MAX_L && dep_q >= 1 && dep_q <= RST_DEPTH_MAX_Q, "depth_decode_frame: L=%d (<= %d), dep_q=%d (<= %d)", L,
@@ -463,12 +465,24 @@ int rst_depth_decode_frame(const uint16_t* const* in_proj, const uint16_t* const
     for (int k = 0; k < dep_q; ++k) {
         p.heads[k] = heads[k]; p.head_bias[k] = head_bias ? head_bias[k] : nullptr; p.emb[k] = emb[k]; p.emb_rows[k] = emb_rows[k];
     }
-    p.h_all = h_all; p.tokens = reinterpret_cast<long*>(tokens); p.noise = noise; p.v_limit = v_limit_dev;
+    p.h_all = h_all; p.tokens = reinterpret_cast<long*>(tokens); p.noise = noise; p.v_limit = v_limit_dev; p.v_limit_stride = v_limit_stride;
     p.gran = static_cast<unsigned long long*>(workspace); p.status = status;
     p.hist_solo = workspace ? reinterpret_cast<float*>(p.gran + 2 * rst_depth_frame_workspace_granules(B, E, Hd, card)) : nullptr;
     p.B = B; p.E = E; p.H = H; p.D = E / H; p.Hd = Hd; p.card = card; p.dep_q = dep_q; p.L = L; p.ld_h = ld_h; p.tok_stride = tok_stride;
     p.noise_stride = noise_stride; p.top_k = top_k; p.use_sampling = use_sampling; p.context = context; p.ring_cap = ring_cap; p.eps = eps; p.temp = temp;
     return rst_launch_depth_frame(p, (hipStream_t)stream);
+}
+
+int rst_depth_decode_frame(const uint16_t* const* in_proj, const uint16_t* const* out_proj, const float* const* norm1,
+                           const float* const* norm2, const uint16_t* const* gate_in, const uint16_t* const* gate_out,
+                           const uint16_t* const* heads, const float* const* head_bias, const uint16_t* const* emb, const int* emb_rows,
+                           const float* h_all, int64_t* tokens, const float* noise, const int* v_limit_dev, void* workspace,
+                           uint32_t* status, int B, int E, int H, int Hd, int card, int dep_q, int L, int ld_h, int tok_stride,
+                           int noise_stride, int top_k, int use_sampling, float temp, float eps, int context, int ring_cap,
+                           rst_stream_t stream) {
+    return rst_depth_decode_frame_rows(in_proj, out_proj, norm1, norm2, gate_in, gate_out, heads, head_bias, emb, emb_rows, h_all, tokens, noise,
+                                       v_limit_dev, 0, workspace, status, B, E, H, Hd, card, dep_q, L, ld_h, tok_stride, noise_stride, top_k,
+                                       use_sampling, temp, eps, context, ring_cap, stream);
 }
 
 int rst_temporal_frame_workspace_bytes(int E, int Hd, int H) {
@@ -641,11 +655,12 @@ int rst_lm_rope_append_f32(const float* qkv, float* q, float* k, float* v, const
     return rst_launch_lm_rope_append(p, (hipStream_t)stream);
 }
 
-int rst_lm_attn_decode_f32(const float* qkv, void* k, void* v, float* ws, uint32_t* counters, float* out,
-                           const int64_t* pos_dev, int B, int H, int D, int cap, int context, int splits, int ldqkv, int rope,
-                           float rope_coef, int kv_heads, int rope_dims, uint16_t* out_packed, int kv_bf16, const float* rope_table,
-                           rst_stream_t stream) {
-    LmAttnParams p;
+int rst_lm_attn_decode_ps_f32(const float* qkv, void* k, void* v, float* ws, uint32_t* counters, float* out,
+                              const int64_t* pos_dev, int pos_stride, int B, int H, int D, int cap, int context, int splits, int ldqkv,
+                              int rope, float rope_coef, int kv_heads, int rope_dims, uint16_t* out_packed, int kv_bf16,
+                              const float* rope_table, rst_stream_t stream) {
+    LmAttnParams p{};
+    p.pos_stride = pos_stride; p.rope_cs_stride = pos_stride ? D : 0;      // per-stream positions: one rope table per stream
     p.kv_bf16 = kv_bf16; p.rope_cs = rope && !(cap <= 64 && splits == 1) ? rope_table : nullptr;
     p.q_pre = nullptr; p.T = 1; p.G = kv_heads > 0 ? kv_heads : H; p.rope_dims = rope_dims > 0 ? rope_dims : D;
     p.out_packed = out_packed; p.out_plane = (long)((B + 31) / 32 * 32) * H * D;
@@ -655,8 +670,20 @@ int rst_lm_attn_decode_f32(const float* qkv, void* k, void* v, float* ws, uint32
     return rst_launch_lm_attn(p, (hipStream_t)stream);
 }
 
+int rst_lm_attn_decode_f32(const float* qkv, void* k, void* v, float* ws, uint32_t* counters, float* out,
+                           const int64_t* pos_dev, int B, int H, int D, int cap, int context, int splits, int ldqkv, int rope,
+                           float rope_coef, int kv_heads, int rope_dims, uint16_t* out_packed, int kv_bf16, const float* rope_table,
+                           rst_stream_t stream) {
+    return rst_lm_attn_decode_ps_f32(qkv, k, v, ws, counters, out, pos_dev, 0, B, H, D, cap, context, splits, ldqkv, rope, rope_coef, kv_heads,
+                                     rope_dims, out_packed, kv_bf16, rope_table, stream);
+}
+
 int rst_lm_rope_table_f32(const int64_t* pos_dev, float* table, int D, int rope_dims, float rope_coef, rst_stream_t stream) {
-    return rst_launch_lm_rope_table((const long*)pos_dev, table, D, rope_dims > 0 ? rope_dims : D, rope_coef, (hipStream_t)stream);
+    return rst_launch_lm_rope_table((const long*)pos_dev, 0, 1, table, D, rope_dims > 0 ? rope_dims : D, rope_coef, (hipStream_t)stream);
+}
+
+int rst_lm_rope_table_ps_f32(const int64_t* pos_dev, float* table, int B, int D, int rope_dims, float rope_coef, rst_stream_t stream) {
+    return rst_launch_lm_rope_table((const long*)pos_dev, 1, B, table, D, rope_dims > 0 ? rope_dims : D, rope_coef, (hipStream_t)stream);
 }
 
 static int lm_prefill_ws_int(int B, int Tc, int H, int G, int D, int kv_bf16) {
@@ -679,9 +706,9 @@ static LmPrefillParams lm_prefill_params(const float* qkv, void* k, void* v, con
     return p;
 }
 
-int rst_lm_attn_prefill_gqa_f32(const float* qkv, const void* k, const void* v, void* workspace, int64_t workspace_bytes, float* out,
-                                const int64_t* pos_dev, int B, int Tc, int H, int G, int D, int cap, int window, int ldqkv, int rope,
-                                float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream) {
+int rst_lm_attn_prefill_ps_f32(const float* qkv, const void* k, const void* v, void* workspace, int64_t workspace_bytes, float* out,
+                               const int64_t* pos_dev, int pos_stride, int B, int Tc, int H, int G, int D, int cap, int window, int ldqkv,
+                               int rope, float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream) {
     RST_REQUIRE(H >= 1 && G >= 1 && H % G == 0, "lm_attn_prefill: %d query heads are not a multiple of %d key/value heads", H, G);
     LmPrefillParams p = lm_prefill_params(qkv, const_cast<void*>(k), const_cast<void*>(v), pos_dev, B, Tc, H, G, D, cap, ldqkv, rope, rope_coef,
                                           rope_dims, kv_bf16, rope_freqs);
@@ -689,11 +716,18 @@ int rst_lm_attn_prefill_gqa_f32(const float* qkv, const void* k, const void* v, 
     RST_REQUIRE(need > 0 && workspace && workspace_bytes >= need && (uintptr_t)workspace % 16 == 0,
                 "lm_attn_prefill: workspace of %ld bytes (16-byte aligned) needed, got %ld", need, (long)workspace_bytes);
     const long nq = (long)B * Tc * H * D, nk = (long)B * Tc * G * D;
-    p.out = out; p.window = window;
+    p.out = out; p.window = window; p.pos_stride = pos_stride;
     p.q_rot = static_cast<float*>(workspace);
     p.k_new = static_cast<char*>(workspace) + nq * 4;
     p.v_new = static_cast<char*>(workspace) + nq * 4 + nk * (kv_bf16 ? 2 : 4);
     return rst_launch_lm_attn_prefill(p, (hipStream_t)stream);
+}
+
+int rst_lm_attn_prefill_gqa_f32(const float* qkv, const void* k, const void* v, void* workspace, int64_t workspace_bytes, float* out,
+                                const int64_t* pos_dev, int B, int Tc, int H, int G, int D, int cap, int window, int ldqkv, int rope,
+                                float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream) {
+    return rst_lm_attn_prefill_ps_f32(qkv, k, v, workspace, workspace_bytes, out, pos_dev, 0, B, Tc, H, G, D, cap, window, ldqkv, rope, rope_coef,
+                                      rope_dims, kv_bf16, rope_freqs, stream);
 }
 
 int rst_lm_attn_prefill_f32(const float* qkv, const void* k, const void* v, void* workspace, int64_t workspace_bytes, float* out,
@@ -703,10 +737,18 @@ int rst_lm_attn_prefill_f32(const float* qkv, const void* k, const void* v, void
                                        rope_dims, kv_bf16, rope_freqs, stream);
 }
 
+int rst_lm_ring_append_ps(const float* qkv, void* k, void* v, const int64_t* pos_dev, int pos_stride, const int32_t* lengths, int t0, int B,
+                          int Tc, int H, int G, int D, int cap, int ldqkv, int rope, float rope_coef, int rope_dims, int kv_bf16,
+                          const float* rope_freqs, rst_stream_t stream) {
+    LmPrefillParams p = lm_prefill_params(qkv, k, v, pos_dev, B, Tc, H, G, D, cap, ldqkv, rope, rope_coef, rope_dims, kv_bf16, rope_freqs);
+    p.pos_stride = pos_stride; p.lengths = lengths; p.t0 = t0;
+    return rst_launch_lm_ring_append(p, (hipStream_t)stream);
+}
+
 int rst_lm_ring_append_gqa(const float* qkv, void* k, void* v, const int64_t* pos_dev, int B, int Tc, int H, int G, int D, int cap, int ldqkv,
                            int rope, float rope_coef, int rope_dims, int kv_bf16, const float* rope_freqs, rst_stream_t stream) {
-    const LmPrefillParams p = lm_prefill_params(qkv, k, v, pos_dev, B, Tc, H, G, D, cap, ldqkv, rope, rope_coef, rope_dims, kv_bf16, rope_freqs);
-    return rst_launch_lm_ring_append(p, (hipStream_t)stream);
+    return rst_lm_ring_append_ps(qkv, k, v, pos_dev, 0, nullptr, 0, B, Tc, H, G, D, cap, ldqkv, rope, rope_coef, rope_dims, kv_bf16, rope_freqs,
+                                 stream);
 }
 
 int rst_lm_ring_append(const float* qkv, void* k, void* v, const int64_t* pos_dev, int B, int Tc, int H, int D, int cap, int ldqkv, int rope,
@@ -717,7 +759,7 @@ int rst_lm_ring_append(const float* qkv, void* k, void* v, const int64_t* pos_de
 int rst_attn_decode_multi_f32(const float* q, const float* k, const float* v, float* ws, uint32_t* counters, float* out,
                               const int64_t* pos_dev, int B, int T, int H, int D, int cap, int context, int splits,
                               int kv_heads, rst_stream_t stream) {
-    LmAttnParams p;
+    LmAttnParams p{};
     p.kv_bf16 = 0; p.rope_cs = nullptr;
     p.G = kv_heads > 0 ? kv_heads : H; p.rope_dims = D; p.out_packed = nullptr; p.out_plane = 0;
     p.qkv = nullptr; p.q_pre = q; p.T = T; p.k = const_cast<float*>(k); p.v = const_cast<float*>(v); p.ws = ws; p.counters = counters;
@@ -731,14 +773,22 @@ int rst_lm_sample_workspace_bytes(int B, int V, int top_k, int top_p_mode) {
     return n > 0x7fffffffL ? -1 : (int)n;
 }
 
-int rst_lm_sample_f32(const float* logits, const float* noise, int64_t* tokens, int B, int V, int ld, int top_k,
-                      int noise_stride, int tok_stride, int use_sampling, float temp, int v_limit, const int32_t* v_limit_dev,
-                      float top_p, void* workspace, int64_t workspace_bytes, rst_stream_t stream) {
-    LmSampleParams p;
-    p.v_limit = v_limit; p.v_limit_dev = v_limit_dev; p.top_p = top_p; p.ws = workspace; p.ws_bytes = workspace ? workspace_bytes : 0;
+int rst_lm_sample_rows_f32(const float* logits, const float* noise, int64_t* tokens, int B, int V, int ld, int top_k,
+                           int noise_stride, int tok_stride, int use_sampling, float temp, int v_limit, const int32_t* v_limit_dev,
+                           int v_limit_stride, float top_p, void* workspace, int64_t workspace_bytes, rst_stream_t stream) {
+    RST_REQUIRE(v_limit_stride >= 0 && (v_limit_stride == 0 || v_limit_dev), "lm_sample: limit row stride %d", v_limit_stride);
+    LmSampleParams p{};
+    p.v_limit = v_limit; p.v_limit_dev = v_limit_dev; p.v_limit_stride = v_limit_stride; p.top_p = top_p; p.ws = workspace; p.ws_bytes = workspace ? workspace_bytes : 0;
     p.logits = logits; p.noise = noise; p.tokens = (long*)tokens; p.B = B; p.V = V; p.ld = ld; p.top_k = top_k;
     p.noise_stride = noise_stride; p.tok_stride = tok_stride; p.use_sampling = use_sampling; p.temp = temp;
     return rst_launch_lm_sample(p, (hipStream_t)stream);
+}
+
+int rst_lm_sample_f32(const float* logits, const float* noise, int64_t* tokens, int B, int V, int ld, int top_k,
+                      int noise_stride, int tok_stride, int use_sampling, float temp, int v_limit, const int32_t* v_limit_dev,
+                      float top_p, void* workspace, int64_t workspace_bytes, rst_stream_t stream) {
+    return rst_lm_sample_rows_f32(logits, noise, tokens, B, V, ld, top_k, noise_stride, tok_stride, use_sampling, temp, v_limit, v_limit_dev, 0,
+                                  top_p, workspace, workspace_bytes, stream);
 }
 
 int rst_lm_ring_begin_i64(int64_t* cache, const int64_t* user_tokens, const int64_t* initial, const int32_t* delays,

@@ -109,7 +109,7 @@ __device__ __forceinline__ void attn_decode_body(const LmAttnParams& p) {
     const int T = p.q_pre ? p.T : 1;
     const long b = blockIdx.z / T;
     const int tq = blockIdx.z % T;
-    const long pos = *p.pos_dev;                 // position of the first new step
+    const long pos = p.pos_dev[b * p.pos_stride];   // position of the first new step (one unconditional scalar load; stride 0: shared)
     const long pos_q = pos + tq;                 // position of this query
     const long end_offset = pos + T;             // RingKVCache.end_offset after the append of all T new steps
     const int slot_cur = p.q_pre ? -1 : (int)(pos % p.cap);   // fused mode: the slot this launch appends
@@ -122,7 +122,7 @@ __device__ __forceinline__ void attn_decode_body(const LmAttnParams& p) {
     // launch skips 24 libm calls per lane: at short context they were most of its duration)
     float rc[8], rs[8];
     if (p.rope_cs) {
-        const f32x4* t4 = reinterpret_cast<const f32x4*>(p.rope_cs + sub * 16);
+        const f32x4* t4 = reinterpret_cast<const f32x4*>(p.rope_cs + b * p.rope_cs_stride + sub * 16);
         const f32x4 t0 = t4[0], t1 = t4[1], t2 = t4[2], t3 = t4[3];
         rc[0] = t0[0]; rs[0] = t0[1]; rc[1] = t0[2]; rs[1] = t0[3]; rc[2] = t1[0]; rs[2] = t1[1]; rc[3] = t1[2]; rs[3] = t1[3];
         rc[4] = t2[0]; rs[4] = t2[1]; rc[5] = t2[2]; rs[5] = t2[3]; rc[6] = t3[0]; rs[6] = t3[1]; rc[7] = t3[2]; rs[7] = t3[3];
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(64) void attn_small_kernel(const LmAttnParams p) {
         *reinterpret_cast<f32x4*>(kn + i) = *reinterpret_cast<const f32x4*>(knp + i);
         *reinterpret_cast<f32x4*>(vn + i) = *reinterpret_cast<const f32x4*>(vnp + i);
     }
-    const long pos = *p.pos_dev;
+    const long pos = p.pos_dev[b * p.pos_stride];
     const int slot_cur = (int)(pos % cap);
     if (p.rope) {
 #pragma unroll
@@ -470,12 +470,14 @@ int rst_launch_lm_rope_append(const LmRopeAppendParams& p, hipStream_t stream) {
 }
 
 namespace {
-__global__ __launch_bounds__(128) void rope_table_kernel(const long* pos_dev, float* out, int D, int rope_dims, float rope_coef) {
+__global__ __launch_bounds__(128) void rope_table_kernel(const long* pos_dev, long pos_stride, float* out, int D, int rope_dims, float rope_coef) {
     const int i = threadIdx.x;
     if (i >= D / 2) return;
+    const long b = blockIdx.x;               // one table per workgroup: stream b at pos_dev[b * pos_stride]
+    out += b * D;
     float c = 1.f, s = 0.f;
     if (2 * i < rope_dims) {
-        const float ang = expf((float)i * rope_coef) * (float)*pos_dev;
+        const float ang = expf((float)i * rope_coef) * (float)pos_dev[b * pos_stride];
         c = cosf(ang); s = sinf(ang);
     }
     out[2 * i] = c;
@@ -483,9 +485,10 @@ __global__ __launch_bounds__(128) void rope_table_kernel(const long* pos_dev, fl
 }
 }  // namespace
 
-int rst_launch_lm_rope_table(const long* pos_dev, float* out, int D, int rope_dims, float rope_coef, hipStream_t stream) {
+int rst_launch_lm_rope_table(const long* pos_dev, long pos_stride, int B, float* out, int D, int rope_dims, float rope_coef, hipStream_t stream) {
+    RST_REQUIRE(B >= 1 && B <= 65535 && (pos_stride == 0 || pos_stride == 1), "lm_rope_table: %d tables at position stride %ld", B, pos_stride);
     RST_REQUIRE(pos_dev && out && D >= 2 && D <= 256 && D % 2 == 0 && rope_dims >= 0 && rope_dims <= D, "lm_rope_table: bad arguments (D=%d rope_dims=%d)", D, rope_dims);
-    hipLaunchKernelGGL(rope_table_kernel, dim3(1), dim3(128), 0, stream, pos_dev, out, D, rope_dims, rope_coef);
+    hipLaunchKernelGGL(rope_table_kernel, dim3(B), dim3(128), 0, stream, pos_dev, pos_stride, out, D, rope_dims, rope_coef);
     return rst_check_launch("lm_rope_table");
 }
 
@@ -499,6 +502,8 @@ int rst_launch_lm_attn(const LmAttnParams& p, hipStream_t stream) {
                 "lm_attn: bad kv head count %d for %d heads or rope_dims %d", p.G, p.H, p.rope_dims);
     RST_REQUIRE(!p.kv_bf16 || (!p.q_pre && !(p.cap <= 64 && p.splits == 1)), "lm_attn: bf16 rings are served by the long-ring single-step form only");
     RST_REQUIRE(!p.rope_cs || (uintptr_t)p.rope_cs % 16 == 0, "lm_attn: the rope table must be 16-byte aligned");
+    RST_REQUIRE((p.pos_stride == 0 || (p.pos_stride == 1 && !p.q_pre)) && (p.rope_cs_stride == 0 || p.rope_cs_stride == p.D),
+                "lm_attn: position stride %ld (0, or 1 on the single-step form) / rope table stride %ld (0 or D)", p.pos_stride, p.rope_cs_stride);
     if (!p.q_pre && p.cap <= 64 && p.splits == 1) {
         switch (p.D) {
             case 32: hipLaunchKernelGGL(attn_small_kernel<32>, dim3(p.H, p.B), dim3(64), 0, stream, p); break;

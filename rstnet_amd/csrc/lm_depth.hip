@@ -357,7 +357,7 @@ __global__ __launch_bounds__(DF_THREADS) void depth_frame_kernel(const DepthFram
             DF_STAMP(sk + 2 + DF_ST_LAYER * RST_DEPTH_MAX_L);
             for (int b = b_lo; b < b_hi; ++b) {
                 const float* nz = p.noise ? p.noise + (long)b * p.noise_stride + (long)k * p.top_k : nullptr;
-                const int limit = p.v_limit ? p.v_limit[k] : 0;
+                const int limit = p.v_limit ? p.v_limit[(long)b * p.v_limit_stride + k] : 0;
 #ifdef RST_ABLATION
                 unsigned long long* sdbg = SOLO || b ? nullptr : df_lds_stamps + sk + 4 + DF_ST_LAYER * RST_DEPTH_MAX_L;
 #else

@@ -51,13 +51,14 @@ __global__ __launch_bounds__(256) void stage_kernel(const LmPrefillParams p, con
     const int half = p.D / 2;
     const int nh = to_ring ? p.G : p.H + p.G;
     const long total = (long)p.B * p.T * nh * half;
-    const long pos0 = *p.pos_dev;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const int i = (int)(idx % half);
         const int hh = (int)((idx / half) % nh) + (to_ring ? p.H : 0);
         const int t = (int)((idx / ((long)half * nh)) % p.T);
         const long b = idx / ((long)half * nh * p.T);
-        const long pos = pos0 + t;
+        const long pos = p.pos_dev[b * p.pos_stride] + t;      // (stride 0: every lane reads the one shared word)
+        // ragged append: rows at or past the stream's length leave their ring slots as they are (a length <= t0 takes nothing)
+        if (to_ring && p.lengths && t >= p.lengths[b] - p.t0) continue;
         const float* row = p.qkv + (b * p.T + t) * (long)p.ldqkv;
         float c = 1.f, s = 0.f;
         if (p.rope && 2 * i < p.rope_dims) {
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(64) void prefill_attn_f32_kernel(const LmPrefillPar
     __shared__ __attribute__((aligned(16))) float sm_q[D];
     const int lane = threadIdx.x, t = blockIdx.x, h = blockIdx.y;
     const long b = blockIdx.z;
-    const long pos = *p.pos_dev;
+    const long pos = p.pos_dev[b * p.pos_stride];
     const int pos_mod = (int)(pos % p.cap);
     const int u_min = -(int)min(pos, (long)p.cap);
     const int u_lo = max(t - p.window + 1, u_min);
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(256) void prefill_attn_bf16_kernel(const LmPrefillP
     const int r = lane & 31, hf = lane >> 5;
     const int t0 = blockIdx.x * 32, h = blockIdx.y;
     const long b = blockIdx.z;
-    const long pos = *p.pos_dev;
+    const long pos = p.pos_dev[b * p.pos_stride];
     const int pos_mod = (int)(pos % p.cap);
     const int u_min = -(int)min(pos, (long)p.cap);
     const int t_last = min(t0 + 31, p.T - 1);
@@ -330,6 +331,8 @@ int prefill_check(const LmPrefillParams& p, const char* what, bool attention) {
     RST_REQUIRE(p.ldqkv >= (p.H + 2 * p.G) * p.D && p.ldqkv % 2 == 0, "%s: qkv row of %d floats for %d + 2 x %d heads of dim %d", what, p.ldqkv,
                 p.H, p.G, p.D);
     RST_REQUIRE(p.rope_dims >= 0 && p.rope_dims <= p.D && p.rope_dims % 2 == 0, "%s: bad rope_dims %d", what, p.rope_dims);
+    RST_REQUIRE(p.pos_stride == 0 || p.pos_stride == 1, "%s: position stride %ld (0: shared, 1: one per stream)", what, p.pos_stride);
+    RST_REQUIRE(!p.lengths || (!attention && p.t0 >= 0), "%s: lengths belong to the append, with a chunk offset >= 0", what);
     if (attention) {
         RST_REQUIRE(p.out && p.q_rot && p.k_new && p.v_new, "%s: null output or workspace", what);
         RST_REQUIRE(p.window >= 1 && p.window <= p.cap, "%s: window %d for a ring of capacity %d", what, p.window, p.cap);

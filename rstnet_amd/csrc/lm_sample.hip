@@ -17,7 +17,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const LmSampleParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long comp[];   // [k rounded up to 8] candidates
     __shared__ SampleShared<NT> sh;
     const long b = blockIdx.x;
-    const int limit = p.v_limit_dev ? *p.v_limit_dev : p.v_limit;
+    const int limit = p.v_limit_dev ? p.v_limit_dev[b * p.v_limit_stride] : p.v_limit;
     const int tok = sample_row<NT, EPT>(p.logits + b * p.ld, p.noise ? p.noise + b * p.noise_stride : nullptr, p.V, p.top_k,
                                         p.use_sampling && p.temp > 0.f, p.temp, limit, comp, sh);
     if (threadIdx.x == 0) p.tokens[b * p.tok_stride] = tok;
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(1024) void sample_big_kernel(const LmSampleParams p
         ++slot;
         return t;
     };
-    int limit = p.v_limit_dev ? *p.v_limit_dev : p.v_limit;
+    int limit = p.v_limit_dev ? p.v_limit_dev[b * p.v_limit_stride] : p.v_limit;
     limit = limit > 0 && limit < V ? limit : V;
     if (tid == 0) n_cand = 0;
 
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(SPLIT_NT) void sample_split_kernel(const LmSamplePa
     const int c = blockIdx.x, tid = threadIdx.x;
     const long b = blockIdx.y;
     const int id0 = c * SPLIT_CHUNK, Vc = min(SPLIT_CHUNK, p.V - id0);
-    int limit = p.v_limit_dev ? *p.v_limit_dev : p.v_limit;
+    int limit = p.v_limit_dev ? p.v_limit_dev[b * p.v_limit_stride] : p.v_limit;
     limit = limit > 0 && limit < p.V ? limit : p.V;
     SampleChunk ch;
     sample_row<SPLIT_NT, SPLIT_EPT, true>(p.logits + b * p.ld + id0, nullptr, Vc, kc, p.use_sampling && p.temp > 0.f, p.temp,
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void sample_merge_kernel(const LmSampleParams 
         return;
     }
     const float mx = s_mx, denom = s_denom;
-    int limit = p.v_limit_dev ? *p.v_limit_dev : p.v_limit;
+    int limit = p.v_limit_dev ? p.v_limit_dev[b * p.v_limit_stride] : p.v_limit;
     limit = limit > 0 && limit < p.V ? limit : p.V;
     const int k = min(p.top_k > 0 ? p.top_k : p.V, limit);
     float win = -INFINITY;
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(1024) void sample_top_p_kernel(const LmSampleParams
     unsigned long long* a = reinterpret_cast<unsigned long long*>(p.ws) + b * vpad;
     auto to_key = [](float f) { unsigned u = __float_as_uint(f + 0.0f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); };
     auto from_key = [](unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); };
-    int limit = p.v_limit_dev ? *p.v_limit_dev : p.v_limit;
+    int limit = p.v_limit_dev ? p.v_limit_dev[b * p.v_limit_stride] : p.v_limit;
     limit = limit > 0 && limit < V ? limit : V;
     // (1) keys, row maximum, composites (ids that may not be drawn and the padding sort last: composite 0)
     unsigned bk = 0u;

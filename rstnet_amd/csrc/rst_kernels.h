@@ -295,17 +295,20 @@ struct LmAttnParams {
     float* out;           // [B][H*D]
     unsigned short* out_packed;   // optional instead of out: bf16 hi / lo planes in skinny-GEMM operand order, K = H*D (T = 1 only)
     long out_plane;       // elements per plane of out_packed (= ceil(B/32)*32 * H*D); pad rows are never written
-    const long* pos_dev;  // position of the new step
+    const long* pos_dev;  // position of the new step: stream b reads pos_dev[b * pos_stride]
+    long pos_stride;      // 0: one position for every stream (a device scalar); 1: one per stream, int64 [B]
     int B, H, D, cap, context, splits, ldqkv, rope;
     float rope_coef;
     int G;                // key/value heads (grouped-query attention: query head h reads kv head h / (H/G)); G == H for MHA
     int rope_dims;        // leading head dims that rotate (pairs (2i, 2i+1), i < rope_dims/2); D = all
     const float* rope_cs; // optional [D/2][2] (cos, sin) of this step's rotation (rst_launch_lm_rope_table): replaces the in-kernel trig
+    long rope_cs_stride;  // floats between the tables of consecutive streams: 0 (one table) or D (one per stream, per-stream positions)
 };
 int rst_launch_lm_attn(const LmAttnParams& p, hipStream_t stream);
 // (cos, sin) of angle_i = exp(i * rope_coef) * pos for i < D/2 (identity beyond rope_dims/2): the rotation of ONE step, computed once
-// per frame with the arithmetic of the attention kernels and read by every layer's launch
-int rst_launch_lm_rope_table(const long* pos_dev, float* out, int D, int rope_dims, float rope_coef, hipStream_t stream);
+// per frame with the arithmetic of the attention kernels and read by every layer's launch.  B tables [B][D/2][2], table b at position
+// pos_dev[b * pos_stride]
+int rst_launch_lm_rope_table(const long* pos_dev, long pos_stride, int B, float* out, int D, int rope_dims, float rope_coef, hipStream_t stream);
 
 // Multi-position (prefill) attention and the append that follows it (lm_prefill.hip)
 struct LmPrefillParams {
@@ -313,7 +316,10 @@ struct LmPrefillParams {
     void* k;              // [B][G][cap][D] ring: fp32, or bf16 when kv_bf16 (read by the attention, written by the append)
     void* v;
     int kv_bf16;
-    const long* pos_dev;  // position of the chunk's first row (== positions already appended)
+    const long* pos_dev;  // position of the chunk's first row (== positions already appended): stream b reads pos_dev[b * pos_stride]
+    long pos_stride;      // 0: one position for every stream; 1: int64 [B]
+    const int* lengths;   // append only, optional int32 [B]: stream b appends rows t < clamp(lengths[b] - t0, 0, T) and writes no other slot
+    int t0;               // offset of this chunk inside the call `lengths` counts from
     float* out;           // [B*T][H*D]
     float* q_rot;         // workspace: [B][H][T][D] rotated queries
     void* k_new;          // workspace: [B][G][T][D] the chunk's rotated keys in the ring's dtype
@@ -334,7 +340,8 @@ struct LmSampleParams {
     int B, V, ld, top_k, noise_stride, tok_stride, use_sampling;
     float temp;
     int v_limit;               // sampling only: ids >= v_limit are never drawn (probabilities blanked AFTER the softmax); 0 = V
-    const int* v_limit_dev;    // optional device scalar overriding v_limit (lets one captured graph serve changing limits)
+    const int* v_limit_dev;    // optional device value overriding v_limit (lets one captured graph serve changing limits): row b reads
+    long v_limit_stride;       // v_limit_dev[b * v_limit_stride] -- 0: one limit for every row
     float top_p;               // > 0: nucleus sampling (sample_top_p) instead of top-k; noise then holds V values per row
     void* ws;                  // scratch of rst_lm_sample_workspace_bytes_impl bytes: chunk records + candidates of the two-level form
     long ws_bytes;             // for V > 32768, the sort buffer of top_p; NULL: one-level kernels only (top_p then refused)
@@ -359,7 +366,8 @@ struct DepthFrameParams {
     const float* h_all;         // fp32 [B][ld_h]: columns [k * E, (k + 1) * E) = depformer_in[k](transformer_out)
     long* tokens;               // int64 [B][tok_stride]: column 0 = the text token (input), column k + 1 = token sampled at step k
     const float* noise;         // fp32 [B][noise_stride] Exp(1): step k uses columns [k * top_k, (k + 1) * top_k)   (sampling only)
-    const int* v_limit;         // optional device int [dep_q]: ids >= v_limit[k] are never drawn at step k
+    const int* v_limit;         // optional device int [dep_q]: ids >= v_limit[k] are never drawn at step k; with v_limit_stride != 0
+    long v_limit_stride;        // [B][v_limit_stride >= dep_q]: row b reads v_limit[b * v_limit_stride + k]
     unsigned long long* gran;   // granule workspace: 2 x rst_depth_frame_workspace_granules(B, E, Hd, card) 8-byte words (persistent + repair launch)
     float* hist_solo;           // KV history of the repair launch: RST_DEPTH_MAX_L * RST_DEPTH_MAX_Q * B * 2 * E floats
     unsigned* status;           // 4 device words: [0] time-out codes of the frame in flight (cleared by the repair launch), [1] frames

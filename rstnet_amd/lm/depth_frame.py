@@ -146,7 +146,7 @@ class DepthDecoder:
         """The whole phase IN PLACE on ``tokens`` (int64 ``[B, >= dep_q + 1]``, any row stride): column 0 holds the text token, step k embeds
         column k and samples column k + 1.  ``h`` fp32 ``[B, dim]``; ``noise``: Exp(1) draws ``[B, dep_q * top_k]`` or None (greedy); ``pos``:
         int64 ``arange(dep_q)`` on the device (the steps are positions 0 .. dep_q - 1 of a ring that restarts every frame, as constant device
-        scalars: no counter to zero and bump); ``limits`` int32 ``[dep_q]``: per-step id blanking; ``w8``: the fp8 copy of ``in_all()``.
+        scalars: no counter to zero and bump); ``limits`` int32 ``[dep_q]``: per-step id blanking, or ``[B, dep_q]``: per stream and step; ``w8``: the fp8 copy of ``in_all()``.
         ``rings``, the KV rings of the launch-per-op chain -- None: those installed on the transformer; a state: swapped in for the call; a
         callable ``B -> state``: called only if the chain runs.  ``keep``: the object whose ``tables`` attribute keeps the pointer tables
         alive (a captured frame embeds their device pointers).  ``persistent=False`` keeps the call off the one-launch route."""
@@ -176,6 +176,6 @@ class DepthDecoder:
                 logits = self.step_logits(k, tokens, k, None, h_all=h_all, pos=pos[k:k + 1], step_index=k)
                 ops.lm_sample(logits, use_sampling=use_sampling, temp=temp, top_k=top_k, out=tokens[:, k + 1],
                               noise=None if noise is None else noise[:, k * top_k:(k + 1) * top_k],
-                              limit_dev=None if limits is None else limits[k:k + 1])
+                              limit_dev=None if limits is None else (limits[k:k + 1] if limits.dim() == 1 else limits[:, k]))
         finally:
             dep._streaming_state = saved

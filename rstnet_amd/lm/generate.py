@@ -14,7 +14,7 @@ reproduces -- a ring that size never lets the `delta <= 0` slot-map quirk (SURVE
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Callable, Dict, Optional
+from typing import Callable, Dict, List, Optional, Sequence
 
 import torch
 
@@ -67,14 +67,18 @@ class GPTGen:
         self._regime = None
         self.B = 0
 
-    def begin(self, batch_size: int, kv_dtype: Optional[torch.dtype] = None, adapter_ids=None) -> None:
+    def begin(self, batch_size: int, kv_dtype: Optional[torch.dtype] = None, adapter_ids=None, per_stream: bool = False) -> None:
         """Open a session of ``batch_size`` streams.  ``kv_dtype``: precision of the global KV rings (None = the model's ``kv_dtype``).
         ``adapter_ids``: the adapter set of every stream (``GPT.set_adapter_ids``; needs ``GPT.load_adapter_bank``) -- they may change
-        during the session through ``set_adapter_ids``, the captured graphs read them from the device."""
+        during the session through ``set_adapter_ids``, the captured graphs read them from the device.  ``per_stream``: every stream keeps
+        its own ring position (int64 ``[B]`` on the device) and its own row of id limits, so ``prefill(tokens, lengths)`` takes prompts of
+        different lengths and ``reset_streams`` restarts single rows; head size 64 or 128 (refused here otherwise).  ``frame``, ``advance``,
+        ``start`` and ``step`` are the same calls on either kind of session."""
         m = self.model
         cfg, dev = m.config, m.device
         eager = self.noise is not None or dev.type != "cuda"
-        ring = m.transformer._make_state(batch_size, cfg.context + 1, kv_dtype)      # (refuses an unserved kv_dtype before anything changes)
+        # (refuses an unserved kv_dtype, or per-stream positions on an unserved head size, before anything changes)
+        ring = m.transformer._make_state(batch_size, cfg.context + 1, kv_dtype, per_stream=per_stream)
         if adapter_ids is not None:
             m.set_adapter_ids(adapter_ids)
         m._bank_rows(batch_size)      # (a loaded bank: one id per stream, in place before a step is captured)
@@ -82,7 +86,7 @@ class GPTGen:
         m.transformer._streaming_state = ring
         m._streaming_state = _GPTState(_Graphed(m._global_step, disable=eager))
         m.codecformer._streaming_state = m.codecformer._init_streaming_state(batch_size, capacity=cfg.dep_q + 1)
-        self._limits = torch.full((cfg.dep_q,), self.n_audio_codes + 1, device=dev, dtype=torch.int32)
+        self._limits = torch.full((batch_size, cfg.dep_q) if per_stream else (cfg.dep_q,), self.n_audio_codes + 1, device=dev, dtype=torch.int32)
         self._depth_pos = torch.arange(cfg.dep_q, device=dev, dtype=torch.long)
         self._depth = _Graphed(self._depth_frame, disable=eager)
         self._regime, self.B, self._eager = None, batch_size, eager
@@ -172,16 +176,47 @@ class GPTGen:
 
     def set_blanking(self, wide: list) -> None:
         """Per-codebook id limit of the next frames: n_audio_codes + 1 where ``wide`` (sample_token_audio) else n_audio_codes
-        (sample_token_audio_2048)."""
-        n = self.n_audio_codes
-        self._limits.copy_(torch.tensor([n + 1 if w else n for w in wide], dtype=torch.int32))
+        (sample_token_audio_2048).  ``wide``: ``[dep_q]`` flags for every stream, or a ``[B][dep_q]`` table with one row per stream
+        (``_limits`` is then ``[B, dep_q]``; a session that held ``[dep_q]`` limits drops its captured frames, which point at the old vector)."""
+        n, dep_q = self.n_audio_codes, self.model.config.dep_q
+        table = len(wide) > 0 and isinstance(wide[0], (list, tuple))
+        if table and (len(wide) != self.B or any(len(r) != dep_q for r in wide)):
+            raise ValueError(f"set_blanking: a per-stream table is [{self.B}][{dep_q}]")
+        if not table and len(wide) != dep_q:
+            raise ValueError(f"set_blanking: {len(wide)} flags for {dep_q} codebooks")
+        if table and self._limits.dim() == 1:
+            self._limits = self._limits.repeat(self.B, 1)
+            self._depth = _Graphed(self._depth_frame, disable=self._eager)
+            if self._fused is not None:
+                self._fused = _Graphed(self._step_fn, disable=self._eager)
+        lim = torch.tensor([[n + 1 if w else n for w in r] for r in (wide if table else [wide])], dtype=torch.int32)
+        self._limits.copy_(lim if table else (lim[0] if self._limits.dim() == 1 else lim.expand(self.B, dep_q)))
 
-    def prefill(self, tokens: torch.Tensor):
+    def reset_streams(self, rows: Sequence[int]) -> None:
+        """Restart the given rows of a per-stream session at position 0, ready for ``prefill`` of a new prompt into them (the other rows
+        taking length 0).  No ring is zeroed: at position 0 the slot -> position map shows a stream none of its slots, and every slot is
+        appended to before a later position can see it."""
+        st = self.model.transformer._streaming_state
+        if st is None or not st.per_stream:
+            raise ValueError("reset_streams needs a per-stream session (begin(..., per_stream=True))")
+        rows = [int(r) for r in rows]
+        if any(r < 0 or r >= self.B for r in rows):
+            raise ValueError(f"reset_streams: rows {rows} outside [0, {self.B})")
+        st.pos.index_fill_(0, torch.tensor(rows, dtype=torch.long).to(st.pos.device), 0)
+
+    def prefill(self, tokens: torch.Tensor, lengths=None):
         """tokens int64 [B, K, T] -> (h [B, n_embd], logits [B, V]) of the LAST position, from which ``frame`` / ``start`` continue.
         Valid at any point of a live session: the T positions are appended behind whatever the session holds (a second turn, a wrapped
-        ring included); the captured step graphs stay valid, positions being device scalars."""
-        h, logits = self.model.forward_global(tokens)
-        return h[:, -1].contiguous(), logits[:, -1].contiguous()
+        ring included); the captured step graphs stay valid, positions being device scalars.
+        ``lengths`` (list or integer tensor ``[B]``, ``0 <= len <= T``; a per-stream session): stream ``b`` consumes its first ``lengths[b]``
+        positions and gets ``h`` / ``logits`` of ITS last position ``lengths[b] - 1``; a stream of length 0 takes nothing and gets
+        unspecified values."""
+        h, logits = self.model.forward_global(tokens, lengths)
+        if lengths is None:
+            return h[:, -1].contiguous(), logits[:, -1].contiguous()
+        last = (torch.as_tensor(lengths).to(h.device, torch.long) - 1).clamp_(min=0)
+        rows = torch.arange(h.shape[0], device=h.device)
+        return h[rows, last].contiguous(), logits[rows, last].contiguous()
 
     def frame(self, h: torch.Tensor, logits: torch.Tensor, g_idx: int = 0):
         """(h, logits) of the last position -> (text token [B], audio tokens [B, dep_q]) of the next frame."""
@@ -205,6 +240,17 @@ class GPTGen:
         col[:, 1:cfg.dep_q + 1, 0] = audio
         h, logits = m.forward_global(col)
         return h[:, 0], logits[:, 0]
+
+
+def blanking_regime(pre_gen_len: int, minlen: int, g_idx: int) -> int:
+    """Blanking regime of frame ``g_idx`` behind a prefix of ``pre_gen_len`` positions (infer_no_streaming.py:264-283): 0 = the first frame,
+    2049 everywhere; later frames: codebook 0 -> 2048, the others 2049 once ``pre_gen_len + g_idx > minlen`` (regime 1), else 2048 (regime 2)."""
+    return 0 if g_idx == 0 else (1 if pre_gen_len + g_idx > minlen else 2)
+
+
+def regime_wide(regime: int, dep_q: int) -> list:
+    """The ``wide`` flags ``GPTGen.set_blanking`` takes for a regime of ``blanking_regime``."""
+    return [True] * dep_q if regime == 0 else [l > 0 and regime == 1 for l in range(dep_q)]
 
 
 class InferenceImp:
@@ -256,19 +302,18 @@ class InferenceImp:
             init[:, 0] = ids.text_initial_token_id
         pre_gen_len = prefix.shape[2]
         n_codes = ids.n_audio_codes
-        gen = GPTGen(m, self.use_sampling, self.temp, self.temp_text, self.top_k, self.top_k_text, n_codes, self.noise)
+        gen = self._make_gen()
         gen.begin(1)
         frames, texts = [], []
         try:
             h, logits = gen.prefill(torch.cat([init, prefix], dim=-1))      # positions 0 .. pre_gen_len
             regime = None
             for g_idx in range(maxlen):
-                g_len = pre_gen_len + g_idx
                 # blanking regime of this frame (:264-283): first frame -> 2049 everywhere; later l = 0 -> 2048,
                 # l > 0 -> 2049 once g_len > minlen else 2048
-                new_regime = 0 if g_len == pre_gen_len else (1 if g_len > minlen else 2)
+                new_regime = blanking_regime(pre_gen_len, minlen, g_idx)
                 if new_regime != regime:
-                    gen.set_blanking([True] * cfg.dep_q if new_regime == 0 else [l > 0 and new_regime == 1 for l in range(cfg.dep_q)])
+                    gen.set_blanking(regime_wide(new_regime, cfg.dep_q))
                     regime = new_regime
                 text, audio = gen.frame(h.contiguous(), logits.contiguous(), g_idx)
                 audio_host = audio[0].tolist()
@@ -286,6 +331,74 @@ class InferenceImp:
         if self.task_name == "TTS" and frames and cfg.dep_q == 8:
             out["codes"] = reverse_delay(out["frames"])
         return out
+
+    def _make_gen(self) -> GPTGen:
+        return GPTGen(self.model, self.use_sampling, self.temp, self.temp_text, self.top_k, self.top_k_text, self.ids.n_audio_codes, self.noise)
+
+    @torch.no_grad()
+    def generate_batch(self, seqs: Sequence[torch.Tensor]) -> List[Dict[str, torch.Tensor]]:
+        """``generate`` for several prompts at once: seqs = B tensors int64 ``[K, L_i]`` of any lengths -> one dict per prompt with the keys
+        and values ``generate`` gives that prompt alone.  One ragged prefill of ``[initial frame | prefix_i]`` on a per-stream session (every
+        stream at its own positions: no padding enters a ring), then lock-step frames with a common ``g_idx``; blanking regime, ``maxlen``
+        and the stop rule are per stream, the latter two on the host from ONE ``[B, dep_q]`` read per frame.  A finished stream keeps
+        stepping and its tokens are dropped; the loop ends when every stream is done.  The noise test hook returns ``[B, k]`` here.  More
+        prompts than one batch holds are the caller's loop."""
+        m, ids = self.model, self.ids
+        cfg, dev = m.config, m.device
+        B = len(seqs)
+        if B < 1:
+            return []
+        init = m._get_initial_token()
+        if ids.text_initial_token_id is not None:
+            init[:, 0] = ids.text_initial_token_id
+        splits = [self.split_prompt(s.to(dev).unsqueeze(0)) for s in seqs]
+        prompts = [torch.cat([init, prefix], dim=-1) for prefix, _, _ in splits]       # positions 0 .. pre_gen_len_i
+        pre = [prefix.shape[2] for prefix, _, _ in splits]
+        maxlen, minlen = [s[1] for s in splits], [s[2] for s in splits]
+        lens = [p.shape[2] for p in prompts]
+        tokens = torch.zeros(B, init.shape[1], max(lens), device=dev, dtype=torch.long)
+        for b, p in enumerate(prompts):
+            tokens[b, :, :lens[b]] = p[0]
+        n_codes = ids.n_audio_codes
+        frames: List[list] = [[] for _ in range(B)]
+        texts: List[list] = [[] for _ in range(B)]
+        done = [n <= 0 for n in maxlen]
+        gen = self._make_gen()
+        gen.begin(B, per_stream=True)
+        try:
+            h, logits = gen.prefill(tokens, lens)
+            regimes, g_idx = None, 0
+            while not all(done):
+                # a finished stream keeps the regime it ended in: only a live stream's change is worth a write to the device
+                new = [regimes[b] if done[b] and regimes is not None else blanking_regime(pre[b], minlen[b], g_idx) for b in range(B)]
+                if new != regimes:
+                    gen.set_blanking([regime_wide(r, cfg.dep_q) for r in new])
+                    regimes = new
+                text, audio = gen.frame(h.contiguous(), logits.contiguous(), g_idx)
+                audio_host = audio.tolist()
+                for b in range(B):
+                    if done[b]:
+                        continue
+                    if g_idx > minlen[b] and any(t >= n_codes for t in audio_host[b][3:]):     # the stop rule of :286-288
+                        done[b] = True
+                        continue
+                    frames[b].append(audio[b].clone())
+                    texts[b].append(text[b].clone())
+                    done[b] = g_idx + 1 == maxlen[b]
+                if all(done):
+                    break
+                h, logits = gen.advance(text, audio)
+                g_idx += 1
+        finally:
+            gen.end()
+        outs = []
+        for b in range(B):
+            out = {"frames": torch.stack(frames[b]) if frames[b] else torch.zeros(0, cfg.dep_q, dtype=torch.long, device=dev),
+                   "text": torch.stack(texts[b]) if texts[b] else torch.zeros(0, dtype=torch.long, device=dev)}
+            if self.task_name == "TTS" and frames[b] and cfg.dep_q == 8:
+                out["codes"] = reverse_delay(out["frames"])
+            outs.append(out)
+        return outs
 
     @torch.no_grad()
     def __call__(self, seq: torch.Tensor, mask: Optional[torch.Tensor] = None):

@@ -40,7 +40,7 @@ from . import model as _lm_model       # PREFILL_CHUNK is read at call time
 from .model import RMSNorm as _AlphaNorm  # noqa: F401  (key layout of the codecformer norms)
 from .model import ScaledEmbedding, StreamingTransformer, _Weight, adopt_state_dict
 from .stack import KV_DTYPES, ROUTE_APPEND_FIRST, ROUTE_PREFILL, prefill_route, prefill_window  # noqa: F401  (the route rules, under the names callers know)
-from .stack import ROUTE_DECODE, Geometry, LayerView, LinearView, LoraBank, _lora_add, _StepState, check_kv_dtype, counted_step, prefill_chunks, run_chunks
+from .stack import ROUTE_DECODE, Geometry, LayerView, LinearView, LoraBank, _lora_add, _StepState, check_kv_dtype, counted_step, per_stream_chunks, prefill_chunks, run_chunks
 
 
 @dataclass
@@ -470,26 +470,38 @@ class LLAMAStreamingTransformer(StreamingModule[_StepState]):
         self.fp8 = False      # opt-in: run the block linears on the fp8 (e4m3, per-row scales) matrix-core path
         self.kv_dtype = torch.float32      # precision of the KV rings (GPT.from_state_dict(..., kv_dtype=))
 
-    def _make_state(self, batch_size: int, capacity: int, kv_dtype: Optional[torch.dtype] = None) -> _StepState:
+    def _make_state(self, batch_size: int, capacity: int, kv_dtype: Optional[torch.dtype] = None, per_stream: bool = False) -> _StepState:
         c = self.config
         kvd = self.kv_dtype if kv_dtype is None else kv_dtype
         check_kv_dtype(kvd, capacity)
-        return _StepState.make(batch_size, c.n_query_groups, c.n_head, c.head_size, capacity, kvd, self.ln_f.weight.device, len(self.h))
+        return _StepState.make(batch_size, c.n_query_groups, c.n_head, c.head_size, capacity, kvd, self.ln_f.weight.device, len(self.h),
+                               per_stream=per_stream)
 
     def _init_streaming_state(self, batch_size: int) -> _StepState:
         if self.config.context is None:
             raise RuntimeError("Cannot create a streaming KVCache without a context to estimate capacity.")
         return self._make_state(batch_size, self.config.context)
 
-    def run(self, x: torch.Tensor, B: int, T: int, st: _StepState) -> torch.Tensor:
+    def plan(self, T: int, st: _StepState, ragged: bool = False) -> list:
+        """``[(t0, Tc, route)]`` of a ``T``-position call on ``st``.  A per-stream state: one decode step for a lone position without
+        lengths, else ``per_stream_chunks`` (every chunk attends before it appends; no host position is consulted)."""
+        cap = st.k[0].shape[2]
+        if st.per_stream:
+            return [(0, 1, ROUTE_DECODE)] if T == 1 and not ragged else per_stream_chunks(cap, T, _lm_model.PREFILL_CHUNK)
+        plan = [(0, 1, ROUTE_DECODE)] if T == 1 else prefill_chunks(cap, st.offset_cpu, T, st.k[0].dtype, _lm_model.PREFILL_CHUNK)
+        return [(t0, Tc, ROUTE_DECODE if Tc == 1 else route) for t0, Tc, route in plan]      # a one-position tail is a decode step, as a lone one
+
+    def run(self, x: torch.Tensor, B: int, T: int, st: _StepState, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x fp32 ``[B*T, n_embd]`` (T new positions per stream) -> final-normed hidden ``[B*T, n_embd]``.  ``T > 1``: one pass per
         entry of ``prefill_chunks`` (decided from the host counter ``st.offset_cpu``), equal to the same positions fed one at a time
-        on any ring -- empty, partly filled or wrapped, fp32 or bf16."""
+        on any ring -- empty, partly filled or wrapped, fp32 or bf16.  ``lengths`` (int32 ``[B]`` on the device, a per-stream state):
+        stream ``b`` takes its first ``lengths[b]`` rows, the rest of its rows come back unspecified."""
         c = self.config
-        plan = [(0, 1, ROUTE_DECODE)] if T == 1 else prefill_chunks(st.k[0].shape[2], st.offset_cpu, T, st.k[0].dtype, _lm_model.PREFILL_CHUNK)
-        plan = [(t0, Tc, ROUTE_DECODE if Tc == 1 else route) for t0, Tc, route in plan]      # a one-position tail is a decode step, as a lone one
+        if lengths is not None and not st.per_stream:
+            raise ValueError("per-stream lengths need a per-stream state (GPTGen.begin(..., per_stream=True))")
+        plan = self.plan(T, st, ragged=lengths is not None)
         geo = Geometry(c.n_head, c.context, True, float(c.rope_base), c.rope_n_elem, litgpt_freqs=True)
-        y = run_chunks(x, B, st, plan, geo, [blk.view() for blk in self.h], fp8=self.fp8)
+        y = run_chunks(x, B, st, plan, geo, [blk.view() for blk in self.h], fp8=self.fp8, lengths=lengths)
         return ops.rmsnorm(y, self.ln_f.gain_f32(), self.ln_f.eps)
 
 
@@ -615,25 +627,41 @@ class GPT(StreamingModule[_GPTState]):
         return h, self._head(h)
 
     @torch.no_grad()
-    def forward_global(self, sequence: torch.Tensor):
+    def forward_global(self, sequence: torch.Tensor, lengths=None):
         """sequence int64 ``[B, n_q+1, T]`` -> (transformer_out fp32 ``[B,T,n_embd]``, text_logits fp32 ``[B,T,V]``).
         Outside ``streaming()`` the T positions are 0..T-1 (plain causal + context mask, no ring effects); inside, they follow
-        the positions already streamed (T = 1 steps replay a captured graph)."""
+        the positions already streamed (T = 1 steps replay a captured graph).
+        ``lengths`` (a list or integer tensor ``[B]``, ``0 <= len <= T``): a ragged batch -- stream ``b`` consumes its first ``lengths[b]``
+        positions, at exactly the positions a call of that length alone would give them (no padding or shifted positions), and advances
+        by that many; rows past a stream's length are ignored on the way in (their tokens are overwritten with id 0 before the embedding
+        launch) and unspecified on the way out.  Inside a session this needs per-stream positions (``GPTGen.begin(per_stream=True)``);
+        outside, the call builds a temporary per-stream state."""
         B, K, T = sequence.shape
         assert K == self.num_codebooks, f"Sequence shape {sequence.shape} must match the number of codebooks."
         if self.max_seq_length < T:
             raise ValueError(f"Cannot forward sequence of length {T}, max seq length is only {self.max_seq_length}.")
         c = self.config
-        self._bank_rows(B)
         st = self.transformer._streaming_state
-        if st is not None and T == 1 and self._streaming_state is not None:
+        len_dev = None
+        if lengths is not None:
+            host = lengths.tolist() if isinstance(lengths, torch.Tensor) else list(lengths)
+            if len(host) != B or any(int(n) != n or n < 0 or n > T for n in host):
+                raise ValueError(f"forward_global: lengths must be {B} integers in [0, {T}], got {host}")
+            if st is not None and not st.per_stream:
+                raise ValueError("forward_global: lengths inside a session need per-stream positions (GPTGen.begin(..., per_stream=True))")
+            len_dev = torch.tensor([int(n) for n in host], dtype=torch.int32).to(sequence.device)
+            # padding content never reaches a table: rows past a stream's length read id 0
+            past = torch.arange(T, device=sequence.device)[None, :] >= len_dev[:, None]
+            sequence = sequence.masked_fill(past[:, None, :], 0)
+        self._bank_rows(B)
+        if st is not None and T == 1 and len_dev is None and self._streaming_state is not None:
             h, logits = counted_step(st, self._streaming_state.graphed_global, sequence.reshape(B, K).contiguous())
             return h.view(B, 1, c.n_embd), logits.view(B, 1, -1)
         if st is None:
             # a ring that never fills: positions 0..T-1 all addressable (bf16 rings: above the 64 slots of the fp32-only short-ring kernel)
-            st = self.transformer._make_state(B, T + 1 if self.kv_dtype == torch.float32 else max(T + 1, 65))
+            st = self.transformer._make_state(B, T + 1 if self.kv_dtype == torch.float32 else max(T + 1, 65), per_stream=len_dev is not None)
         toks = sequence.permute(0, 2, 1).reshape(B * T, K).contiguous()
-        h = self.transformer.run(self._embed(toks), B, T, st)
+        h = self.transformer.run(self._embed(toks), B, T, st, lengths=len_dev)
         logits = self._head(h)
         return h.view(B, T, c.n_embd), logits.view(B, T, -1)
 

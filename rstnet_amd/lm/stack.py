@@ -22,22 +22,27 @@ ROUTE_PREFILL = "prefill"                # lm_attn_prefill against ring + chunk,
 class _StepState:
     k: List[torch.Tensor]      # per layer [B, G, cap, D] ring (fp32 or bf16)
     v: List[torch.Tensor]
-    pos: torch.Tensor          # int64 [1] on device: steps appended so far (= position of the next step)
+    pos: torch.Tensor          # int64 [1] on device: steps appended so far (= position of the next step); per-stream state: int64 [B]
     scratch: Optional[tuple] = None   # (split workspace, arrival counters) of the long-ring attention kernel
     # host mirror of `pos`.  Graph replays move `pos` without running Python: whoever replays a captured step keeps the mirror in step
     # (LMGen through temporal_base, GPT / GPTGen through lm.stack.counted_step) -- GPT chooses the route of a T > 1 call from it
     offset_cpu: int = 0
     tables: object = None             # ops.TemporalFrameTables of the persistent batch-1 launch (built at the first step that takes it)
     tables_key: object = None
+    per_stream: bool = False          # `pos` holds one position per stream: every T > 1 call attends before it appends, chunk by chunk
 
     def reset(self) -> None:
         self.pos.zero_()
         self.offset_cpu = 0
 
     @classmethod
-    def make(cls, batch: int, kv_heads: int, heads: int, head_dim: int, cap: int, dtype: torch.dtype, device, layers: int) -> "_StepState":
+    def make(cls, batch: int, kv_heads: int, heads: int, head_dim: int, cap: int, dtype: torch.dtype, device, layers: int,
+             per_stream: bool = False) -> "_StepState":
         """Zeroed rings ``[batch, kv_heads, cap, head_dim]`` per layer; rings of more than 64 slots also get the split scratch of the
-        long-ring decode kernel (one partial per query head and split)."""
+        long-ring decode kernel (one partial per query head and split).  ``per_stream``: ``pos`` is int64 ``[batch]``, one position per
+        stream -- its multi-position calls all take ``ROUTE_PREFILL``, whose kernels serve head size 64 or 128 only."""
+        if per_stream and head_dim not in (64, 128):
+            raise ValueError(f"per-stream positions: head size {head_dim} is outside the multi-position attention kernels (64 or 128)")
         shape = (batch, kv_heads, cap, head_dim)
         scratch = None
         if cap > 64:
@@ -46,7 +51,7 @@ class _StepState:
                        torch.zeros(batch, heads, device=device, dtype=torch.int32))
         return cls([torch.zeros(shape, device=device, dtype=dtype) for _ in range(layers)],
                    [torch.zeros(shape, device=device, dtype=dtype) for _ in range(layers)],
-                   torch.zeros(1, device=device, dtype=torch.long), scratch)
+                   torch.zeros(batch if per_stream else 1, device=device, dtype=torch.long), scratch, per_stream=per_stream)
 
 
 def check_kv_dtype(kv_dtype: torch.dtype, capacity: Optional[int] = None) -> None:
@@ -85,13 +90,29 @@ def prefill_chunks(cap: int, pos: int, T: int, kv_dtype: torch.dtype, chunk: int
     return [(t0, min(step, T - t0), prefill_route(cap, pos + t0, min(step, T - t0), kv_dtype)) for t0 in range(0, T, step)]
 
 
+def per_stream_chunks(cap: int, T: int, chunk: int) -> list:
+    """``[(t0, Tc, ROUTE_PREFILL)]`` of a ``T``-position call on a per-stream state: chunks of ``min(chunk, cap)``, every one attending
+    before it appends -- right at any fill level, so no position has to be known on the host.  A one-position tail stays on this route
+    too: the decode kernels know no lengths."""
+    step = min(chunk, cap)
+    return [(t0, min(step, T - t0), ROUTE_PREFILL) for t0 in range(0, T, step)]
+
+
+def chunk_advance(lengths: Sequence[int], t0: int, Tc: int) -> list:
+    """Positions each stream takes from the chunk ``[t0, t0 + Tc)`` of a call with per-stream ``lengths``: ``clamp(len - t0, 0, Tc)`` --
+    the host statement of what ``lm_ring_append_ragged(lengths=, t0=)`` appends and ``run_layers`` adds to ``st.pos``."""
+    return [max(0, min(Tc, int(n) - t0)) for n in lengths]
+
+
 def counted_step(st: _StepState, step, *args):
     """Run ONE T = 1 step of the global transformer through ``step`` -- a ``Graphed`` callable or a plain one -- and leave the host
     mirror ``st.offset_cpu`` one further, whether Python ran (warm-up, capture, eager: ``run_layers`` counted already) or a graph was
     replayed (the device counter ``st.pos`` moved, no Python ran).  ``prefill_chunks`` decides the route of a later ``T > 1`` call from
     that mirror without a device synchronisation, and a mirror that lags sends a chunk across the wrap down the append-first route:
     wrong values, no error.  So EVERY caller that may replay a captured step goes through here, and code that moves ``st.pos`` by hand
-    (a benchmark that seeds a full ring) sets ``st.offset_cpu`` with it."""
+    (a benchmark that seeds a full ring) sets ``st.offset_cpu`` with it.  A per-stream state (``st.per_stream``) never consults the
+    mirror or ``prefill_chunks``: its streams stand at different positions, and its ``T > 1`` calls attend before they append
+    (``per_stream_chunks``), which is right at any fill level."""
     at = st.offset_cpu
     out = step(*args)
     st.offset_cpu = at + 1
@@ -160,16 +181,21 @@ def _linear(x: torch.Tensor, lin: LinearView, fp8: bool, res: Optional[torch.Ten
 
 
 def run_layers(x: Optional[torch.Tensor], T: int, st: _StepState, route: str, geo: Geometry, layers: Sequence[LayerView], *,
-               pos: Optional[torch.Tensor] = None, embed: Optional[tuple] = None, fp8: bool = False) -> torch.Tensor:
+               pos: Optional[torch.Tensor] = None, embed: Optional[tuple] = None, fp8: bool = False,
+               lengths: Optional[torch.Tensor] = None, t0: int = 0) -> torch.Tensor:
     """x fp32 ``[B*T, E]`` (row ``b*T + t``) -> ``[B*T, E]``: ``T`` consecutive positions per stream through every layer, on ``route``
     (``T == 1``: a decode route).  Per layer: in-projection with the RMSNorm prologue | attention and ring append of the route |
     out-projection | gated MLP -- the MLP as two plain products where it carries unmerged adapters, because the gate follows fc_1 / fc_2
     WITH their updates.  ``embed = (add, table, tokens, col)`` instead of ``x``: the input is ``add + table[tokens[:, col]]``, formed inside
     the first launch for batch <= 2.  ``fp8``: the linears run on the fp8 matrix-core path (``GPT.use_fp8``).  Advances ``st.pos`` /
-    ``st.offset_cpu`` by ``T`` unless the caller owns the position (``pos``)."""
+    ``st.offset_cpu`` by ``T`` unless the caller owns the position (``pos``).  ``lengths`` (int32 ``[B]`` on the device, ``ROUTE_PREFILL`` on a
+    per-stream state) with the offset ``t0`` of these ``T`` rows inside the call the lengths count from: stream ``b`` appends, and its
+    position advances by, ``clamp(lengths[b] - t0, 0, T)`` rows; the outputs of its other rows are unspecified."""
     B = (x.shape[0] if x is not None else embed[0].shape[0]) // T
     cap, D = st.k[0].shape[2], st.k[0].shape[3]
     pos_t = st.pos if pos is None else pos
+    if lengths is not None and (route != ROUTE_PREFILL or not st.per_stream or pos is not None):
+        raise ValueError("run_layers: per-stream lengths need a per-stream state on the prefill route")
     rot = dict(rope=geo.rope, max_period=geo.max_period, rope_dims=geo.rope_dims)
     rope_table = window = freqs = None
     if route == ROUTE_DECODE and geo.rope and cap > 64:
@@ -200,7 +226,10 @@ def run_layers(x: Optional[torch.Tensor], T: int, st: _StepState, route: str, ge
                 q3 = qkv.view(B, T, -1)
                 a = ops.lm_attn_prefill(q3, k, v, pos_t, window=window, heads=geo.heads, freqs=freqs, **rot)
                 # after the attention, in stream order: the slot of position pos + t still held position pos + t - cap
-                ops.lm_ring_append(q3, k, v, pos_t, heads=geo.heads, freqs=freqs, **rot)
+                if lengths is None:
+                    ops.lm_ring_append(q3, k, v, pos_t, heads=geo.heads, freqs=freqs, **rot)
+                else:
+                    ops.lm_ring_append_ragged(q3, k, v, pos_t, heads=geo.heads, freqs=freqs, lengths=lengths, t0=t0, **rot)
             else:
                 q = ops.lm_rope_append(qkv.view(B, T, -1), k, v, pos_t, heads=geo.heads, **rot)
                 a = ops.attention(q, k, v, pos_dev=pos_t, ring=True, context=geo.context).view(B * T, -1)
@@ -212,17 +241,20 @@ def run_layers(x: Optional[torch.Tensor], T: int, st: _StepState, route: str, ge
             u = _linear(x, ly.fc, fp8, prologue=ops.PROLOGUE_RMSNORM, alpha=ly.norm2[0], eps=ly.norm2[1])
             x = _linear(u, ly.proj, fp8, res=x, prologue=ops.PROLOGUE_SILU_GATE)
     if pos is None:
-        st.pos.add_(T)
+        st.pos.add_(T if lengths is None else (lengths - t0).clamp_(0, T))
         st.offset_cpu += T
     return x
 
 
-def run_chunks(x: torch.Tensor, B: int, st: _StepState, plan: Sequence[tuple], geo: Geometry, layers: Sequence[LayerView], fp8: bool = False) -> torch.Tensor:
-    """x fp32 ``[B*T, E]`` -> ``[B*T, E]``: one ``run_layers`` pass per ``(t0, Tc, route)`` of ``plan``, which covers the ``T`` positions in order."""
+def run_chunks(x: torch.Tensor, B: int, st: _StepState, plan: Sequence[tuple], geo: Geometry, layers: Sequence[LayerView], fp8: bool = False,
+               lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x fp32 ``[B*T, E]`` -> ``[B*T, E]``: one ``run_layers`` pass per ``(t0, Tc, route)`` of ``plan``, which covers the ``T`` positions in
+    order; ``lengths``: per-stream lengths of the whole call (each pass gets them with its ``t0``)."""
     if len(plan) == 1:
-        return run_layers(x, plan[0][1], st, plan[0][2], geo, layers, fp8=fp8)
+        return run_layers(x, plan[0][1], st, plan[0][2], geo, layers, fp8=fp8, lengths=lengths)
     xv = x.view(B, -1, x.shape[1])
     y = torch.empty_like(xv)
     for t0, Tc, route in plan:
-        y[:, t0:t0 + Tc] = run_layers(xv[:, t0:t0 + Tc].reshape(B * Tc, -1), Tc, st, route, geo, layers, fp8=fp8).view(B, Tc, -1)
+        y[:, t0:t0 + Tc] = run_layers(xv[:, t0:t0 + Tc].reshape(B * Tc, -1), Tc, st, route, geo, layers, fp8=fp8, lengths=lengths,
+                                      t0=t0).view(B, Tc, -1)
     return y.view(x.shape)

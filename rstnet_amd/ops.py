@@ -130,6 +130,21 @@ def _chk(t: Optional[torch.Tensor], name: str, dtype=torch.float32, contiguous: 
         raise ValueError(f"rstnet_amd.ops: `{name}` must be contiguous")
 
 
+def _shared_pos(pos_dev: Optional[torch.Tensor], op: str) -> None:
+    """Kernels outside the GPT global transformer know ONE position per call: a per-stream vector is refused, never read as its row 0."""
+    if pos_dev is not None and pos_dev.numel() != 1:
+        raise ValueError(f"rstnet_amd.ops: {op} takes one position for all streams (numel 1), got {tuple(pos_dev.shape)}; per-stream positions "
+                         "are served by lm_attn_decode / lm_rope_table / lm_attn_prefill / lm_ring_append")
+
+
+def _pos_stride(pos_dev: torch.Tensor, B: int, op: str) -> int:
+    """0: ``pos_dev`` holds one position shared by the ``B`` streams (today's entry points); 1: int64 ``[B]``, one per stream."""
+    n = pos_dev.numel()
+    if n != 1 and (n != B or pos_dev.dim() != 1):
+        raise ValueError(f"rstnet_amd.ops: {op}: pos_dev holds one position, or one per stream as int64 [{B}]; got {tuple(pos_dev.shape)}")
+    return 0 if n == 1 else 1
+
+
 _gemm_scratch: dict = {}
 
 
@@ -517,6 +532,7 @@ def rope_split(qkv: torch.Tensor, H: int, *, q: Optional[torch.Tensor] = None, k
         _chk(t, n)
     if pos_dev is not None:
         _chk(pos_dev, "pos_dev", torch.int64)
+        _shared_pos(pos_dev, "rope_split")
     cap = k.shape[2]
     _lib.check(_lib.lib().rst_rope_split_f32(_ptr(qkv), _ptr(q), _ptr(k), _ptr(v), _ptr(pos_dev), pos0, B, T, H, D, cap,
                                              int(ring), int(rope), rope_coef(max_period, D), _stream()))
@@ -537,6 +553,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, pos0: int = 
     out = torch.empty(B, T, H * D, device=q.device, dtype=torch.float32)
     if pos_dev is not None:
         _chk(pos_dev, "pos_dev", torch.int64)
+        _shared_pos(pos_dev, "attention")
     if G != H and not (ring and pos_dev is not None and D in (64, 128)):
         raise NotImplementedError("grouped key/value heads are served by the ring decode path only (head dim 64 / 128)")
     if ring and pos_dev is not None and (T <= 8 or G != H) and D in (64, 128):
@@ -575,6 +592,7 @@ def attention_step(qkv: torch.Tensor, H: int, k: torch.Tensor, v: torch.Tensor, 
     for t, n in ((qkv, "qkv"), (k, "k"), (v, "v")):
         _chk(t, n)
     _chk(pos_dev, "pos_dev", torch.int64)
+    _shared_pos(pos_dev, "attention_step")
     B, T, E3 = qkv.shape
     D = E3 // (3 * H)
     if k.shape != v.shape or k.shape[0] != B or k.shape[1] != H or k.shape[3] != D:
@@ -1033,6 +1051,7 @@ def gemv_attn(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, p
     ``[B, H, cap <= 8, D]`` (the new step is appended by the launch), ``w`` bf16 ``[N, H*D]``."""
     _chk(qkv, "qkv"); _chk(k_cache, "k_cache"); _chk(v_cache, "v_cache"); _chk(res, "res"); _chk(bias, "bias")
     _chk(pos_dev, "pos_dev", torch.int64)
+    _shared_pos(pos_dev, "gemv_attn")
     _chk(w, "w", torch.bfloat16)
     B, H, cap, D = k_cache.shape
     N = w.shape[0]
@@ -1518,6 +1537,7 @@ def lm_rope_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     for t, n in ((qkv, "qkv"), (k_cache, "k_cache"), (v_cache, "v_cache")):
         _chk(t, n)
     _chk(pos_dev, "pos_dev", torch.int64)
+    _shared_pos(pos_dev, "lm_rope_append")
     B, G, cap, D = k_cache.shape
     T = qkv.shape[1]
     assert qkv.dim() == 3 and qkv.shape[2] == (heads + 2 * G) * D, (tuple(qkv.shape), heads, G, D)
@@ -1530,10 +1550,18 @@ def lm_rope_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
 @_on_tensor_device
 def lm_rope_table(pos_dev: torch.Tensor, D: int, *, max_period: float = 10000.0, rope_dims: int = 0) -> torch.Tensor:
     """The rotation of ONE decode step as ``[D/2, 2]`` (cos, sin) pairs (rst_lm_rope_table_f32; identity beyond ``rope_dims / 2``): computed
-    once per frame and handed to every layer's ``lm_attn_decode(rope_table=...)`` -- the values the attention launch would compute itself."""
+    once per frame and handed to every layer's ``lm_attn_decode(rope_table=...)`` -- the values the attention launch would compute itself.
+    Per-stream positions (``pos_dev`` int64 ``[B]``, a 1-D vector of more than one element): ``[B, D/2, 2]``, table ``b`` at ``pos_dev[b]``
+    (rst_lm_rope_table_ps_f32)."""
     _chk(pos_dev, "pos_dev", torch.int64)
-    out = torch.empty(D // 2, 2, device=pos_dev.device, dtype=torch.float32)
-    _lib.check(_lib.lib().rst_lm_rope_table_f32(_ptr(pos_dev), _ptr(out), D, rope_dims, rope_coef(max_period, rope_dims or D), _stream()))
+    if pos_dev.numel() == 1:
+        out = torch.empty(D // 2, 2, device=pos_dev.device, dtype=torch.float32)
+        _lib.check(_lib.lib().rst_lm_rope_table_f32(_ptr(pos_dev), _ptr(out), D, rope_dims, rope_coef(max_period, rope_dims or D), _stream()))
+        return out
+    B = pos_dev.numel()
+    _pos_stride(pos_dev, B, "lm_rope_table")
+    out = torch.empty(B, D // 2, 2, device=pos_dev.device, dtype=torch.float32)
+    _lib.check(_lib.lib().rst_lm_rope_table_ps_f32(_ptr(pos_dev), _ptr(out), B, D, rope_dims, rope_coef(max_period, rope_dims or D), _stream()))
     return out
 
 
@@ -1545,7 +1573,9 @@ def lm_attn_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     """Single-query attention of the new step given its qkv row ``[B, (H+2G)*D]`` (RoPE, ring append, attention and the
     reduction over slot splits in ONE launch) -> ``[B, H*D]``; the ring is ``[B,G,cap,D]`` (``heads`` = H when G < H).
     ``scratch = (ws [B,H,splits,D+2] fp32, counters [B,H] int32 zeros)`` may be passed to reuse buffers (the counters re-arm
-    themselves).  ``rope_dims``: leading head dims that rotate (0 = all; the frequencies then span ``rope_dims``)."""
+    themselves).  ``rope_dims``: leading head dims that rotate (0 = all; the frequencies then span ``rope_dims``).  ``pos_dev``: one
+    position for all streams (``numel() == 1``, rst_lm_attn_decode_f32) or int64 ``[B]``, one per stream (rst_lm_attn_decode_ps_f32;
+    ``rope_table`` is then the ``[B, D/2, 2]`` table ``lm_rope_table`` returns for that vector)."""
     _chk(qkv, "qkv")
     kv16 = k_cache.dtype == torch.bfloat16          # bf16 rings: the reference's cache precision (long-ring form)
     _chk(k_cache, "k_cache", k_cache.dtype if kv16 else torch.float32)
@@ -1555,7 +1585,8 @@ def lm_attn_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     B, G, cap, D = k_cache.shape
     H = heads or G
     assert qkv.shape[1] == (H + 2 * G) * D, (tuple(qkv.shape), H, G, D)
-    assert rope_table is None or rope_table.numel() == D, "rope_table: [D/2, 2] of lm_rope_table"
+    ps = _pos_stride(pos_dev, B, "lm_attn_decode")
+    assert rope_table is None or rope_table.numel() == (B * D if ps else D), "rope_table: what lm_rope_table returns for this pos_dev"
     if kv16 and cap <= 64:
         raise NotImplementedError("bf16 KV rings are served by the long-ring attention (capacity > 64)")
     if splits is None:
@@ -1572,10 +1603,10 @@ def lm_attn_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     packed = packed and D in (64, 128)
     out = None if packed else torch.empty(B, H * D, device=qkv.device, dtype=torch.float32)
     xp = _packed_buffer(qkv.device, B, H * D) if packed else None
-    _lib.check(_lib.lib().rst_lm_attn_decode_f32(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(ws), _ptr(counters), _ptr(out),
-                                                _ptr(pos_dev), B, H, D, cap, _ctx(context), splits, qkv.shape[1],
-                                                int(rope), rope_coef(max_period, rope_dims or D), G, rope_dims, _ptr(xp), int(kv16),
-                                                _ptr(rope_table) if rope else None, _stream()))
+    head = (_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(ws), _ptr(counters), _ptr(out), _ptr(pos_dev))
+    tail = (B, H, D, cap, _ctx(context), splits, qkv.shape[1], int(rope), rope_coef(max_period, rope_dims or D), G, rope_dims, _ptr(xp), int(kv16),
+            _ptr(rope_table) if rope else None, _stream())
+    _lib.check(_lib.lib().rst_lm_attn_decode_ps_f32(*head, ps, *tail) if ps else _lib.lib().rst_lm_attn_decode_f32(*head, *tail))
     return PackedAct(xp, B, H * D) if packed else out
 
 
@@ -1630,8 +1661,10 @@ def lm_attn_prefill(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     row 0) sees keys ``max(0, p - window + 1) .. p``; the chunk's own keys / values take part rounded to the ring's dtype.  Follow with
     ``lm_ring_append`` (head dim 64 / 128, ``Tc <= cap``, ``1 <= window <= cap``).  ``heads`` = H when the ring holds G < H grouped
     key/value heads (as in ``lm_attn_decode``; None: G == H, rst_lm_attn_prefill_f32, else rst_lm_attn_prefill_gqa_f32).  ``freqs``: the
-    fp32 frequency table of the caller's reference (``rope_dims / 2`` values); None: the Moshi table of ``_rope_freqs``."""
+    fp32 frequency table of the caller's reference (``rope_dims / 2`` values); None: the Moshi table of ``_rope_freqs``.  ``pos_dev`` int64
+    ``[B]``: the chunk of stream ``b`` starts at ``pos_dev[b]`` (rst_lm_attn_prefill_ps_f32)."""
     B, Tc, H, G, D, cap, kv16 = _prefill_args(qkv, k_cache, v_cache, pos_dev, heads, freqs, rope_dims)
+    ps = _pos_stride(pos_dev, B, "lm_attn_prefill")
     L = _lib.lib()
     nbytes = int(L.rst_lm_attn_prefill_workspace_bytes(B, Tc, H, D, int(kv16)) if heads is None else
                  L.rst_lm_attn_prefill_gqa_workspace_bytes(B, Tc, H, G, D, int(kv16)))
@@ -1641,10 +1674,13 @@ def lm_attn_prefill(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     out = torch.empty(B * Tc, H * D, device=qkv.device, dtype=torch.float32)
     if freqs is None:
         freqs = _rope_freqs(qkv.device, max_period, rope_dims or D)
-    head = (_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(ws), nbytes, _ptr(out), _ptr(pos_dev), B, Tc, H)
+    head = (_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(ws), nbytes, _ptr(out), _ptr(pos_dev))
     tail = (D, cap, int(window), qkv.shape[2], int(rope), rope_coef(max_period, rope_dims or D), rope_dims, int(kv16),
             _ptr(freqs) if rope else None, _stream())
-    _lib.check(L.rst_lm_attn_prefill_f32(*head, *tail) if heads is None else L.rst_lm_attn_prefill_gqa_f32(*head, G, *tail))
+    if ps:
+        _lib.check(L.rst_lm_attn_prefill_ps_f32(*head, ps, B, Tc, H, G, *tail))
+    else:
+        _lib.check(L.rst_lm_attn_prefill_f32(*head, B, Tc, H, *tail) if heads is None else L.rst_lm_attn_prefill_gqa_f32(*head, B, Tc, H, G, *tail))
     return out
 
 
@@ -1654,15 +1690,40 @@ def lm_ring_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
                    freqs: Optional[torch.Tensor] = None) -> None:
     """The append that follows ``lm_attn_prefill`` in stream order: the ``Tc`` keys of ``qkv [B, Tc, (H+2G)*D]`` rotated at positions
     ``pos_dev + t``, and the values, into ring slots ``(pos_dev + t) % cap`` of ``[B,G,cap,D]`` in the ring's dtype (rst_lm_ring_append;
-    ``heads`` given: rst_lm_ring_append_gqa).  ``heads`` / ``freqs`` as in ``lm_attn_prefill``."""
+    ``heads`` given: rst_lm_ring_append_gqa).  ``heads`` / ``freqs`` as in ``lm_attn_prefill``.  ``pos_dev`` int64 ``[B]``: per-stream
+    positions (rst_lm_ring_append_ps).  Per-stream LENGTHS: ``lm_ring_append_ragged``."""
+    _ring_append(qkv, k_cache, v_cache, pos_dev, rope, max_period, rope_dims, heads, freqs, None, 0)
+
+
+@_on_tensor_device
+def lm_ring_append_ragged(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos_dev: torch.Tensor, *, rope: bool,
+                          max_period: float = 10000.0, rope_dims: int = 0, heads: Optional[int] = None,
+                          freqs: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None, t0: int = 0) -> None:
+    """``lm_ring_append`` with per-stream lengths (rst_lm_ring_append_ps): ``lengths`` int32 ``[B]`` on the device with the offset ``t0`` of
+    this chunk inside the call the lengths count from -- stream ``b`` appends rows ``t < clamp(lengths[b] - t0, 0, Tc)`` only and no other
+    ring slot is written; a length of 0 takes nothing.  ``pos_dev``: one position or int64 ``[B]``.  (Its own entry point so that
+    ``lm_ring_append`` keeps the signature its callers and their recorded launch plans know.)"""
+    _ring_append(qkv, k_cache, v_cache, pos_dev, rope, max_period, rope_dims, heads, freqs, lengths, t0)
+
+
+def _ring_append(qkv, k_cache, v_cache, pos_dev, rope, max_period, rope_dims, heads, freqs, lengths, t0) -> None:
     B, Tc, H, G, D, cap, kv16 = _prefill_args(qkv, k_cache, v_cache, pos_dev, heads, freqs, rope_dims)
+    ps = _pos_stride(pos_dev, B, "lm_ring_append")
+    _chk(lengths, "lengths", torch.int32)
+    if lengths is not None and (lengths.dim() != 1 or lengths.numel() != B):
+        raise ValueError(f"rstnet_amd.ops: lm_ring_append: lengths must be int32 [{B}], got {tuple(lengths.shape)}")
+    if t0 < 0:
+        raise ValueError(f"rstnet_amd.ops: lm_ring_append: chunk offset t0 = {t0}")
     L = _lib.lib()
     if freqs is None:
         freqs = _rope_freqs(qkv.device, max_period, rope_dims or D)
-    head = (_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(pos_dev), B, Tc, H)
+    head = (_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(pos_dev))
     tail = (D, cap, qkv.shape[2], int(rope), rope_coef(max_period, rope_dims or D), rope_dims, int(kv16), _ptr(freqs) if rope else None,
             _stream())
-    _lib.check(L.rst_lm_ring_append(*head, *tail) if heads is None else L.rst_lm_ring_append_gqa(*head, G, *tail))
+    if ps or lengths is not None:
+        _lib.check(L.rst_lm_ring_append_ps(*head, ps, _ptr(lengths), int(t0), B, Tc, H, G, *tail))
+    else:
+        _lib.check(L.rst_lm_ring_append(*head, B, Tc, H, *tail) if heads is None else L.rst_lm_ring_append_gqa(*head, B, Tc, H, G, *tail))
 
 
 _sample_ws: dict = {}
@@ -1673,12 +1734,16 @@ def lm_sample(logits: torch.Tensor, *, use_sampling: bool, temp: float, top_k: i
               out: Optional[torch.Tensor] = None, limit: int = 0, limit_dev: Optional[torch.Tensor] = None, top_p: float = 0.0,
               two_level: bool = True) -> torch.Tensor:
     """logits fp32 ``[B, V]`` -> tokens int64 ``[B]`` (greedy, or top-k sampling with Exp(1) ``noise [B, top_k]``).  ``limit``
-    (or the int32 device scalar ``limit_dev``): ids >= limit are never drawn when sampling.  ``top_p > 0``: nucleus sampling
+    (or the int32 device scalar ``limit_dev``; int32 ``[B]``, any element stride, e.g. a column of a ``[B, n]`` table: one limit per row,
+    rst_lm_sample_rows_f32): ids >= limit are never drawn when sampling.  ``top_p > 0``: nucleus sampling
     (utils/sampling.py:66-82) instead of top-k; ``noise`` is then ``[B, V]`` (one draw per sorted position).  ``two_level=False``
     keeps the one-workgroup-per-row kernel for vocabularies above 32768 (A/B measurements, tests)."""
     _chk(logits, "logits")
-    _chk(limit_dev, "limit_dev", torch.int32)
+    _chk(limit_dev, "limit_dev", torch.int32, contiguous=False)
     B, V = logits.shape
+    if limit_dev is not None and limit_dev.numel() != 1 and (limit_dev.dim() != 1 or limit_dev.numel() != B):
+        raise ValueError(f"rstnet_amd.ops: `limit_dev` holds one limit, or one per row as int32 [{B}]; got {tuple(limit_dev.shape)}")
+    rows = limit_dev is not None and limit_dev.numel() == B and B > 1
     sampling = bool(use_sampling and temp > 0)
     nucleus = sampling and top_p > 0.0
     if noise is not None:       # a [B, >= top_k] column slice of a wider noise buffer is fine (row stride is passed on)
@@ -1695,9 +1760,10 @@ def lm_sample(logits: torch.Tensor, *, use_sampling: bool, temp: float, top_k: i
         nbytes = int(_lib.lib().rst_lm_sample_workspace_bytes(B, V, top_k if sampling else 1, int(nucleus)))
         if nbytes:
             ws = _scratch(_sample_ws, logits.device, ("sample", nbytes), lambda: torch.empty((nbytes + 7) // 8, device=logits.device, dtype=torch.int64))
-    _lib.check(_lib.lib().rst_lm_sample_f32(_ptr(logits), _ptr(noise), _ptr(out), B, V, V, top_k, noise.stride(0) if noise is not None else 0,
-                                           out.stride(0) if B > 1 else 1, int(use_sampling), float(temp), int(limit), _ptr(limit_dev),
-                                           float(top_p) if nucleus else 0.0, _ptr(ws), nbytes, _stream()))
+    head = (_ptr(logits), _ptr(noise), _ptr(out), B, V, V, top_k, noise.stride(0) if noise is not None else 0, out.stride(0) if B > 1 else 1,
+            int(use_sampling), float(temp), int(limit), _ptr(limit_dev))
+    tail = (float(top_p) if nucleus else 0.0, _ptr(ws), nbytes, _stream())
+    _lib.check(_lib.lib().rst_lm_sample_rows_f32(*head, limit_dev.stride(0), *tail) if rows else _lib.lib().rst_lm_sample_f32(*head, *tail))
     return out
 
 
@@ -1891,7 +1957,8 @@ def depth_decode_frame(tables, h_all: torch.Tensor, tokens: torch.Tensor, noise:
                        ring_cap: Optional[int] = None) -> None:
     """``tables``: a ``lm.depth_frame.DepthFrameTables``; ``h_all`` fp32 ``[B, dep_q * E]``; ``tokens`` int64 ``[B, >= dep_q + 1]`` with the
     text token in column 0 -- columns 1 .. dep_q are written; ``noise`` fp32 ``[B, >= dep_q * top_k]`` (unit column stride);
-    ``limits`` int32 ``[dep_q]`` on the device (optional id blanking per step); ``ring_cap``: capacity of the depth transformer's KV
+    ``limits`` int32 ``[dep_q]`` on the device (optional id blanking per step), or ``[B, dep_q]``: one row of limits per stream
+    (rst_depth_decode_frame_rows); ``ring_cap``: capacity of the depth transformer's KV
     ring (default dep_q, the LMGen setup; the slot -> position map of RingKVCache.complete depends on it)."""
     _chk(h_all, "h_all")
     _chk(limits, "limits", torch.int32)
@@ -1900,6 +1967,12 @@ def depth_decode_frame(tables, h_all: torch.Tensor, tokens: torch.Tensor, noise:
     B = h_all.shape[0]
     t = tables
     assert h_all.shape[1] == t.dep_q * t.E and tokens.shape[0] == B and tokens.shape[1] >= t.dep_q + 1
+    if limits is not None and not (limits.dim() == 1 and limits.numel() >= t.dep_q) and \
+            not (limits.dim() == 2 and limits.shape[0] == B and limits.shape[1] >= t.dep_q):
+        raise ValueError(f"rstnet_amd.ops: `limits` must be int32 [>= {t.dep_q}] or [{B}, >= {t.dep_q}], got {tuple(limits.shape)}")
+    fn, lim = _lib.lib().rst_depth_decode_frame, (_ptr(limits),)
+    if limits is not None and limits.dim() == 2:
+        fn, lim = _lib.lib().rst_depth_decode_frame_rows, (_ptr(limits), limits.shape[1])
     sampling = bool(use_sampling and temp > 0)
     if sampling:
         if noise is None or not noise.is_cuda or noise.dtype != torch.float32 or noise.dim() != 2 or noise.stride(1) != 1 or \
@@ -1910,9 +1983,9 @@ def depth_decode_frame(tables, h_all: torch.Tensor, tokens: torch.Tensor, noise:
                                       dtype=torch.int64))
     n_w = t.dep_q * (t.L * (3 * t.E * t.E + t.E * t.E + 3 * t.Hd * t.E) + t.card * t.E)      # weight elements read once per frame
     with _profiled("depth_frame", 2.0 * B * n_w, 2 * n_w + 4 * h_all.numel(), (B, t.dep_q, t.L)):
-        _lib.check(_lib.lib().rst_depth_decode_frame(
+        _lib.check(fn(
             t.in_proj, t.out_proj, t.norm1, t.norm2, t.gate_in, t.gate_out, t.heads, t.head_bias, t.emb, t.emb_rows,
-            _ptr(h_all), _ptr(tokens), _ptr(noise) if sampling else None, _ptr(limits), _ptr(ws), _ptr(t.status),
+            _ptr(h_all), _ptr(tokens), _ptr(noise) if sampling else None, *lim, _ptr(ws), _ptr(t.status),
             B, t.E, t.H, t.Hd, t.card, t.dep_q, t.L, h_all.stride(0) if B > 1 else h_all.shape[1], tokens.stride(0) if B > 1 else tokens.shape[1],
             noise.stride(0) if (sampling and B > 1) else (noise.shape[1] if sampling else 0), int(top_k), int(sampling), float(temp), float(eps),
             _ctx(context), int(ring_cap) if ring_cap else t.dep_q, _stream()))
@@ -1998,6 +2071,7 @@ def temporal_decode_frame(tables: "TemporalFrameTables", x: torch.Tensor, pos_de
     ``rope_table``: fp32 ``[D/2, 2]`` of `lm_rope_table` or None (no rotation)."""
     _chk(x, "x")
     _chk(pos_dev, "pos_dev", torch.int64)
+    _shared_pos(pos_dev, "temporal_decode_frame")
     _chk(rope_table, "rope_table")
     t = tables
     assert x.shape == (1, t.E)
@@ -2052,6 +2126,7 @@ def codec_transformer_frame(x: torch.Tensor, layers: Sequence[dict], pos_dev: to
     k_cache / v_cache [B, H, cap, D]`` (rings: the new steps are appended).  ``pos_dev``: int64 device scalar, position of x[:, 0]."""
     _chk(x, "x")
     _chk(pos_dev, "pos_dev", torch.int64)
+    _shared_pos(pos_dev, "codec_transformer_frame")
     B, T, E = x.shape
     L = len(layers)
     F_ = layers[0]["linear1"].shape[0]

@@ -22,6 +22,16 @@ def main():
         name, value = item.split("=", 1)
         if name == "LIB":
             _lib.LIB_PATH = os.path.abspath(value)
+            # an OLDER build (a parent commit's library next to this tree's Python): entry points it lacks leave the table, so the
+            # launches both builds have can be compared; a call of a missing one then fails by name
+            import ctypes
+            import torch  # noqa: F401  (first, as in _lib.lib(): the library must find torch's HIP runtime, not the system's)
+            other =ctypes.CDLL(_lib.LIB_PATH)
+            missing = [n for n in _lib.SIGNATURES if not hasattr(other, n)]
+            for n in missing:
+                del _lib.SIGNATURES[n]
+            if missing:
+                print(f"tools/ab.py: {value} lacks {missing}", file=sys.stderr)
             continue
         assert hasattr(ops, name), f"rstnet_amd.ops has no switch {name}"
         setattr(ops, name, ast.literal_eval(value))
