@@ -557,24 +557,29 @@ int rst_skinny_pack_act_f32(const float* x, const float* alpha, uint16_t* xp, in
 
 int rst_skinny_bf16_split_plan(int B, int N, int K) { return rst_skinny_bf16_split_plan_impl(B, N, K); }
 
+// what the four skinny GEMM entry points share; each adds its operand pointers
+static SkinnyParams skinny_params(const float* res, const float* bias, float* y, int B, int N, int K, int ldy, uint16_t* gate_out, int split_k,
+                                  float* ws, uint32_t* counters) {
+    SkinnyParams p = {};
+    p.res = res; p.bias = bias; p.y = y; p.B = B; p.N = N; p.K = K; p.ldy = ldy;
+    p.gate_out = gate_out; p.gate_plane = (long)((B + 31) / 32 * 32) * (N / 2);
+    p.split_k = split_k; p.ws = ws; p.counters = counters;
+    return p;
+}
+
 int rst_gemm_skinny_bf16_f32(const uint16_t* xp, const uint16_t* wp, const float* res, const float* bias, float* y, int B, int N,
                              int K, int ldy, uint16_t* gate_out, int split_k, float* ws, uint32_t* counters, rst_stream_t stream) {
     RST_REQUIRE(xp, "gemm_skinny_bf16: null packed activations");
-    SkinnyParams p = {};
-    p.xp = xp; p.w = wp; p.res = res; p.bias = bias; p.y = y; p.B = B; p.N = N; p.K = K; p.ldy = ldy;
-    p.gate_out = gate_out; p.gate_plane = (long)((B + 31) / 32 * 32) * (N / 2);
-    p.split_k = split_k; p.ws = ws; p.counters = counters;
+    SkinnyParams p = skinny_params(res, bias, y, B, N, K, ldy, gate_out, split_k, ws, counters);
+    p.xp = xp; p.w = wp;
     return rst_launch_gemm_skinny(p, (hipStream_t)stream);
 }
 
 int rst_gemm_skinny_x32_bf16_f32(const float* x, const float* alpha, float eps, int mode, int ldx, const uint16_t* wp, const float* res,
                                  const float* bias, float* y, int B, int N, int K, int ldy, uint16_t* gate_out, rst_stream_t stream) {
     RST_REQUIRE(x, "gemm_skinny_x32: null activations");
-    SkinnyParams p = {};
-    p.xf = x; p.alpha = alpha; p.eps = eps; p.xmode = mode; p.ldx = ldx;
-    p.w = wp; p.res = res; p.bias = bias; p.y = y; p.B = B; p.N = N; p.K = K; p.ldy = ldy;
-    p.gate_out = gate_out; p.gate_plane = (long)((B + 31) / 32 * 32) * (N / 2);
-    p.split_k = 1;
+    SkinnyParams p = skinny_params(res, bias, y, B, N, K, ldy, gate_out, 1, nullptr, nullptr);
+    p.xf = x; p.alpha = alpha; p.eps = eps; p.xmode = mode; p.ldx = ldx; p.w = wp;
     return rst_launch_gemm_skinny(p, (hipStream_t)stream);
 }
 
@@ -583,16 +588,14 @@ int rst_skinny_pack_weight_fp8w(const uint8_t* q, const float* scale, uint8_t* q
     return rst_launch_skinny_pack_weight_fp8w(q, scale, qp, sp, N, K, interleave_halves, (hipStream_t)stream);
 }
 
-int rst_gemm_skinny_fp8w_supported(int B, int N, int K) { return rst_gemm_skinny_fp8w_supported_impl(B, N, K); }
+int rst_gemm_skinny_fp8w_supported(int B, int N, int K) { return rst_gemm_skinny_wq_supported_impl(B, N, K); }
 
 int rst_gemm_skinny_fp8w_f32(const uint16_t* xp, const uint8_t* qp, const float* sp, const float* res, const float* bias, float* y, int B,
                              int N, int K, int ldy, uint16_t* gate_out, int split_k, float* ws, uint32_t* counters, rst_stream_t stream) {
     RST_REQUIRE(xp && qp && sp, "gemm_skinny_fp8w: null packed activations, weights or scales");
-    RST_REQUIRE(rst_gemm_skinny_fp8w_supported_impl(B, N, K), "gemm_skinny_fp8w: need 1 <= B <= 64, N > 0 and K %% 32 == 0 (B=%d N=%d K=%d)", B, N, K);
-    SkinnyParams p = {};
-    p.xp = xp; p.w8 = qp; p.wscale = sp; p.res = res; p.bias = bias; p.y = y; p.B = B; p.N = N; p.K = K; p.ldy = ldy;
-    p.gate_out = gate_out; p.gate_plane = (long)((B + 31) / 32 * 32) * (N / 2);
-    p.split_k = split_k; p.ws = ws; p.counters = counters;
+    RST_REQUIRE(rst_gemm_skinny_wq_supported_impl(B, N, K), "gemm_skinny_fp8w: need 1 <= B <= 64, N > 0 and K %% 32 == 0 (B=%d N=%d K=%d)", B, N, K);
+    SkinnyParams p = skinny_params(res, bias, y, B, N, K, ldy, gate_out, split_k, ws, counters);
+    p.xp = xp; p.w8 = qp; p.wscale = sp;
     return rst_launch_gemm_skinny(p, (hipStream_t)stream);
 }
 
@@ -601,16 +604,14 @@ int rst_skinny_pack_weight_mxfp4w(const uint8_t* q, const uint8_t* scale, uint8_
     return rst_launch_skinny_pack_weight_mxfp4w(q, scale, qp, sp, N, K, interleave_halves, (hipStream_t)stream);
 }
 
-int rst_gemm_skinny_mxfp4w_supported(int B, int N, int K) { return rst_gemm_skinny_mxfp4w_supported_impl(B, N, K); }
+int rst_gemm_skinny_mxfp4w_supported(int B, int N, int K) { return rst_gemm_skinny_wq_supported_impl(B, N, K); }
 
 int rst_gemm_skinny_mxfp4w_f32(const uint16_t* xp, const uint8_t* qp, const uint8_t* sp, const float* res, const float* bias, float* y, int B,
                                int N, int K, int ldy, uint16_t* gate_out, int split_k, float* ws, uint32_t* counters, rst_stream_t stream) {
     RST_REQUIRE(xp && qp && sp, "gemm_skinny_mxfp4w: null packed activations, codes or scale bytes");
-    RST_REQUIRE(rst_gemm_skinny_mxfp4w_supported_impl(B, N, K), "gemm_skinny_mxfp4w: need 1 <= B <= 64, N > 0 and K %% 32 == 0 (B=%d N=%d K=%d)", B, N, K);
-    SkinnyParams p = {};
-    p.xp = xp; p.w4 = qp; p.w4scale = sp; p.res = res; p.bias = bias; p.y = y; p.B = B; p.N = N; p.K = K; p.ldy = ldy;
-    p.gate_out = gate_out; p.gate_plane = (long)((B + 31) / 32 * 32) * (N / 2);
-    p.split_k = split_k; p.ws = ws; p.counters = counters;
+    RST_REQUIRE(rst_gemm_skinny_wq_supported_impl(B, N, K), "gemm_skinny_mxfp4w: need 1 <= B <= 64, N > 0 and K %% 32 == 0 (B=%d N=%d K=%d)", B, N, K);
+    SkinnyParams p = skinny_params(res, bias, y, B, N, K, ldy, gate_out, split_k, ws, counters);
+    p.xp = xp; p.w4 = qp; p.w4scale = sp;
     return rst_launch_gemm_skinny(p, (hipStream_t)stream);
 }
 

@@ -233,21 +233,16 @@ int rst_launch_attn_step(const AttnStepParams& p, hipStream_t stream) {
                 "attention_step: a packed result needs whole 32-row tiles (out_rows=%d for %d rows) and H * D %% 8 == 0", p.out_rows, p.B * p.T);
     RST_REQUIRE((uintptr_t)p.qkv % 16 == 0 && (uintptr_t)p.k % 16 == 0 && (uintptr_t)p.v % 16 == 0, "attention_step: 16-byte aligned buffers required");
     const size_t lds = as_lds_bytes(p.T, p.D, p.cap);
-    auto go = [&](auto kern) {
-        if (lds > 48 * 1024) {
-            static RstOncePerDevice attr_once;       // one flag per kernel instance
-            if (attr_once.first()) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-                (void)hipGetLastError();
-            }
-        }
+    auto go = [&](auto k) {
+        constexpr auto kern = decltype(k)::fn;
+        if (lds > 48 * 1024) rst_allow_dynamic_lds<kern>(144 * 1024);
         hipLaunchKernelGGL(kern, dim3(p.B * p.H), dim3(AS_THREADS), lds, stream, p);
     };
     switch (p.T) {
-        case 1: go(attn_step_kernel<1>); break;
-        case 2: go(attn_step_kernel<2>); break;
-        case 3: go(attn_step_kernel<3>); break;
-        default: go(attn_step_kernel<4>); break;
+        case 1: go(RstKernel<attn_step_kernel<1>>{}); break;
+        case 2: go(RstKernel<attn_step_kernel<2>>{}); break;
+        case 3: go(RstKernel<attn_step_kernel<3>>{}); break;
+        default: go(RstKernel<attn_step_kernel<4>>{}); break;
     }
     return rst_check_launch("attention_step");
 }

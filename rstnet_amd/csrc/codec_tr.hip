@@ -482,20 +482,17 @@ int rst_launch_codec_tr(const CodecTrParams& p, hipStream_t stream) {
         rst_set_error("codec_tr: workspace memset failed");
         return RST_ERR_LAUNCH;
     }
-    auto go = [&](auto kern, int grid) {
-        static RstOncePerDevice attr_once;       // one flag per kernel instance
-        if (attr_once.first()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            (void)hipGetLastError();
-        }
+    auto go = [&](auto k, int grid) {
+        constexpr auto kern = decltype(k)::fn;
+        rst_allow_dynamic_lds<kern>(150 * 1024);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(DF_THREADS), lds, stream, p);
     };
     // the persistent launch, then its one-workgroup repair launch (a no-op unless a hand-off timed out: persist.h)
     switch (R) {
-        case 1: go(codec_tr_kernel<1, false>, G); go(codec_tr_kernel<1, true>, 1); break;
-        case 2: go(codec_tr_kernel<2, false>, G); go(codec_tr_kernel<2, true>, 1); break;
-        case 3: go(codec_tr_kernel<3, false>, G); go(codec_tr_kernel<3, true>, 1); break;
-        default: go(codec_tr_kernel<4, false>, G); go(codec_tr_kernel<4, true>, 1); break;
+        case 1: go(RstKernel<codec_tr_kernel<1, false>>{}, G); go(RstKernel<codec_tr_kernel<1, true>>{}, 1); break;
+        case 2: go(RstKernel<codec_tr_kernel<2, false>>{}, G); go(RstKernel<codec_tr_kernel<2, true>>{}, 1); break;
+        case 3: go(RstKernel<codec_tr_kernel<3, false>>{}, G); go(RstKernel<codec_tr_kernel<3, true>>{}, 1); break;
+        default: go(RstKernel<codec_tr_kernel<4, false>>{}, G); go(RstKernel<codec_tr_kernel<4, true>>{}, 1); break;
     }
     return rst_check_launch("codec_tr");
 }

@@ -1269,20 +1269,17 @@ int launch_cfg(const GemmWinParams& p, bool vec, hipStream_t stream) {
         return RST_ERR_UNSUPPORTED;
     }
     const size_t lds = 2 * (BM + BN) * (KB + 4) * sizeof(float);
-    auto go = [&](auto kern) {
-        static RstOncePerDevice attr_once;  // > 64 KiB of dynamic LDS needs the opt-in once per kernel instantiation
-        if (attr_once.first()) {
-            // the kernel also has a few bytes of static LDS: stay below the 160 KiB total (the largest tile needs 83 KiB)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            (void)hipGetLastError();
-        }
+    auto go = [&](auto k) {
+        constexpr auto kern = decltype(k)::fn;
+        // the kernel also has a few bytes of static LDS: stay below the 160 KiB total (the largest tile needs 83 KiB)
+        rst_allow_dynamic_lds<kern>(128 * 1024);
         hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)(p.split_k > 1 ? p.split_k : 1)), dim3(256), lds, stream, p);
     };
     const bool elu = p.act_in == 1;
-    if (vec && elu) go(gemm_win_kernel<TM, TN, WM, WN, true, true, KB>);
-    else if (vec) go(gemm_win_kernel<TM, TN, WM, WN, true, false, KB>);
-    else if (elu) go(gemm_win_kernel<TM, TN, WM, WN, false, true, KB>);
-    else go(gemm_win_kernel<TM, TN, WM, WN, false, false, KB>);
+    if (vec && elu) go(RstKernel<gemm_win_kernel<TM, TN, WM, WN, true, true, KB>>{});
+    else if (vec) go(RstKernel<gemm_win_kernel<TM, TN, WM, WN, true, false, KB>>{});
+    else if (elu) go(RstKernel<gemm_win_kernel<TM, TN, WM, WN, false, true, KB>>{});
+    else go(RstKernel<gemm_win_kernel<TM, TN, WM, WN, false, false, KB>>{});
     return rst_check_launch("gemm_win");
 }
 
@@ -1302,23 +1299,20 @@ int launch_stream(const GemmWinParams& p, long tiles, hipStream_t stream) {
     const int per_cu = per_cu_env > 0 ? per_cu_env : (KB == 16 ? 3 : 2);
     const long resident = (long)per_cu * gw_cu_count();
     const unsigned grid = (unsigned)(tiles < resident ? tiles : resident);
-    auto go = [&](auto kern) {
-        static RstOncePerDevice attr_once;
-        if (attr_once.first()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            (void)hipGetLastError();
-        }
+    auto go = [&](auto k) {
+        constexpr auto kern = decltype(k)::fn;
+        rst_allow_dynamic_lds<kern>(128 * 1024);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p, (int)tiles);
     };
 #ifdef RST_ABLATION
     // ceiling measurements: instances that skip the loads / run the MFMAs only -- WRONG RESULTS by construction, which
     // is why they are compiled into the tools build alone
     static const int dbg = rst_knob("RST_GEMM_DBG", 0);
-    if (KB == 16 && dbg == 1) { go(gemm_win_stream_kernel<false, 16, 1>); return rst_check_launch("gemm_win"); }
-    if (KB == 16 && dbg == 5) { go(gemm_win_stream_kernel<false, 16, 5>); return rst_check_launch("gemm_win"); }
+    if (KB == 16 && dbg == 1) { go(RstKernel<gemm_win_stream_kernel<false, 16, 1>>{}); return rst_check_launch("gemm_win"); }
+    if (KB == 16 && dbg == 5) { go(RstKernel<gemm_win_stream_kernel<false, 16, 5>>{}); return rst_check_launch("gemm_win"); }
 #endif
-    if (p.act_in == 1) go(gemm_win_stream_kernel<true, KB>);
-    else go(gemm_win_stream_kernel<false, KB>);
+    if (p.act_in == 1) go(RstKernel<gemm_win_stream_kernel<true, KB>>{});
+    else go(RstKernel<gemm_win_stream_kernel<false, KB>>{});
     return rst_check_launch("gemm_win");
 }
 
@@ -1363,12 +1357,9 @@ int launch_stream_b3_cfg(const GemmWinParams& p, hipStream_t stream) {
     static const int per_cu = rst_knob("RST_B3_WGS", NWN == 2 ? 2 : 1);      // tools build only
     const long resident = (long)per_cu * gw_cu_count();
     const unsigned grid = (unsigned)(tiles < resident ? tiles : resident);
-    auto go = [&](auto kern) {
-        static RstOncePerDevice attr_once;
-        if (attr_once.first()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            (void)hipGetLastError();
-        }
+    auto go = [&](auto k) {
+        constexpr auto kern = decltype(k)::fn;
+        rst_allow_dynamic_lds<kern>(128 * 1024);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(128 * NWN), lds, stream, p, (int)tiles);
     };
     // rows whose window reaches into the zero padding (or past the end), ragged last tiles: the masked form for the whole launch.
@@ -1383,26 +1374,26 @@ int launch_stream_b3_cfg(const GemmWinParams& p, hipStream_t stream) {
     if (force_mask) lean = false;
     // (the ablation instances of the SHIPPED form: weight fragments direct; RST_B3_DIRW=0 has no ablation instances)
     static const int dbg = rst_knob("RST_B3_DBG", 0);
-    if (dirw && dbg == 1) { go(gemm_win_b3_stream_kernel<false, true, NWN, 1, true, true>); return rst_check_launch("gemm_win_b3"); }
-    if (dirw && dbg == 2) { go(gemm_win_b3_stream_kernel<false, true, NWN, 2, true, true>); return rst_check_launch("gemm_win_b3"); }
-    if (dirw && dbg == 3) { go(gemm_win_b3_stream_kernel<false, true, NWN, 3, true, true>); return rst_check_launch("gemm_win_b3"); }
-    if (dirw && dbg == 4) { go(gemm_win_b3_stream_kernel<false, true, NWN, 4, true, true>); return rst_check_launch("gemm_win_b3"); }
-    if (dirw && dbg == 5) { go(gemm_win_b3_stream_kernel<false, true, NWN, 5, true, true>); return rst_check_launch("gemm_win_b3"); }
+    if (dirw && dbg == 1) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 1, true, true>>{}); return rst_check_launch("gemm_win_b3"); }
+    if (dirw && dbg == 2) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 2, true, true>>{}); return rst_check_launch("gemm_win_b3"); }
+    if (dirw && dbg == 3) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 3, true, true>>{}); return rst_check_launch("gemm_win_b3"); }
+    if (dirw && dbg == 4) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 4, true, true>>{}); return rst_check_launch("gemm_win_b3"); }
+    if (dirw && dbg == 5) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 5, true, true>>{}); return rst_check_launch("gemm_win_b3"); }
     static const int bufl = rst_knob("RST_B3_BUF", 1);        // 0: plain global loads (64-bit addresses on the vector unit)
     if (!bufl && dirw && p.act_in != 1) {
-        if (lean) go(gemm_win_b3_stream_kernel<false, false, NWN, 0, false, true>);
-        else go(gemm_win_b3_stream_kernel<false, true, NWN, 0, false, true>);
+        if (lean) go(RstKernel<gemm_win_b3_stream_kernel<false, false, NWN, 0, false, true>>{});
+        else go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 0, false, true>>{});
         return rst_check_launch("gemm_win_b3");
     }
 #endif
 #ifdef RST_ABLATION
     if (!dirw) {
         if (p.act_in == 1) {
-            if (lean) go(gemm_win_b3_stream_kernel<true, false, NWN>);
-            else go(gemm_win_b3_stream_kernel<true, true, NWN>);
+            if (lean) go(RstKernel<gemm_win_b3_stream_kernel<true, false, NWN>>{});
+            else go(RstKernel<gemm_win_b3_stream_kernel<true, true, NWN>>{});
         } else {
-            if (lean) go(gemm_win_b3_stream_kernel<false, false, NWN>);
-            else go(gemm_win_b3_stream_kernel<false, true, NWN>);
+            if (lean) go(RstKernel<gemm_win_b3_stream_kernel<false, false, NWN>>{});
+            else go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN>>{});
         }
         return rst_check_launch("gemm_win_b3");
     }
@@ -1415,11 +1406,11 @@ int launch_stream_b3_cfg(const GemmWinParams& p, hipStream_t stream) {
         if (taps == 3) return launch_shared_b3_cfg<NWN, 3>(p, stream);
     }
     if (p.act_in == 1) {
-        if (lean) go(gemm_win_b3_stream_kernel<true, false, NWN, 0, true, true>);
-        else go(gemm_win_b3_stream_kernel<true, true, NWN, 0, true, true>);
+        if (lean) go(RstKernel<gemm_win_b3_stream_kernel<true, false, NWN, 0, true, true>>{});
+        else go(RstKernel<gemm_win_b3_stream_kernel<true, true, NWN, 0, true, true>>{});
     } else {
-        if (lean) go(gemm_win_b3_stream_kernel<false, false, NWN, 0, true, true>);
-        else go(gemm_win_b3_stream_kernel<false, true, NWN, 0, true, true>);
+        if (lean) go(RstKernel<gemm_win_b3_stream_kernel<false, false, NWN, 0, true, true>>{});
+        else go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 0, true, true>>{});
     }
     return rst_check_launch("gemm_win_b3");
 }

@@ -469,16 +469,13 @@ int rst_launch_depth_frame(const DepthFrameParams& p, hipStream_t stream) {
         rst_set_error("depth_frame: workspace memset failed");
         return RST_ERR_LAUNCH;
     }
-    auto go = [&](auto kern, int grid) {
-        static RstOncePerDevice attr_once;       // one flag per kernel instance (the lambda is instantiated per `kern` type)
-        if (attr_once.first()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-            (void)hipGetLastError();
-        }
+    auto go = [&](auto k, int grid) {
+        constexpr auto kern = decltype(k)::fn;
+        rst_allow_dynamic_lds<kern>(150 * 1024);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(DF_THREADS), lds, stream, p);
     };
     // the persistent launch, then its one-workgroup repair launch (a no-op unless a hand-off timed out: persist.h)
-    if (p.B == 1) { go(depth_frame_kernel<1, false>, G); go(depth_frame_kernel<1, true>, 1); }
-    else { go(depth_frame_kernel<2, false>, G); go(depth_frame_kernel<2, true>, 1); }
+    if (p.B == 1) { go(RstKernel<depth_frame_kernel<1, false>>{}, G); go(RstKernel<depth_frame_kernel<1, true>>{}, 1); }
+    else { go(RstKernel<depth_frame_kernel<2, false>>{}, G); go(RstKernel<depth_frame_kernel<2, true>>{}, 1); }
     return rst_check_launch("depth_frame");
 }

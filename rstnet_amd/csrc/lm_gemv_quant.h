@@ -287,14 +287,9 @@ __global__ __launch_bounds__(NT) void gemvq_rows_kernel(const GemvQuantParams p)
     }
 }
 
-// the opt-in to more than 64 KiB of dynamic LDS is per kernel and per device: one flag per instantiation
 template <auto KERN>
 void launch_gemvq(const GemvQuantParams& p, unsigned grid, size_t shmem, hipStream_t stream) {
-    static RstOncePerDevice attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        (void)hipGetLastError();
-    }
+    rst_allow_dynamic_lds<KERN>(128 * 1024);
     hipLaunchKernelGGL(KERN, dim3(grid), dim3(NT), shmem, stream, p);
 }
 

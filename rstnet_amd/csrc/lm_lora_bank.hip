@@ -150,11 +150,7 @@ int rst_launch_lora_bank_shrink(const LoraBankShrinkParams& p, int n_ids, hipStr
     const long grid = p.rows * (p.r / LB_SLAB);
     RST_REQUIRE(grid <= 0x7fffffffL, "lora_bank_shrink: rows * r / %d = %ld workgroups exceed one grid", LB_SLAB, grid);
     const size_t lds = (size_t)(p.K + LB_WAVES) * sizeof(float);
-    static RstOncePerDevice attr_once;
-    if (attr_once.first()) {      // K = 16384 stages 64 KiB and the reduction scratch behind it
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lora_bank_shrink_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        (void)hipGetLastError();
-    }
+    rst_allow_dynamic_lds<lora_bank_shrink_kernel>(128 * 1024);      // K = 16384 stages 64 KiB and the reduction scratch behind it
     hipLaunchKernelGGL(lora_bank_shrink_kernel, dim3((unsigned)grid), dim3(LB_THREADS), lds, stream, p);
     return rst_check_launch("lora_bank_shrink");
 }

@@ -679,6 +679,27 @@ int rst_skinny_bf16_split_plan_impl(int B, int N, int K) {
     return s;
 }
 
+// The kernel of p's operand form (fp32 input | fp8 weights | MXFP4 weights | bf16) at NB batch tiles and CT column tiles per workgroup;
+// returns the name its launch is checked under.
+template <int NB, int CT>
+static const char* skinny_launch(const SkinnyParams& p, dim3 grid, hipStream_t stream) {
+    const dim3 block(64 * SKINNY_WAVES);
+    if (!p.xp) {
+        hipLaunchKernelGGL((gemm_skinny_x32_kernel<NB, CT>), grid, block, 0, stream, p);
+        return "gemm_skinny_x32";
+    }
+    if (p.w8) {
+        hipLaunchKernelGGL((gemm_skinny_kernel<NB, CT, true>), grid, block, 0, stream, p);
+        return "gemm_skinny_fp8w";
+    }
+    if (p.w4) {
+        hipLaunchKernelGGL((gemm_skinny_kernel<NB, CT, false, true>), grid, block, 0, stream, p);
+        return "gemm_skinny_mxfp4w";
+    }
+    hipLaunchKernelGGL((gemm_skinny_kernel<NB, CT>), grid, block, 0, stream, p);
+    return "gemm_skinny";
+}
+
 int rst_launch_gemm_skinny(const SkinnyParams& p, hipStream_t stream) {
     RST_REQUIRE(p.B >= 1 && p.B <= 64 && p.N > 0 && p.K > 0 && p.K % 16 == 0, "gemm_skinny: need 1 <= B <= 64 and K %% 16 == 0 (B=%d K=%d)", p.B, p.K);
     RST_REQUIRE((p.xp || p.xf) && (p.w || p.w8 || p.w4) && (p.y || p.gate_out), "gemm_skinny: null pointer");
@@ -691,61 +712,22 @@ int rst_launch_gemm_skinny(const SkinnyParams& p, hipStream_t stream) {
                 "gemm_skinny: the fp32-input form needs K %% 256 == 0, 16-byte aligned rows (ldx %% 4 == 0), mode 0 / 1 (with alpha) and no K split");
     RST_REQUIRE(!p.gate_out || (p.N % 32 == 0 && !p.res), "gemm_skinny: the gated epilogue needs N %% 32 == 0 and takes no residual");
     const int tiles = (p.N + 31) / 32;
-    const int threads = 64 * SKINNY_WAVES;
     const int split = p.split_k > 1 ? p.split_k : 1;
     RST_REQUIRE(split == 1 || (p.ws && p.counters && split <= 64), "gemm_skinny: split-K needs the scratch buffers (split <= 64)");
     const int ct = skinny_ct(p.B, tiles, p.K, split);
     const dim3 grid((tiles + ct - 1) / ct, split);
-    if (xf) {
-        if (p.B <= 32) {
-            if (ct == 4) hipLaunchKernelGGL((gemm_skinny_x32_kernel<1, 4>), grid, dim3(threads), 0, stream, p);
-            else if (ct == 3) hipLaunchKernelGGL((gemm_skinny_x32_kernel<1, 3>), grid, dim3(threads), 0, stream, p);
-            else if (ct == 2) hipLaunchKernelGGL((gemm_skinny_x32_kernel<1, 2>), grid, dim3(threads), 0, stream, p);
-            else hipLaunchKernelGGL((gemm_skinny_x32_kernel<1, 1>), grid, dim3(threads), 0, stream, p);
-        } else {
-            if (ct == 3) hipLaunchKernelGGL((gemm_skinny_x32_kernel<2, 3>), grid, dim3(threads), 0, stream, p);
-            else if (ct == 2) hipLaunchKernelGGL((gemm_skinny_x32_kernel<2, 2>), grid, dim3(threads), 0, stream, p);
-            else hipLaunchKernelGGL((gemm_skinny_x32_kernel<2, 1>), grid, dim3(threads), 0, stream, p);
-        }
-        return rst_check_launch("gemm_skinny_x32");
-    }
-    if (p.w8) {
-        if (p.B <= 32) {
-            if (ct == 4) hipLaunchKernelGGL((gemm_skinny_kernel<1, 4, true>), grid, dim3(threads), 0, stream, p);
-            else if (ct == 3) hipLaunchKernelGGL((gemm_skinny_kernel<1, 3, true>), grid, dim3(threads), 0, stream, p);
-            else if (ct == 2) hipLaunchKernelGGL((gemm_skinny_kernel<1, 2, true>), grid, dim3(threads), 0, stream, p);
-            else hipLaunchKernelGGL((gemm_skinny_kernel<1, 1, true>), grid, dim3(threads), 0, stream, p);
-        } else {
-            if (ct == 3) hipLaunchKernelGGL((gemm_skinny_kernel<2, 3, true>), grid, dim3(threads), 0, stream, p);
-            else if (ct == 2) hipLaunchKernelGGL((gemm_skinny_kernel<2, 2, true>), grid, dim3(threads), 0, stream, p);
-            else hipLaunchKernelGGL((gemm_skinny_kernel<2, 1, true>), grid, dim3(threads), 0, stream, p);
-        }
-        return rst_check_launch("gemm_skinny_fp8w");
-    }
-    if (p.w4) {
-        if (p.B <= 32) {
-            if (ct == 4) hipLaunchKernelGGL((gemm_skinny_kernel<1, 4, false, true>), grid, dim3(threads), 0, stream, p);
-            else if (ct == 3) hipLaunchKernelGGL((gemm_skinny_kernel<1, 3, false, true>), grid, dim3(threads), 0, stream, p);
-            else if (ct == 2) hipLaunchKernelGGL((gemm_skinny_kernel<1, 2, false, true>), grid, dim3(threads), 0, stream, p);
-            else hipLaunchKernelGGL((gemm_skinny_kernel<1, 1, false, true>), grid, dim3(threads), 0, stream, p);
-        } else {
-            if (ct == 3) hipLaunchKernelGGL((gemm_skinny_kernel<2, 3, false, true>), grid, dim3(threads), 0, stream, p);
-            else if (ct == 2) hipLaunchKernelGGL((gemm_skinny_kernel<2, 2, false, true>), grid, dim3(threads), 0, stream, p);
-            else hipLaunchKernelGGL((gemm_skinny_kernel<2, 1, false, true>), grid, dim3(threads), 0, stream, p);
-        }
-        return rst_check_launch("gemm_skinny_mxfp4w");
-    }
+    const char* what;
     if (p.B <= 32) {
-        if (ct == 4) hipLaunchKernelGGL((gemm_skinny_kernel<1, 4>), grid, dim3(threads), 0, stream, p);
-        else if (ct == 3) hipLaunchKernelGGL((gemm_skinny_kernel<1, 3>), grid, dim3(threads), 0, stream, p);
-        else if (ct == 2) hipLaunchKernelGGL((gemm_skinny_kernel<1, 2>), grid, dim3(threads), 0, stream, p);
-        else hipLaunchKernelGGL((gemm_skinny_kernel<1, 1>), grid, dim3(threads), 0, stream, p);
+        if (ct == 4) what = skinny_launch<1, 4>(p, grid, stream);
+        else if (ct == 3) what = skinny_launch<1, 3>(p, grid, stream);
+        else if (ct == 2) what = skinny_launch<1, 2>(p, grid, stream);
+        else what = skinny_launch<1, 1>(p, grid, stream);
     } else {
-        if (ct == 3) hipLaunchKernelGGL((gemm_skinny_kernel<2, 3>), grid, dim3(threads), 0, stream, p);
-        else if (ct == 2) hipLaunchKernelGGL((gemm_skinny_kernel<2, 2>), grid, dim3(threads), 0, stream, p);
-        else hipLaunchKernelGGL((gemm_skinny_kernel<2, 1>), grid, dim3(threads), 0, stream, p);
+        if (ct == 3) what = skinny_launch<2, 3>(p, grid, stream);
+        else if (ct == 2) what = skinny_launch<2, 2>(p, grid, stream);
+        else what = skinny_launch<2, 1>(p, grid, stream);
     }
-    return rst_check_launch("gemm_skinny");
+    return rst_check_launch(what);
 }
 
 // ======================================================================================================================
@@ -1000,7 +982,8 @@ __global__ __launch_bounds__(256) void skinny_pack_weight_fp8w_kernel(const unsi
 
 }  // namespace
 
-int rst_gemm_skinny_fp8w_supported_impl(int B, int N, int K) { return B >= 1 && B <= 64 && N > 0 && K > 0 && K % 32 == 0; }
+// shapes the weight-only forms (fp8 and MXFP4 alike) serve: a lane load carries two steps, K % 32 == 0
+int rst_gemm_skinny_wq_supported_impl(int B, int N, int K) { return B >= 1 && B <= 64 && N > 0 && K > 0 && K % 32 == 0; }
 
 int rst_launch_skinny_pack_weight_fp8w(const unsigned char* q, const float* scale, unsigned char* qp, float* sp, int N, int K, int interleave,
                                        hipStream_t stream) {
@@ -1045,8 +1028,6 @@ __global__ __launch_bounds__(256) void skinny_pack_weight_mxfp4w_kernel(const un
 }
 
 }  // namespace
-
-int rst_gemm_skinny_mxfp4w_supported_impl(int B, int N, int K) { return B >= 1 && B <= 64 && N > 0 && K > 0 && K % 32 == 0; }
 
 int rst_launch_skinny_pack_weight_mxfp4w(const unsigned char* q, const unsigned char* scale, unsigned char* qp, unsigned char* sp, int N, int K,
                                          int interleave, hipStream_t stream) {

@@ -539,31 +539,28 @@ int rst_launch_gemv(const GemvParams& p, hipStream_t stream) {
     const int rows_per_group = (rpw4 ? 4 : 2) * GEMV_WAVES;
     const long groups = p.gate_out ? ((long)p.N / 2 + GEMV_WAVES - 1) / GEMV_WAVES : ((long)p.N + rows_per_group - 1) / rows_per_group;
     const unsigned grid = cap_grid(groups, norm_stream ? 1024 : (lds > 48 * 1024 ? 512 : 768));
-    auto go = [&](auto kern) {
-        static RstOncePerDevice attr_once;     // one flag per kernel instantiation (generic lambda)
-        if (attr_once.first()) {
-            // static LDS (the 16-byte reduction scratch) counts against the 160 KiB budget: ask for what the check above allows
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            (void)hipGetLastError();
-        }
+    auto go = [&](auto k) {
+        constexpr auto kern = decltype(k)::fn;
+        // static LDS (the 16-byte reduction scratch) counts against the 160 KiB budget: ask for what the check above allows
+        rst_allow_dynamic_lds<kern>(128 * 1024);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * GEMV_WAVES), lds, stream, p);
     };
     if (p.w_f32) {
         switch (p.B) {
-            case 1: go(gemv_kernel<1, 2, true>); break;
-            case 2: go(gemv_kernel<2, 2, true>); break;
-            case 3: go(gemv_kernel<3, 2, true>); break;
-            default: go(gemv_kernel<4, 2, true>); break;
+            case 1: go(RstKernel<gemv_kernel<1, 2, true>>{}); break;
+            case 2: go(RstKernel<gemv_kernel<2, 2, true>>{}); break;
+            case 3: go(RstKernel<gemv_kernel<3, 2, true>>{}); break;
+            default: go(RstKernel<gemv_kernel<4, 2, true>>{}); break;
         }
         return rst_check_launch("gemv_f32");
     }
     if (p.prologue >= 4) {
         RST_REQUIRE(p.B <= 2, "gemv: the fused attention / embedding prologues serve B <= 2 (got %d)", p.B);
-        if (p.B == 1) go(gemv_kernel<1, 2, false, true>); else go(gemv_kernel<2, 2, false, true>);
+        if (p.B == 1) go(RstKernel<gemv_kernel<1, 2, false, true>>{}); else go(RstKernel<gemv_kernel<2, 2, false, true>>{});
         return rst_check_launch("gemv_fused");
     }
     if (norm_stream) {
-        if (p.gate_out) go(gemv_norm_kernel<true>); else go(gemv_norm_kernel<false>);
+        if (p.gate_out) go(RstKernel<gemv_norm_kernel<true>>{}); else go(RstKernel<gemv_norm_kernel<false>>{});
         return rst_check_launch("gemv_bf16");
     }
     // the large batch-1 layers on a plain vector: K split over the waves, activations straight into registers (gemv_ksplit_kernel)
@@ -573,14 +570,14 @@ int rst_launch_gemv(const GemvParams& p, hipStream_t stream) {
         return rst_check_launch("gemv_bf16");
     }
     switch (p.B * 2 + (rpw4 ? 1 : 0)) {
-        case 2: go(gemv_kernel<1, 2, false>); break;
-        case 3: go(gemv_kernel<1, 4, false>); break;
-        case 4: go(gemv_kernel<2, 2, false>); break;
-        case 5: go(gemv_kernel<2, 4, false>); break;
-        case 6: go(gemv_kernel<3, 2, false>); break;
-        case 7: go(gemv_kernel<3, 4, false>); break;
-        case 8: go(gemv_kernel<4, 2, false>); break;
-        default: go(gemv_kernel<4, 4, false>); break;
+        case 2: go(RstKernel<gemv_kernel<1, 2, false>>{}); break;
+        case 3: go(RstKernel<gemv_kernel<1, 4, false>>{}); break;
+        case 4: go(RstKernel<gemv_kernel<2, 2, false>>{}); break;
+        case 5: go(RstKernel<gemv_kernel<2, 4, false>>{}); break;
+        case 6: go(RstKernel<gemv_kernel<3, 2, false>>{}); break;
+        case 7: go(RstKernel<gemv_kernel<3, 4, false>>{}); break;
+        case 8: go(RstKernel<gemv_kernel<4, 2, false>>{}); break;
+        default: go(RstKernel<gemv_kernel<4, 4, false>>{}); break;
     }
     return rst_check_launch("gemv_bf16");
 }

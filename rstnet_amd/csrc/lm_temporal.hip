@@ -895,16 +895,9 @@ int rst_temporal_frame_grid(const TemporalFrameParams& p) {
 }
 
 namespace {
-// The opt-in to more than 64 KB of dynamic LDS is per kernel and per device.  The flag is keyed by the kernel itself (a template on its
-// pointer): all eight instantiations have the same function-pointer type, so a flag inside a generic lambda over `auto kern` is one flag
-// for all of them and only the first variant launched would ever get the attribute.
 template <auto KERN>
 void tf_launch(const TemporalFrameParams& pk, int grid, size_t lds, hipStream_t stream) {
-    static RstOncePerDevice attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipGetLastError();
-    }
+    rst_allow_dynamic_lds<KERN>(150 * 1024);
     hipLaunchKernelGGL(KERN, dim3(grid), dim3(TF_THREADS), lds, stream, pk);
 }
 }  // namespace

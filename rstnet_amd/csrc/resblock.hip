@@ -345,11 +345,7 @@ int launch(const ResblockParams& p, hipStream_t stream) {
     const int halo = POST ? p.Kf - 1 : 0;
     const long tiles = (long)p.B * ((p.T + (BM - halo) - 1) / (BM - halo));
     if (tiles > 0x7fffffffL) { rst_set_error("resblock: grid too large"); return RST_ERR_UNSUPPORTED; }
-    static RstOncePerDevice attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(resblock_kernel<C, BM, WM, WN, PRE, POST>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
+    rst_allow_dynamic_lds<resblock_kernel<C, BM, WM, WN, PRE, POST>>(160 * 1024);
     hipLaunchKernelGGL((resblock_kernel<C, BM, WM, WN, PRE, POST>), dim3((unsigned)tiles), dim3(256), lds, stream, p);
     return rst_check_launch("resblock");
 }
@@ -643,11 +639,7 @@ int launch64_stream(const ResblockParams& p, hipStream_t stream) {
     const long total = (long)p.B * tiles_u;
     if (total > 0x7fffffffL) { rst_set_error("resblock: grid too large"); return RST_ERR_UNSUPPORTED; }
     const int cus = rst_cu_count();
-    static RstOncePerDevice attr_once;
-    if (attr_once.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(resblock64_stream_kernel<PRE, POST>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
+    rst_allow_dynamic_lds<resblock64_stream_kernel<PRE, POST>>(160 * 1024);
     const long resident = 2L * cus;
     const unsigned grid = (unsigned)(total < resident ? total : resident);
     hipLaunchKernelGGL((resblock64_stream_kernel<PRE, POST>), dim3(grid), dim3(256), RS_LDS_FLOATS * sizeof(float), stream, p,

@@ -764,9 +764,7 @@ int launch64(const ResblockB3Params& p, hipStream_t stream) {
     const long tiles_u = (p.T + RO - 1) / RO;
     const long total = (long)p.B * tiles_u;
     if (total > 0x7ffffff0L - 8L * rst_cu_count()) { rst_set_error("resblock_b3: too many tiles (%ld)", total); return RST_ERR_UNSUPPORTED; }
-    static RstOncePerDevice attr_once;
-    if (attr_once.first())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(resblock64_b3_kernel<PRE, POST>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    rst_allow_dynamic_lds<resblock64_b3_kernel<PRE, POST>>(160 * 1024);
     const long wgs = (total + R6_WAVES - 1) / R6_WAVES;
     const long resident = rst_cu_count();
     const unsigned grid = (unsigned)(wgs < resident ? wgs : resident);
@@ -779,9 +777,7 @@ int launch128(const ResblockB3Params& p, hipStream_t stream) {
     const long tiles_u = (p.T + R8_BM - 1) / R8_BM;
     const long total = (long)p.B * tiles_u;
     if (total > 0x7fffffffL) { rst_set_error("resblock_b3: grid too large"); return RST_ERR_UNSUPPORTED; }
-    static RstOncePerDevice attr_once;
-    if (attr_once.first())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(resblock128_b3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    rst_allow_dynamic_lds<resblock128_b3_kernel>(160 * 1024);
     const long resident = rst_cu_count();
     const unsigned grid = (unsigned)(total < resident ? total : resident);
     hipLaunchKernelGGL(resblock128_b3_kernel, dim3(grid), dim3(R8_THREADS), R8_LDS, stream, p, (int)tiles_u, (int)total);

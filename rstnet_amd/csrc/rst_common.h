@@ -58,6 +58,23 @@ struct RstOncePerDevice {
         return !(mask.fetch_or(bit, std::memory_order_acq_rel) & bit);
     }
 };
+// The opt-in to more than 64 KiB of dynamic LDS is per kernel and per device: asked before every launch that may need it, set the first
+// time on each device.  The flag is keyed by the kernel itself (a template on its pointer): all instantiations of one kernel template
+// have the same function-pointer type, so a flag inside a generic lambda over `auto kern` is one flag for all of them and only the
+// first variant launched would ever get the attribute.  A launcher that picks among instantiations inside a lambda therefore takes the
+// kernel wrapped in its own type, `go(RstKernel<kern<...>>{})`, and reads it back as `decltype(k)::fn`.
+template <auto KERN>
+void rst_allow_dynamic_lds(int bytes) {
+    static RstOncePerDevice once;
+    if (once.first()) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        (void)hipGetLastError();
+    }
+}
+template <auto KERN>
+struct RstKernel {
+    static constexpr auto fn = KERN;
+};
 // CUs of the current device
 static inline int rst_cu_count() {
     static std::atomic<int> n[RST_MAX_DEVICES];

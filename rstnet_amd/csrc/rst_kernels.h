@@ -470,10 +470,9 @@ struct SkinnyParams {
     const unsigned char* w4scale;   // [ceil(N/32)][K/32][32] scale bytes e + 127 of the 32-k blocks, pad rows 127
 };
 int rst_launch_gemm_skinny(const SkinnyParams& p, hipStream_t stream);
-int rst_gemm_skinny_mxfp4w_supported_impl(int B, int N, int K);
+int rst_gemm_skinny_wq_supported_impl(int B, int N, int K);      // the weight-only forms, fp8 and MXFP4 alike
 int rst_launch_skinny_pack_weight_mxfp4w(const unsigned char* q, const unsigned char* scale, unsigned char* qp, unsigned char* sp, int N, int K,
                                          int interleave, hipStream_t stream);
-int rst_gemm_skinny_fp8w_supported_impl(int B, int N, int K);
 int rst_launch_skinny_pack_weight_fp8w(const unsigned char* q, const float* scale, unsigned char* qp, float* sp, int N, int K, int interleave,
                                        hipStream_t stream);
 int rst_skinny_bf16_split_plan_impl(int B, int N, int K);

@@ -1141,6 +1141,32 @@ def _packed_buffer(device, B: int, K: int, role: str = "in") -> torch.Tensor:
 SKINNY_X32_MAX_K = 2048
 
 
+def _gemm_skinny_packed(op: str, entry: str, x, wptrs: tuple, wbytes: int, N: int, K: int, prologue: int, alpha, eps: float, res, bias,
+                        gate_out: bool):
+    """The body of ``gemm_skinny`` (past its fp32-input form), ``gemm_skinny_fp8w`` and ``gemm_skinny_mxfp4w``: the packed activations
+    (a ``PackedAct`` as is, fp32 rows through ``skinny_pack_act``), the output, the profile row ``op`` and the launch ``entry`` on the
+    bf16 route's split plan.  ``wptrs`` (the packed weight and what goes with it) and ``wbytes`` (weight + scale bytes streamed) are
+    what the formats differ in."""
+    if isinstance(x, PackedAct):
+        assert prologue == PROLOGUE_NONE and x.K == K
+        xp, B = x.xp, x.B
+        x = xp
+    else:
+        B = x.shape[0]
+        xp = skinny_pack_act(x, prologue=prologue, alpha=alpha, eps=eps)
+    assert xp.shape[2] == K, (tuple(x.shape), N, K, prologue)
+    # gate_out: the weight is a stacked [W_u ; W_v]; the epilogue emits silu(u) * v as the packed operand of the next GEMM
+    out = None if gate_out else torch.empty(B, N, device=x.device, dtype=torch.float32)
+    gp = _packed_buffer(x.device, B, N // 2, "gate") if gate_out else None
+    with _profiled(op, 2.0 * B * N * K, wbytes + 4 * (x.numel() + B * N), (B, N, K)):
+        # one launch plan and scratch for every weight format (same shape key: launches on one stream are ordered)
+        sc = _split_scratch(xp.device, ("skinny_bf16", B, N, K), lambda: _lib.lib().rst_skinny_bf16_split_plan(B, N, K),
+                            (B + 31) // 32 * 32, N, lambda: (N + 31) // 32)
+        _lib.check(getattr(_lib.lib(), entry)(_ptr(xp), *wptrs, _ptr(res), _ptr(bias), _ptr(out), B, N, K, N, _ptr(gp),
+                                              sc[0], _ptr(sc[1]), _ptr(sc[2]), _stream()))
+    return PackedAct(gp, B, N // 2) if gate_out else out
+
+
 @_on_tensor_device
 def gemm_skinny(x, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Optional[torch.Tensor] = None,
                 eps: float = 1e-8, res: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, gate_out: bool = False):
@@ -1167,23 +1193,7 @@ def gemm_skinny(x, w: torch.Tensor, *, prologue: int = PROLOGUE_NONE, alpha: Opt
                                                               1 if prologue == PROLOGUE_RMSNORM else 0, x.stride(0) if B > 1 else K, _ptr(wp),
                                                               _ptr(res), _ptr(bias), _ptr(out), B, N, K, N, _ptr(gp), _stream()))
         return PackedAct(gp, B, N // 2) if gate_out else out
-    if isinstance(x, PackedAct):
-        assert prologue == PROLOGUE_NONE and x.K == K
-        xp, B = x.xp, x.B
-        x = xp
-    else:
-        B = x.shape[0]
-        xp = skinny_pack_act(x, prologue=prologue, alpha=alpha, eps=eps)
-    assert xp.shape[2] == K, (tuple(x.shape), N, K, prologue)
-    # gate_out: w is a stacked [W_u ; W_v]; the epilogue emits silu(u) * v as the packed operand of the next GEMM
-    out = None if gate_out else torch.empty(B, N, device=x.device, dtype=torch.float32)
-    gp = _packed_buffer(x.device, B, N // 2, "gate") if gate_out else None
-    with _profiled("gemm_skinny", 2.0 * B * N * K, 2 * N * K + 4 * (x.numel() + B * N), (B, N, K)):
-        sc = _split_scratch(xp.device, ("skinny_bf16", B, N, K), lambda: _lib.lib().rst_skinny_bf16_split_plan(B, N, K),
-                            (B + 31) // 32 * 32, N, lambda: (N + 31) // 32)
-        _lib.check(_lib.lib().rst_gemm_skinny_bf16_f32(_ptr(xp), _ptr(wp), _ptr(res), _ptr(bias), _ptr(out), B, N, K, N, _ptr(gp),
-                                                      sc[0], _ptr(sc[1]), _ptr(sc[2]), _stream()))
-    return PackedAct(gp, B, N // 2) if gate_out else out
+    return _gemm_skinny_packed("gemm_skinny", "rst_gemm_skinny_bf16_f32", x, (_ptr(wp),), 2 * N * K, N, K, prologue, alpha, eps, res, bias, gate_out)
 
 
 _skinny_weights_fp8w = _PackedWeights()
@@ -1234,21 +1244,8 @@ def gemm_skinny_fp8w(x, q: torch.Tensor, scale: torch.Tensor, *, prologue: int =
                          "(1 <= B <= 64 and K % 32 == 0 required)")
     gate_out = gate_out and N % 32 == 0 and res is None
     qp, sp = skinny_pack_weight_fp8w(q, scale, interleave_halves=gate_out)
-    if isinstance(x, PackedAct):
-        assert prologue == PROLOGUE_NONE and x.K == K
-        xp = x = x.xp
-    else:
-        xp = skinny_pack_act(x, prologue=prologue, alpha=alpha, eps=eps)
-    assert xp.shape[2] == K, (tuple(x.shape), N, K, prologue)
-    out = None if gate_out else torch.empty(B, N, device=xp.device, dtype=torch.float32)
-    gp = _packed_buffer(xp.device, B, N // 2, "gate") if gate_out else None
-    with _profiled("gemm_skinny_fp8w", 2.0 * B * N * K, N * K + 4 * N + 4 * (x.numel() + B * N), (B, N, K)):
-        # the launch plan and its scratch are the bf16 route's (same shape key: launches on one stream are ordered)
-        sc = _split_scratch(xp.device, ("skinny_bf16", B, N, K), lambda: _lib.lib().rst_skinny_bf16_split_plan(B, N, K),
-                            (B + 31) // 32 * 32, N, lambda: (N + 31) // 32)
-        _lib.check(_lib.lib().rst_gemm_skinny_fp8w_f32(_ptr(xp), _ptr(qp), _ptr(sp), _ptr(res), _ptr(bias), _ptr(out), B, N, K, N, _ptr(gp),
-                                                      sc[0], _ptr(sc[1]), _ptr(sc[2]), _stream()))
-    return PackedAct(gp, B, N // 2) if gate_out else out
+    return _gemm_skinny_packed("gemm_skinny_fp8w", "rst_gemm_skinny_fp8w_f32", x, (_ptr(qp), _ptr(sp)), N * K + 4 * N, N, K, prologue, alpha, eps,
+                               res, bias, gate_out)
 
 
 _skinny_weights_mxfp4w = _PackedWeights()
@@ -1299,21 +1296,8 @@ def gemm_skinny_mxfp4w(x, q: torch.Tensor, scale: torch.Tensor, *, prologue: int
                          "(1 <= B <= 64 and K % 32 == 0 required)")
     gate_out = gate_out and N % 32 == 0 and res is None
     qp, sp = skinny_pack_weight_mxfp4w(q, scale, interleave_halves=gate_out)
-    if isinstance(x, PackedAct):
-        assert prologue == PROLOGUE_NONE and x.K == K
-        xp = x = x.xp
-    else:
-        xp = skinny_pack_act(x, prologue=prologue, alpha=alpha, eps=eps)
-    assert xp.shape[2] == K, (tuple(x.shape), N, K, prologue)
-    out = None if gate_out else torch.empty(B, N, device=xp.device, dtype=torch.float32)
-    gp = _packed_buffer(xp.device, B, N // 2, "gate") if gate_out else None
-    with _profiled("gemm_skinny_mxfp4w", 2.0 * B * N * K, N * K // 2 + N * K // 32 + 4 * (x.numel() + B * N), (B, N, K)):
-        # the launch plan and its scratch are the bf16 route's (same shape key: launches on one stream are ordered)
-        sc = _split_scratch(xp.device, ("skinny_bf16", B, N, K), lambda: _lib.lib().rst_skinny_bf16_split_plan(B, N, K),
-                            (B + 31) // 32 * 32, N, lambda: (N + 31) // 32)
-        _lib.check(_lib.lib().rst_gemm_skinny_mxfp4w_f32(_ptr(xp), _ptr(qp), _ptr(sp), _ptr(res), _ptr(bias), _ptr(out), B, N, K, N, _ptr(gp),
-                                                        sc[0], _ptr(sc[1]), _ptr(sc[2]), _stream()))
-    return PackedAct(gp, B, N // 2) if gate_out else out
+    return _gemm_skinny_packed("gemm_skinny_mxfp4w", "rst_gemm_skinny_mxfp4w_f32", x, (_ptr(qp), _ptr(sp)), N * K // 2 + N * K // 32, N, K,
+                               prologue, alpha, eps, res, bias, gate_out)
 
 
 _skinny_weights_fp8 = _PackedWeights()
