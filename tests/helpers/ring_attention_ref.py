@@ -1,5 +1,6 @@
 """The launch-per-op ring attention (csrc/lm_attn.hip behind ops.lm_attn_decode and ops.attention(ring=True), csrc/lm_prefill.hip behind
-ops.lm_attn_prefill / ops.lm_ring_append[_ragged], the short-ring prologue of rst_gemv_attn_bf16_f32 behind ops.gemv_attn) restated for
+ops.lm_attn_prefill / ops.lm_ring_append[_ragged], the short-ring prologue of rst_gemv_attn_bf16_f32 behind ops.gemv_attn, and the tile
+walk of csrc/attention.hip that ops.attention(ring=True) takes with more than 8 queries or a head dim of 32: the `walk-` cases) restated for
 tests that hold every launch to fp64 at DESIGNED scores: the case table, a builder of the ring as that many single steps would have
 left it, the score profiles and the poison, a reference of the window definition in any dtype that can carry one named defect, the
 launchers' dispatch (`instance`) and the acceptance function.  Nothing here needs a GPU until `device_run` is called;
@@ -37,7 +38,8 @@ group's rows: independent randn values, an O(1) error for a query head that read
 Bound, per (stream, query, head) vector and element: |got_i - ref64_i| <= tol sum_j p_j |v_ji|, p the fp64 probabilities.
 tol = max(16 r32, t_op) within [2^-18, 1e-3]; r32 the same ratio of the fp32 run of `reference` on the same operands.  t_op, from the
 code:
-  * attn_small / attn_decode / attn_decode_dense / prefill_attn_f32 / gemv prologue: fp32 FMAs on the stored bytes: 0.
+  * attn_small / attn_decode / attn_decode_dense / prefill_attn_f32 / gemv prologue / attention_kernel's ring walk: fp32 FMAs (fp32
+    MFMAs) on the stored bytes: 0.
   * packed output (store_packed8): the result leaves as bf16 hi + lo, |x - hi - lo| <= 2^-16 |x| (lm_common.h): 2^-16.
   * prefill_attn_bf16_kernel: Q enters the score MFMA as hi + lo planes, so score j is off by at most 2^-16 sum_i |q_i k_ji| / sqrt(D)
     =: e_j; a weight exp(s_j - M) / L moves by e_j in the numerator and max e in L: 2 max_j e_j relative.  The probabilities enter the
@@ -154,7 +156,15 @@ CASES = (
     # -- ops.attention(ring=True) with T > 1 (`lm/stack.py`): queries already rotated, keys already in the ring
     Case("qpre-d64", "qpre", 2, 2, 2, 64, 130, None, "f32", (0, 50, 127, 300), T=3, profiles=("flat",) + PEAKS),
     Case("qpre-d128-gqa", "qpre", 2, 4, 2, 128, 300, 100, "f32", (40, 298, 905), T=2, profiles=("flat",) + PEAKS),
+    # -- the same entry past the few-query path (T > 8, or D = 32 at any T): attention_kernel<D> of csrc/attention.hip walks the ring in
+    # 32-slot tiles.  An empty ring, a filling one, a chunk across the wrap, a ring wrapped twice; T = cap, where slot end_offset % cap
+    # is the FIRST query's own key and counts as the future (that query sees nothing: the launch returns 0 for it)
+    Case("walk-c250-d64-t12", "qpre", 2, 2, 2, 64, 250, 250, "f32", (0, 100, 245, 738), T=12),
+    Case("walk-c70-d128-t40", "qpre", 2, 2, 2, 128, 70, None, "f32", (0, 50, 200), T=40),
+    Case("walk-c10-d32-t3", "qpre", 2, 2, 2, 32, 10, 7, "f32", (0, 8, 25), T=3),
+    Case("walk-c33-d64-t33", "qpre", 2, 2, 2, 64, 33, None, "f32", (0, 40), T=33),
 )
+WALK_CASES = tuple(c.name for c in CASES if c.name.startswith("walk-"))
 BY_NAME = {c.name: c for c in CASES}
 
 # Every kernel instance (template arguments) the three launchers reach, plus the run-time forms the issue names
@@ -163,7 +173,7 @@ REACHABLE = frozenset(
     [f"{k}<{D},{kv}>" for k in ("attn_decode", "attn_decode_dense") for D in (64, 128) for kv in ("f32", "bf16")] +
     [f"prefill_attn_{kv}<{D}>" for kv in ("f32", "bf16") for D in (64, 128)] + ["stage<f32>", "stage<bf16>", "stage<f32>:ring", "stage<bf16>:ring"] +
     ["gemv_attn<1>", "gemv_attn<2>", "q_pre:T>1<64>", "q_pre:T>1<128>", "splits>8", "splits=1", "splits=2", "per_stream", "rope_table", "packed",
-     "gqa2", "gqa4", "ragged", "rope_dims<D"])
+     "gqa2", "gqa4", "ragged", "rope_dims<D"] + [f"attention<{D}>:ring" for D in (32, 64, 128)])
 
 
 def resolve(case, cus):
@@ -196,12 +206,17 @@ def instance(case, cus, pos=None):
             names.add("ragged")
     else:
         T = c.T if c.entry == "qpre" else 1
-        if c.entry == "qpre":          # ops.attention: the few-query ring path
-            assert T <= 8 or c.G != c.H
-            out.splits = max(1, min(4, c.cap // 64, 1024 // max(1, c.B * T * c.H)))
+        walk = False
+        if c.entry == "qpre":          # ops.attention: the few-query ring path, else the tile walk of attention_kernel<D>
+            walk = not ((T <= 8 or c.G != c.H) and c.D in (64, 128))
+            assert not walk or c.G == c.H, "grouped key/value heads are served by the few-query path only"
+            out.splits = 1 if walk else max(1, min(4, c.cap // 64, 1024 // max(1, c.B * T * c.H)))
         else:
             out.splits = 1 if c.cap <= 64 else lm_attn_splits(c.cap, c.B * c.H)
-        if c.entry == "decode" and c.cap <= 64 and out.splits == 1:
+        if walk:
+            out.kernel = f"attention<{c.D}>:ring"
+            out.unit = 32
+        elif c.entry == "decode" and c.cap <= 64 and out.splits == 1:
             assert kv == "f32", "bf16 rings are served by the long-ring form only"
             out.kernel = f"attn_small<{c.D}>"
         else:

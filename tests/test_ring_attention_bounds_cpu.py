@@ -86,7 +86,8 @@ def test_ring_by_position_is_the_stepped_ring():
                 content, pos_k = _stepped_cached(c.cap)
                 qs = R.queries(c, P)
                 for t, rows in enumerate(qs):
-                    assert any(r[2] == P + t for r in rows), "the query's own key"
+                    # (a chunk of a whole ring: the first query's slot is end_offset % cap, the future -- that query sees nothing)
+                    assert any(r[2] == P + t for r in rows) or (c.entry == "qpre" and c.T == c.cap and t == 0 and not rows), "the query's own key"
                     n_ring = P + c.T if c.entry == "qpre" else P
                     for kind, i, p in rows:
                         if kind == "ring":
@@ -130,6 +131,9 @@ def test_designed_scores_after_rounding():
         for bi in range(c.B):
             d = b.designed[bi]
             for t in R.live_queries(c, bi):
+                if c.entry == "qpre" and c.T == c.cap and t == 0:          # sees nothing (its own slot counts as the future): the launch returns 0
+                    assert (bi, t) not in ref.scores and float(ref.out[bi, t].abs().max()) == 0.0
+                    continue
                 sc, rows, _ = ref.scores[bi, t]
                 where = (c.name, profile, position, bi, t)
                 assert float(sc.abs().max()) <= 100.0, where

@@ -18,7 +18,9 @@ Worst quotient (kernel ratio / tol) per case over its profiles and positions, MI
   pf-t33-w299-d128-bf16 0.100;  pf-t33-w299-d64-f32 0.216;  pf-t33-w299-d64-bf16 0.060;  pf-t70-w69-d64-f32 0.172;
   pf-t70-w69-d64-bf16 0.064;  pf-t33-w140-d128-gqa-f32 0.209;  pf-t33-w140-d128-gqa-bf16 0.049;  pf-t33-w140-d64-gqa4-f32 0.178;
   pf-t33-w140-d64-gqa4-bf16 0.020;  pf-ragged-d64-f32 0.225;  pf-ragged-d64-bf16 0.016;  pf-ragged-d128-f32 0.230;
-  pf-ragged-d128-bf16 0.055;  qpre-d64 0.029;  qpre-d128-gqa 0.032.
+  pf-ragged-d128-bf16 0.055;  qpre-d64 0.029;  qpre-d128-gqa 0.032;
+  (added with tests/test_utterance_attention_bounds_gpu.py: ops.attention(ring=True) past the few-query path, attention_kernel<D> of
+  csrc/attention.hip)  walk-c250-d64-t12 0.251;  walk-c70-d128-t40 0.238;  walk-c10-d32-t3 0.149;  walk-c33-d64-t33 0.087.
 No launch saw a poisoned slot, none produced a non-finite value, and no kernel was changed.  The two cases near 1 leave through the
 packed bf16 hi + lo output, whose own 2^-16 IS their tolerance (t_op); the rotating cases sit at 0.15 - 0.5 of the 2^-18 floor because
 the launch's expf frequency differs from the reference's by an ulp (the helper's docstring: why they stay at positions <= 22).  The
