@@ -296,6 +296,12 @@ int rst_hist_update_f32(const float* x, const float* hist_in, float* hist_out, i
 int rst_hist_update_batch_f32(const float* const* x, float* const* hist, const int* T_in, const int* P, const int* C, int n, int B,
                               rst_stream_t stream);
 
+/* A stream of a live batch starts over: for every b with fresh[b] != 0 (device int32 [B]) the history row hist[b] [P][C] becomes what a
+ * new session's first chunk finds -- P copies of x[b][0][:] (replicate != 0: the replicate padding of StreamingConv1d, modules/conv.py:
+ * 249-253, x [B][T_in][C] being that first chunk) or zeros -- and fresh[b] is cleared; rows with fresh[b] == 0 are not touched.  Runs in
+ * front of the convolution inside a captured frame: which rows it rewrites is decided by the flags at replay time. */
+int rst_hist_seed_f32(const float* x, float* hist, int32_t* fresh, int B, int T_in, int P, int C, int replicate, rst_stream_t stream);
+
 /* rst_codec_transformer_frame -- ONE streaming step of a Mimi transformer (ProjectedTransformer / StreamingTransformer with all its
  * StreamingTransformerLayers, modules/transformer.py:434-750, as MimiModel calls it per 80 ms frame: compression.py:368-419) as one
  * persistent launch, for B streams x T new positions with B * T <= 4 rows: per layer LayerNorm(eps) -> in_proj [3E][E] ->
@@ -703,6 +709,11 @@ int rst_attn_decode_multi_f32(const float* q, const float* k, const float* v, fl
 int rst_attention_step_supported(int T, int D, int cap);
 int rst_attention_step_f32(const float* qkv, float* k, float* v, float* out, const int64_t* pos_dev, int B, int T, int H, int D, int cap,
                            int context, int rope, float rope_coef, int out_packed_rows, rst_stream_t stream);
+/* The same with one position per stream: stream b stands at pos_dev[b * pos_stride] (int64 [B] at pos_stride == 1), which sets its ring
+ * slots, its rotation angles, how much of its ring is in use and which slots its queries see -- so a stream at position 0 reads nothing of
+ * what an earlier conversation left in its ring.  pos_stride == 0 is rst_attention_step_f32, which forwards here. */
+int rst_attention_step_ps_f32(const float* qkv, float* k, float* v, float* out, const int64_t* pos_dev, int pos_stride, int B, int T, int H,
+                              int D, int cap, int context, int rope, float rope_coef, int out_packed_rows, rst_stream_t stream);
 
 /* sample_token (utils/sampling.py:85-105): greedy argmax, or softmax(logits/temp) -> top-k (sorted descending) ->
  * argmax_j p_j / noise_j with caller-provided Exp(1) noise [B][noise_stride] (the reference draws it with
@@ -736,6 +747,14 @@ int rst_lm_ring_begin_i64(int64_t* cache, const int64_t* user_tokens, const int6
                           int64_t* offset_dev, int64_t* input_out, int B, int K, int CT, int Ki, int first_user_k, rst_stream_t stream);
 int rst_lm_ring_commit_i64(int64_t* cache, const int64_t* tokens, const int32_t* delays, int64_t* offset_dev, int64_t* out, int B, int K,
                            int CT, int n_out, int max_delay, rst_stream_t stream);
+/* The same with one frame counter per stream: stream b reads (and commit increments) offset_dev[b * offset_stride], int64 [B] at
+ * offset_stride == 1 -- a stream of a live batch that started over gets its initial tokens while ITS offset <= delay_k, its own ring
+ * column and its own increment.  offset_stride == 0 is the pair above, which forwards here. */
+int rst_lm_ring_begin_ps_i64(int64_t* cache, const int64_t* user_tokens, const int64_t* initial, const int32_t* delays,
+                             int64_t* offset_dev, int offset_stride, int64_t* input_out, int B, int K, int CT, int Ki, int first_user_k,
+                             rst_stream_t stream);
+int rst_lm_ring_commit_ps_i64(int64_t* cache, const int64_t* tokens, const int32_t* delays, int64_t* offset_dev, int offset_stride,
+                              int64_t* out, int B, int K, int CT, int n_out, int max_delay, rst_stream_t stream);
 
 #ifdef __cplusplus
 }

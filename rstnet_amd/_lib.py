@@ -52,6 +52,7 @@ SIGNATURES = {
     "rst_transpose_f32": [_p, _p, _i, _i, _i, _p],
     "rst_hist_update_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _p],
     "rst_hist_update_batch_f32": [C.POINTER(_p), C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _i, _p],
+    "rst_hist_seed_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _p],
     "rst_skinny_f32_pack_weight": [_p, _p, _i, _i, _p],
     "rst_skinny_f32_pack_win": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _l, _i, _p],
     "rst_skinny_f32_pack_ln": [_p, _p, _p, _f, _p, _i, _i, _p],
@@ -116,11 +117,14 @@ SIGNATURES = {
     "rst_attn_decode_multi_f32":[_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "rst_attention_step_supported": [_i, _i, _i],
     "rst_attention_step_f32": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p],
+    "rst_attention_step_ps_f32": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p],
     "rst_lm_sample_workspace_bytes": [_i, _i, _i, _i],
     "rst_lm_sample_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p, _f, _p, _l, _p],
     "rst_lm_sample_rows_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p, _i, _f, _p, _l, _p],
     "rst_lm_ring_begin_i64": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "rst_lm_ring_commit_i64": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "rst_lm_ring_begin_ps_i64": [_p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
+    "rst_lm_ring_commit_ps_i64": [_p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],
 }
 
 _lib: Optional[C.CDLL] = None

@@ -178,11 +178,22 @@ class StreamResampler:
         self.filt = None if self.o == self.n else device_table(self.o, self.n, device)
         self.buf = torch.zeros(self.batch_size, self.hist + self.frame_in, device=device, dtype=torch.float32)
         self.out = torch.zeros(self.batch_size, self.frame_out, device=device, dtype=torch.float32)
-        self.fresh = torch.ones(1, 1, device=device, dtype=torch.bool)         # no step since the last reset
+        self.fresh = torch.ones(self.batch_size, 1, device=device, dtype=torch.bool)     # per stream: no step since its last reset
 
     def reset(self) -> None:
         self.buf.zero_()
         self.fresh.fill_(True)
+
+    def reset_rows(self, rows) -> None:
+        """Streams ``rows`` start over with the next step (their history zeroed, their first ``delay_out`` outputs masked again); the
+        others go on.  In place: a captured step stays valid."""
+        rows = sorted({int(r) for r in rows})
+        bad = [r for r in rows if not 0 <= r < self.batch_size]
+        if bad:
+            raise ValueError(f"reset_rows: rows {bad} are outside the batch of {self.batch_size} streams")
+        if rows:
+            self.buf[rows] = 0.0
+            self.fresh[rows] = True
 
     def step(self, chunk: torch.Tensor) -> torch.Tensor:
         """``chunk [B, 1, frame_in]`` fp32 -> ``[B, 1, frame_out]`` (a view of the persistent output)."""

@@ -22,7 +22,7 @@ from dataclasses import dataclass, field
 
 from .. import ops
 from ..graphs import Graphed
-from .streaming import StreamingModule
+from .streaming import StreamingModule, check_rows, reset_stream_rows
 
 
 @dataclass
@@ -31,6 +31,8 @@ class _MimiState:
     enc: dict = field(default_factory=dict)
     dec: dict = field(default_factory=dict)
     calls: int = 0
+    batch_size: int = 0
+    per_stream: bool = False
 
     def reset(self) -> None:
         self.enc.clear()
@@ -81,7 +83,29 @@ class MimiCodec(StreamingModule[_MimiState]):
         self.frame_hop = self.hop_length * stride  # samples per code frame (1920 for Mimi)
 
     def _init_streaming_state(self, batch_size: int) -> _MimiState:
-        return _MimiState()
+        return _MimiState(batch_size=batch_size, per_stream=self._streaming_per_stream)
+
+    def reset_streams(self, rows, side: str = "both") -> None:
+        """Streams ``rows`` of a per-stream session (``streaming(batch_size, per_stream=True)``) start over with their next frame: their
+        convolution histories, transformer positions and the down-sampler's padding become those of a new session, on the ``"encoder"``
+        side, the ``"decoder"`` side or ``"both"``; the other streams do not notice.  Eager in-place writes between two steps: the captured
+        encode / decode graphs stay valid.  From then on a reset stream's codes / waveform equal those of a new session fed the same frames."""
+        state = self._streaming_state
+        if state is None:
+            raise RuntimeError("reset_streams outside a streaming session")
+        if not state.per_stream:
+            raise ValueError("reset_streams needs a per-stream session: open it with streaming(batch_size, per_stream=True)")
+        if side not in ("both", "encoder", "decoder"):
+            raise ValueError(f"side must be 'both', 'encoder' or 'decoder', got {side!r}")
+        rows = check_rows(rows, state.batch_size)
+        if not rows:
+            return
+        if side in ("both", "encoder"):
+            for m in (self.encoder, self.encoder_transformer, self.downsample):
+                reset_stream_rows(m, rows)
+        if side in ("both", "decoder"):
+            for m in (self.upsample, self.decoder_transformer, self.decoder):
+                reset_stream_rows(m, rows)
 
     # ------------------------------------------------------------------ reference API
     def forward(self, audio_data: torch.Tensor, semantic_features: torch.Tensor):

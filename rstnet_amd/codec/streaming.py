@@ -11,7 +11,7 @@ from __future__ import annotations
 import abc
 from contextlib import contextmanager
 from dataclasses import dataclass
-from typing import Any, Callable, Dict, Generic, Optional, TypeVar
+from typing import Any, Callable, Dict, Generic, List, Optional, Sequence, TypeVar
 
 import torch
 from torch import nn
@@ -19,11 +19,34 @@ from torch import nn
 State = TypeVar("State")
 
 
+def check_rows(rows: Sequence[int], batch_size: int) -> List[int]:
+    """The streams of a ``reset_streams(rows)`` call as a sorted list of distinct ints; ``ValueError`` for a row outside the batch."""
+    out = sorted({int(r) for r in rows})
+    bad = [r for r in out if not 0 <= r < batch_size]
+    if bad:
+        raise ValueError(f"reset_streams: rows {bad} are outside the batch of {batch_size} streams")
+    return out
+
+
+def reset_stream_rows(module: nn.Module, rows: Sequence[int]) -> None:
+    """Streams ``rows`` of every live streaming state under ``module`` go back to what a new session holds (the state's ``reset_rows``:
+    history rows zeroed or flagged for re-seeding, positions to 0), in place and eagerly: tensors keep their addresses, so a captured
+    frame that points at them stays valid and sees the new rows on its next replay.  The other streams' bytes are not touched."""
+    for m in module.modules():
+        if isinstance(m, StreamingModule) and m._streaming_state is not None:
+            fn = getattr(m._streaming_state, "reset_rows", None)
+            if fn is not None:
+                fn(rows)
+
+
 class StreamingModule(abc.ABC, nn.Module, Generic[State]):
     def __init__(self) -> None:
         super().__init__()
         self._streaming_state: Optional[State] = None
         self._streaming_propagate: bool = True
+        # the live session keeps one position / history seed per stream (``streaming(batch_size, per_stream=True)``): any row can then be
+        # reset between two steps while the others go on (``reset_stream_rows``); read by ``_init_streaming_state``
+        self._streaming_per_stream: bool = False
 
     @property
     def is_streaming(self) -> bool:
@@ -54,22 +77,30 @@ class StreamingModule(abc.ABC, nn.Module, Generic[State]):
     def _init_streaming_state(self, batch_size: int) -> State:
         ...
 
-    def _start_streaming(self, batch_size: int) -> None:
+    def _start_streaming(self, batch_size: int, per_stream: bool = False) -> None:
         def start(_: str, m: "StreamingModule") -> None:
+            m._streaming_per_stream = bool(per_stream)
             m._streaming_state = m._init_streaming_state(batch_size)
-        self._apply_named_streaming(start)
+        try:
+            self._apply_named_streaming(start)
+        except Exception:
+            self._stop_streaming()      # (a module that does not serve the session's mode refuses it: leave nothing half open)
+            raise
 
     def _stop_streaming(self) -> None:
         def stop(_: str, m: "StreamingModule") -> None:
             m._streaming_state = None
+            m._streaming_per_stream = False
         self._apply_named_streaming(stop)
 
-    def streaming_forever(self, batch_size: int) -> None:
-        self._start_streaming(batch_size)
+    def streaming_forever(self, batch_size: int, per_stream: bool = False) -> None:
+        self._start_streaming(batch_size, per_stream)
 
     @contextmanager
-    def streaming(self, batch_size: int):
-        self._start_streaming(batch_size)
+    def streaming(self, batch_size: int, per_stream: bool = False):
+        """``per_stream``: every stateful module keeps one position per stream instead of one for the batch, so that single streams can
+        be reset while the session runs (``MimiCodec.reset_streams``, ``LMGen.reset_streams``); off, nothing changes."""
+        self._start_streaming(batch_size, per_stream)
         try:
             yield
         finally:
@@ -121,6 +152,11 @@ class _StreamingAddState:
     def reset(self) -> None:
         self.previous_x = None
         self.previous_y = None
+
+    def reset_rows(self, rows) -> None:
+        for t in (self.previous_x, self.previous_y):
+            if t is not None and t.numel():
+                raise RuntimeError("StreamingAdd holds back a surplus: its streams cannot be reset one by one")
 
 
 class StreamingAdd(StreamingModule[_StreamingAddState]):

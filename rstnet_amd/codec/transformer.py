@@ -79,13 +79,21 @@ class RotaryEmbedding(nn.Module):
 class _MHAState:
     k_cache: torch.Tensor   # [B, H, capacity, D]
     v_cache: torch.Tensor
-    offset: torch.Tensor    # int64 [1] on device (kept for API parity / graph capture)
+    offset: torch.Tensor    # int64 [1] on device (kept for API parity / graph capture); per-stream session: int64 [B]
     offset_cpu: int
     shared: Optional[torch.Tensor] = None   # the enclosing transformer's counter: one increment per step instead of one per layer
+    per_stream: bool = False                # one position per stream: the step is always ops.attention_step_ps
 
     def reset(self) -> None:
         self.offset.zero_()
         self.offset_cpu = 0
+
+    def reset_rows(self, rows) -> None:
+        """Those streams stand at position 0 again.  Their ring rows are left as they are: at position 0 the step kernel loads no slot at
+        or past the part of the ring the stream has written since."""
+        if not self.per_stream:
+            raise ValueError("reset_streams needs a per-stream session: open it with streaming(batch_size, per_stream=True)")
+        self.offset[list(rows)] = 0
 
 
 class StreamingMultiheadAttention(StreamingModule[_MHAState]):
@@ -116,8 +124,12 @@ class StreamingMultiheadAttention(StreamingModule[_MHAState]):
         dev = self.in_proj_weight.device
         D = self.embed_dim // self.num_heads
         shape = (batch_size, self.num_heads, capacity, D)
+        per_stream = self._streaming_per_stream
+        if per_stream and (self.weights_per_step or not ops.attention_step_serves(1, D, capacity)):
+            raise ValueError(f"per-stream session: the one-launch attention step does not serve head size {D} on a ring of {capacity} slots"
+                             + (" with per-step weights" if self.weights_per_step else "") + " (ops.attention_step_supported)")
         return _MHAState(torch.zeros(shape, device=dev, dtype=torch.float32), torch.zeros(shape, device=dev, dtype=torch.float32),
-                         torch.zeros(1, device=dev, dtype=torch.long), 0)
+                         torch.zeros(batch_size if per_stream else 1, device=dev, dtype=torch.long), 0, per_stream=per_stream)
 
     def _project(self, weight: torch.Tensor, x: torch.Tensor, offset: int, ln=None, **epilogue) -> torch.Tensor:
         if not self.weights_per_step:
@@ -155,7 +167,16 @@ class StreamingMultiheadAttention(StreamingModule[_MHAState]):
         else:
             # position from the device-side counter (graph-replay safe), mirrored on the host in offset_cpu
             pos_dev = state.shared if state.shared is not None else state.offset
-            if ops.attention_step_supported(qkv, H, state.k_cache.shape[2]):
+            if state.per_stream:
+                # one position per stream: the one-launch step is the only form that reads them (no persistent frame, no two-launch fallback)
+                if not ops.attention_step_supported(qkv, H, state.k_cache.shape[2]):
+                    raise ValueError(f"per-stream session: the one-launch attention step does not serve {T} new positions of head size "
+                                     f"{qkv.shape[2] // (3 * H)} on a ring of {state.k_cache.shape[2]} slots")
+                E = self.embed_dim
+                packed = ops.ATTENTION_STEP_PACKED and B * T > 4 and ops._few_rows(B * T, self.out_proj.weight.shape[0], E) and E % 8 == 0
+                a = ops.attention_step_ps(qkv, H, state.k_cache, state.v_cache, pos_dev, context=self.context, rope=use_rope, max_period=period,
+                                          out_packed=packed)
+            elif ops.attention_step_supported(qkv, H, state.k_cache.shape[2]):
                 # a few new positions: split, rotation, ring append and the queries against the ring in one launch
                 # (on the few-row route the result is written as the out-projection's packed operand)
                 E = self.embed_dim
@@ -242,10 +263,16 @@ class StreamingTransformerLayer(StreamingModule[_LayerState]):
 
 @dataclass
 class _TransformerState:
-    offset: torch.Tensor
+    offset: torch.Tensor          # int64 [1]: the position every layer reads; per-stream session: int64 [B]
+    per_stream: bool = False
 
     def reset(self) -> None:
         self.offset.zero_()
+
+    def reset_rows(self, rows) -> None:
+        if not self.per_stream:
+            raise ValueError("reset_streams needs a per-stream session: open it with streaming(batch_size, per_stream=True)")
+        self.offset[list(rows)] = 0
 
 
 class StreamingTransformer(StreamingModule[_TransformerState]):
@@ -268,14 +295,15 @@ class StreamingTransformer(StreamingModule[_TransformerState]):
 
     def _init_streaming_state(self, batch_size: int) -> _TransformerState:
         device = next(self.parameters()).device
-        return _TransformerState(offset=torch.zeros(1, device=device, dtype=torch.long))
+        per_stream = self._streaming_per_stream
+        return _TransformerState(offset=torch.zeros(batch_size if per_stream else 1, device=device, dtype=torch.long), per_stream=per_stream)
 
     def _frame_layers(self, x: torch.Tensor):
         """The per-layer tensors of ``ops.codec_transformer_frame`` if this streaming step can run as ONE persistent launch (a few
         rows, plain layers with attention + GELU FFN + LayerNorm, all of them streaming), else None."""
         state = self._streaming_state
-        if state is None or not x.is_cuda or x.dtype != torch.float32 or not self.layers:
-            return None
+        if state is None or state.per_stream or not x.is_cuda or x.dtype != torch.float32 or not self.layers:
+            return None         # (the persistent launch knows one position per call)
         out = []
         for layer in self.layers:
             att = getattr(layer, "self_attn", None)

@@ -303,13 +303,22 @@ int rst_linear_few_rows_f32(const float* x, int ldx, const float* wp, const floa
 
 int rst_attention_step_supported(int T, int D, int cap) { return rst_attn_step_supported_impl(T, D, cap); }
 
-int rst_attention_step_f32(const float* qkv, float* k, float* v, float* out, const int64_t* pos_dev, int B, int T, int H, int D, int cap,
-                           int context, int rope, float rope_coef, int out_packed_rows, rst_stream_t stream) {
+int rst_attention_step_ps_f32(const float* qkv, float* k, float* v, float* out, const int64_t* pos_dev, int pos_stride, int B, int T, int H,
+                              int D, int cap, int context, int rope, float rope_coef, int out_packed_rows, rst_stream_t stream) {
     AttnStepParams p = {};
     p.out_rows = out_packed_rows;
-    p.qkv = qkv; p.k = k; p.v = v; p.out = out; p.pos_dev = reinterpret_cast<const long*>(pos_dev);
+    p.qkv = qkv; p.k = k; p.v = v; p.out = out; p.pos_dev = reinterpret_cast<const long*>(pos_dev); p.pos_stride = pos_stride;
     p.B = B; p.T = T; p.H = H; p.D = D; p.cap = cap; p.context = context; p.rope = rope; p.rope_coef = rope_coef;
     return rst_launch_attn_step(p, (hipStream_t)stream);
+}
+
+int rst_attention_step_f32(const float* qkv, float* k, float* v, float* out, const int64_t* pos_dev, int B, int T, int H, int D, int cap,
+                           int context, int rope, float rope_coef, int out_packed_rows, rst_stream_t stream) {
+    return rst_attention_step_ps_f32(qkv, k, v, out, pos_dev, 0, B, T, H, D, cap, context, rope, rope_coef, out_packed_rows, stream);
+}
+
+int rst_hist_seed_f32(const float* x, float* hist, int32_t* fresh, int B, int T_in, int P, int C, int replicate, rst_stream_t stream) {
+    return rst_launch_hist_seed(x, hist, fresh, B, T_in, P, C, replicate, (hipStream_t)stream);
 }
 
 int rst_hist_update_batch_f32(const float* const* x, float* const* hist, const int* T_in, const int* P, const int* C, int n, int B,
@@ -792,20 +801,33 @@ int rst_lm_sample_f32(const float* logits, const float* noise, int64_t* tokens, 
                                   top_p, workspace, workspace_bytes, stream);
 }
 
-int rst_lm_ring_begin_i64(int64_t* cache, const int64_t* user_tokens, const int64_t* initial, const int32_t* delays,
-                          int64_t* offset_dev, int64_t* input_out, int B, int K, int CT, int Ki, int first_user_k, rst_stream_t stream) {
+int rst_lm_ring_begin_ps_i64(int64_t* cache, const int64_t* user_tokens, const int64_t* initial, const int32_t* delays,
+                             int64_t* offset_dev, int offset_stride, int64_t* input_out, int B, int K, int CT, int Ki, int first_user_k,
+                             rst_stream_t stream) {
     LmRingParams p{};
     p.cache = (long*)cache; p.user = (const long*)user_tokens; p.initial = (const long*)initial; p.delays = delays;
-    p.offset_dev = (long*)offset_dev; p.input_out = (long*)input_out; p.B = B; p.K = K; p.CT = CT; p.Ki = Ki; p.first_user = first_user_k;
+    p.offset_dev = (long*)offset_dev; p.offset_stride = offset_stride; p.input_out = (long*)input_out;
+    p.B = B; p.K = K; p.CT = CT; p.Ki = Ki; p.first_user = first_user_k;
     return rst_launch_lm_ring_begin(p, (hipStream_t)stream);
+}
+
+int rst_lm_ring_begin_i64(int64_t* cache, const int64_t* user_tokens, const int64_t* initial, const int32_t* delays,
+                          int64_t* offset_dev, int64_t* input_out, int B, int K, int CT, int Ki, int first_user_k, rst_stream_t stream) {
+    return rst_lm_ring_begin_ps_i64(cache, user_tokens, initial, delays, offset_dev, 0, input_out, B, K, CT, Ki, first_user_k, stream);
+}
+
+int rst_lm_ring_commit_ps_i64(int64_t* cache, const int64_t* tokens, const int32_t* delays, int64_t* offset_dev, int offset_stride,
+                              int64_t* out, int B, int K, int CT, int n_out, int max_delay, rst_stream_t stream) {
+    LmRingParams p{};
+    p.cache = (long*)cache; p.tokens = (const long*)tokens; p.delays = delays; p.offset_dev = (long*)offset_dev;
+    p.offset_stride = offset_stride; p.out = (long*)out;
+    p.B = B; p.K = K; p.CT = CT; p.n_out = n_out; p.max_delay = max_delay;
+    return rst_launch_lm_ring_commit(p, (hipStream_t)stream);
 }
 
 int rst_lm_ring_commit_i64(int64_t* cache, const int64_t* tokens, const int32_t* delays, int64_t* offset_dev, int64_t* out, int B, int K,
                            int CT, int n_out, int max_delay, rst_stream_t stream) {
-    LmRingParams p{};
-    p.cache = (long*)cache; p.tokens = (const long*)tokens; p.delays = delays; p.offset_dev = (long*)offset_dev; p.out = (long*)out;
-    p.B = B; p.K = K; p.CT = CT; p.n_out = n_out; p.max_delay = max_delay;
-    return rst_launch_lm_ring_commit(p, (hipStream_t)stream);
+    return rst_lm_ring_commit_ps_i64(cache, tokens, delays, offset_dev, 0, out, B, K, CT, n_out, max_delay, stream);
 }
 
 }  // extern "C"

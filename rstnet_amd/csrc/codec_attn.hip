@@ -30,7 +30,7 @@ __global__ __launch_bounds__(AS_THREADS) void attn_step_kernel(const AttnStepPar
     float* pB = sraw + T * capS;
     float* opart = pB + T * capS;
     float* wred = opart + 1024 * T;
-    const long pos = *p.pos_dev;
+    const long pos = p.pos_dev[b * p.pos_stride];   // position of the first new step (one unconditional scalar load; stride 0: shared)
 
     float* kring = p.k + ((long)(b * H + h) * cap) * D;
     float* vring = p.v + ((long)(b * H + h) * cap) * D;
@@ -227,6 +227,7 @@ int rst_attn_step_supported_impl(int T, int D, int cap) {
 
 int rst_launch_attn_step(const AttnStepParams& p, hipStream_t stream) {
     RST_REQUIRE(p.qkv && p.k && p.v && p.out && p.pos_dev && p.B >= 1 && p.H >= 1, "attention_step: null buffers / bad sizes");
+    RST_REQUIRE(p.pos_stride == 0 || p.pos_stride == 1, "attention_step: position stride %ld (0: shared, 1: one per stream)", p.pos_stride);
     RST_REQUIRE(rst_attn_step_supported_impl(p.T, p.D, p.cap), "attention_step: unsupported shape (T=%d D=%d cap=%d; 1 <= T <= 4, D in 32 / 64 / 128)",
                 p.T, p.D, p.cap);
     RST_REQUIRE(p.out_rows == 0 || (p.out_rows >= p.B * p.T && p.out_rows % 32 == 0 && (p.H * p.D) % 8 == 0),

@@ -171,6 +171,20 @@ __global__ __launch_bounds__(1024) void hist_update_batch_kernel(const HistBatch
     }
 }
 
+// A stream of a live batch that starts over: where fresh[b] is set, the history row h[b] [P][C] becomes what a new session's first
+// chunk would find -- P copies of the chunk's first step x[b][0][:] (replicate padding) or zeros -- and the flag is cleared; the
+// other rows are not touched.  One workgroup per stream, so the flag test is uniform and the barrier below is reached by all or none.
+__global__ __launch_bounds__(256) void hist_seed_kernel(const float* __restrict__ x, float* __restrict__ h, int* fresh, int T_in, int P, int C,
+                                                        int replicate) {
+    const long b = blockIdx.x;
+    if (fresh[b] == 0) return;
+    const float* x0 = x + b * (long)T_in * C;
+    float* hb = h + b * (long)P * C;
+    for (int e = threadIdx.x; e < P * C; e += 256) hb[e] = replicate ? x0[e % C] : 0.f;
+    __syncthreads();                 // every thread has read the flag before it is cleared
+    if (threadIdx.x == 0) fresh[b] = 0;
+}
+
 // Rows t >= len[b] of x [B][T][C] become zero (mode 0) or a copy of row len[b] - 1 (mode 1).
 __global__ __launch_bounds__(256) void mask_tail_kernel(float* __restrict__ x, const int* __restrict__ len, int B, int T, int C, int mode) {
     const long total = (long)B * T * (C / 4);
@@ -255,6 +269,16 @@ int rst_launch_hist_update_batch(const HistBatchParams& p, hipStream_t stream) {
                     "hist_update_batch: entry %d (T_in=%d P=%d C=%d; P * C <= %d)", i, p.T_in[i], p.P[i], p.C[i], 1024 * HIST_INPLACE_MAX);
     hipLaunchKernelGGL(hist_update_batch_kernel, dim3(p.B, p.n), dim3(1024), 0, stream, p);
     return rst_check_launch("hist_update_batch");
+}
+
+int rst_launch_hist_seed(const float* x, float* hist, int* fresh, int B, int T_in, int P, int C, int replicate, hipStream_t stream) {
+    RST_REQUIRE(B >= 0 && B <= 65535 && T_in >= 0 && P >= 0 && C > 0 && (long)P * C <= 0x7fffffffL, "hist_seed: bad sizes (B=%d T_in=%d P=%d C=%d)",
+                B, T_in, P, C);
+    if (B == 0 || P == 0) return RST_OK;
+    RST_REQUIRE(hist && fresh, "hist_seed: null pointer");
+    RST_REQUIRE(!replicate || (x && T_in >= 1), "hist_seed: replicate padding needs the chunk's first step (T_in=%d)", T_in);
+    hipLaunchKernelGGL(hist_seed_kernel, dim3(B), dim3(256), 0, stream, x, hist, fresh, T_in, P, C, replicate);
+    return rst_check_launch("hist_seed");
 }
 
 int rst_launch_mask_tail(float* x, const int* lengths, int B, int T, int C, int mode, hipStream_t stream) {

@@ -69,7 +69,8 @@ struct AttnStepParams {
     float* k;                     // rings [B][H][cap][D]
     float* v;
     float* out;                   // [B][T][H*D], or (out_rows) [out_rows][H*D] in the packed operand order of the few-row GEMM
-    const long* pos_dev;          // position of the first new step
+    const long* pos_dev;          // position of the first new step: stream b reads pos_dev[b * pos_stride]
+    long pos_stride;              // 0: one position for every stream (a device scalar); 1: one per stream, int64 [B]
     int B, T, H, D, cap, context, rope;
     int out_rows;                 // 0: row-major result; else B*T rounded up to 32 (64 above 32, 128 above 64: rst_skinny_f32_pack_win's rows)
     float rope_coef;
@@ -134,6 +135,8 @@ struct HistBatchParams {          // in-place rolls: hist[i] [B][P][C] <- last P
     int n, B;
 };
 int rst_launch_hist_update_batch(const HistBatchParams& p, hipStream_t stream);
+// rows b with fresh[b] != 0: hist[b] [P][C] <- P copies of x[b][0][:] (replicate) or zeros, then fresh[b] <- 0; other rows untouched
+int rst_launch_hist_seed(const float* x, float* hist, int* fresh, int B, int T_in, int P, int C, int replicate, hipStream_t stream);
 
 int rst_launch_act(const float* x, float* y, long n, int act, hipStream_t stream);  // 1: ELU, 2: GELU
 int rst_launch_mask_tail(float* x, const int* lengths, int B, int T, int C, int mode, hipStream_t stream);
@@ -436,7 +439,8 @@ struct LmRingParams {
     const long* user;           // begin: [B][Ki] tokens of the user streams (codebooks first_user .. first_user + Ki - 1)
     const long* initial;        // begin: [K] initial token per codebook
     const int* delays;          // [K] device
-    long* offset_dev;           // int64 scalar: frames stepped so far (commit increments it)
+    long* offset_dev;           // frames stepped so far (commit increments it): stream b reads offset_dev[b * offset_stride]
+    long offset_stride;         // 0: one int64 counter for every stream; 1: one per stream, int64 [B]
     long* input_out;            // begin: [B][K] the model input of this step
     const long* tokens;         // commit: [B][n_out] generated (text, audio_0 .. audio_{dep_q-1})
     long* out;                  // commit: [B][n_out] delay-aligned output

@@ -21,7 +21,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..codec.streaming import StreamingContainer, StreamingModule
+from ..codec.streaming import StreamingContainer, StreamingModule, check_rows
 from ..graphs import Graphed as _Graphed, RecaptureGate
 from ..packed import _PackedCache
 from .depth_frame import DepthDecoder
@@ -202,8 +202,11 @@ class StreamingTransformer(StreamingModule[_StepState]):
             raise RuntimeError("Cannot create a streaming KVCache without a context to estimate capacity.")
         cap = capacity or (self.context if self.context is not None else self.weights_per_step)
         H = self.num_heads
+        # (a per-stream session, `streaming(batch_size, per_stream=True)`: one position per stream on the temporal rings; the depth rings
+        # restart every frame for all streams and keep their scalar positions)
         return _StepState.make(batch_size, H, H, self.d_model // H, cap, self.kv_dtype if cap > 64 else torch.float32,
-                               self.layers[0].norm1.alpha.device, len(self.layers))
+                               self.layers[0].norm1.alpha.device, len(self.layers),
+                               per_stream=self._streaming_per_stream and not self.weights_per_step and capacity is None)
 
     def _geometry(self) -> Geometry:
         return Geometry(None, self.context, self.rope, self.max_period)
@@ -244,6 +247,10 @@ class StreamingTransformer(StreamingModule[_StepState]):
         k_idx = 0
         if self.weights_per_step:
             k_idx = st.offset_cpu if step_index is None else step_index
+        if st.per_stream and pos is None:
+            # one position per stream: the decode launch that reads them, at every batch size (never the fused short-ring form, never
+            # the persistent launch -- both know one position per call)
+            return run_layers(x, 1, st, ROUTE_DECODE, self._geometry(), self._views(k_idx), embed=embed)
         if B == 1 and x is not None and not self.weights_per_step and cap > 64 and ops.temporal_frame_wanted(st.offset_cpu):
             y = self._persistent_step(st, x, st.pos if pos is None else pos, cap)
             if y is not None:
@@ -634,7 +641,7 @@ def prefill_token_plan(cache: torch.Tensor, offset: int, user: torch.Tensor, own
 class _LMGenState:
     cache: torch.Tensor            # int64 [B, K, max_delay + 2] token ring
     initial: torch.Tensor          # int64 [1, K, 1]
-    offset_dev: torch.Tensor       # int64 [1]: the frame counter as the ring kernels see it
+    offset_dev: torch.Tensor       # int64 [1]: the frame counter as the ring kernels see it; per-stream session: int64 [B], one per stream
     graphed_frame: _Graphed
     gate: RecaptureGate                    # whether the device's persistent launches were retired since the frame graph was captured
     depth: Optional[_StepState] = None     # the depth transformer's KV rings of THIS session (a captured frame points at them)
@@ -642,11 +649,14 @@ class _LMGenState:
     tables: object = None                  # the DepthFrameTables the captured frame points at (kept alive with the graph)
     temporal_base: Optional[int] = None    # host-side position of the temporal rings at frame 0 of this session
     temporal_choice: Optional[bool] = None  # whether the captured frame takes the persistent temporal launch
+    frames: Optional[List[int]] = None     # per-stream session: host mirror of `offset_dev`, frames each stream has stepped since its (re)start
 
     def reset(self) -> None:
         self.offset = 0
         self.offset_dev.zero_()
         self.temporal_base = None       # (the temporal rings were reset with the session: re-read their position at the next frame)
+        if self.frames is not None:
+            self.frames = [0] * len(self.frames)
 
 
 class LMGen(StreamingModule[_LMGenState]):
@@ -671,9 +681,45 @@ class LMGen(StreamingModule[_LMGenState]):
         cache = torch.full((batch_size, lm.num_codebooks, self.max_delay + 2), lm.ungenerated_token_id, device=lm.device,
                            dtype=torch.long)
         disable = lm.device.type != "cuda"
-        return _LMGenState(cache, lm._get_initial_token(), torch.zeros(1, device=lm.device, dtype=torch.long),
+        per_stream = self._streaming_per_stream
+        return _LMGenState(cache, lm._get_initial_token(), torch.zeros(batch_size if per_stream else 1, device=lm.device, dtype=torch.long),
                            _Graphed(self._frame, disable=disable), RecaptureGate(lm.device),
-                           depth=lm.depformer._init_streaming_state(batch_size))
+                           depth=lm.depformer._init_streaming_state(batch_size), frames=[0] * batch_size if per_stream else None)
+
+    def reset_streams(self, rows) -> None:
+        """Streams ``rows`` of a per-stream session (``streaming(batch_size, per_stream=True)``) start a new conversation with the next
+        frame: their token-ring rows go back to ``ungenerated_token_id``, their frame counters and their positions on the temporal rings
+        to 0.  The other streams do not notice.  Eager in-place writes between two frames: the captured frame reads all three from device
+        memory and stays valid.  ``step`` output of such a stream is meaningful again once ``stream_valid()`` lists it."""
+        state = self._streaming_state
+        if state is None:
+            raise RuntimeError("You should wrap those calls with a `with lm_gen.streaming(): ...`.")
+        if state.frames is None:
+            raise ValueError("reset_streams needs a per-stream session: open it with streaming(batch_size, per_stream=True)")
+        rows = check_rows(rows, len(state.frames))
+        if not rows:
+            return
+        lm = self.lm_model
+        state.cache[rows] = lm.ungenerated_token_id
+        state.offset_dev[rows] = 0
+        tst = lm.transformer._streaming_state
+        if tst is not None:
+            if not tst.per_stream:
+                raise ValueError("reset_streams: the model's temporal rings keep one position for the batch (the session was not opened per stream)")
+            tst.pos[rows] = 0
+        for b in rows:
+            state.frames[b] = 0
+
+    def stream_valid(self) -> List[int]:
+        """The streams whose last ``step`` output is meaningful: those whose own frame count exceeds ``max_delay`` (a scalar session:
+        all of them or none)."""
+        state = self._streaming_state
+        if state is None:
+            raise RuntimeError("You should wrap those calls with a `with lm_gen.streaming(): ...`.")
+        if state.frames is None:
+            B = state.cache.shape[0]
+            return list(range(B)) if state.offset > self.max_delay else []
+        return [b for b, n in enumerate(state.frames) if n > self.max_delay]
 
     def _noise(self, B: int, k: int) -> Optional[torch.Tensor]:
         if not self.use_sampling:
@@ -724,6 +770,17 @@ class LMGen(StreamingModule[_LMGenState]):
         if lm.device.type == "cuda" and state.gate.moved(state.offset):
             # a device that had to repair frames moves to the launch-per-op chain, which needs a fresh capture
             state.graphed_frame = _Graphed(self._frame)
+        if state.frames is not None:
+            # per-stream session: the streams stand at different frames and positions, all of them on the device (no host mirror of the
+            # temporal rings, one route -- ROUTE_DECODE -- at every fill level, so nothing is ever re-captured for a position)
+            out, input_ = state.graphed_frame(input_tokens.reshape(B, Ki).contiguous())
+            if self.check:
+                lm.depth_decoder.check()
+            state.offset += 1
+            state.frames = [n + 1 for n in state.frames]
+            if max(state.frames) <= self.max_delay:
+                return None
+            return out.view(B, lm.dep_q + 1, 1).clone()
         tst = lm.transformer._streaming_state
         if tst is not None:
             # the temporal rings' fill as the host knows it (graph replays do not run the Python that counts steps): the persistent
@@ -775,6 +832,8 @@ class LMGen(StreamingModule[_LMGenState]):
         state = self._streaming_state
         if state is None:
             raise RuntimeError("You should wrap those calls with a `with lm_gen.streaming(): ...`.")
+        if state.frames is not None:
+            raise ValueError("LMGen.prefill on a per-stream session: its token plan counts one frame offset for the batch")
         lm = self.lm_model
         assert user_tokens.dim() == 3 and own_tokens.dim() == 3, "Shape should be [B, K, T]."
         B, Ki, T = user_tokens.shape

@@ -578,6 +578,12 @@ ATTENTION_STEP = True
 ATTENTION_STEP_PACKED = True       # its result straight in the out-projection's packed operand order on the few-row route (False: row-major)
 
 
+def attention_step_serves(T: int, D: int, cap: int) -> bool:
+    """Whether the library's one-launch attention step serves ``T`` new positions of head size ``D`` on a ring of ``cap`` slots -- the shape
+    rule alone, asked before any tensor exists (a per-stream codec session checks it when it opens)."""
+    return bool(ATTENTION_STEP and _lib.lib().rst_attention_step_supported(int(T), int(D), int(cap)))
+
+
 def attention_step_supported(qkv: torch.Tensor, H: int, cap: int) -> bool:
     B, T, E3 = qkv.shape
     return bool(ATTENTION_STEP and qkv.is_cuda and E3 % (3 * H) == 0 and qkv.data_ptr() % 16 == 0 and
@@ -604,6 +610,31 @@ def attention_step(qkv: torch.Tensor, H: int, k: torch.Tensor, v: torch.Tensor, 
     out = torch.empty((rows, H * D) if out_packed else (B, T, H * D), device=qkv.device, dtype=torch.float32)
     _lib.check(_lib.lib().rst_attention_step_f32(_ptr(qkv), _ptr(k), _ptr(v), _ptr(out), _ptr(pos_dev), B, T, H, D, k.shape[2],
                                                  _ctx(context), int(rope), rope_coef(max_period, D), rows, _stream()))
+    return PackedRows(out, (B, T, H * D)) if out_packed else out
+
+
+@_on_tensor_device
+def attention_step_ps(qkv: torch.Tensor, H: int, k: torch.Tensor, v: torch.Tensor, pos_dev: torch.Tensor, *, context: Optional[int] = None,
+                      rope: bool = True, max_period: float = 10000.0, out_packed: bool = False):
+    """``attention_step`` with one position per stream (rst_attention_step_ps_f32): ``pos_dev`` int64 ``[B]``, stream ``b`` appends at slots
+    ``(pos_dev[b] + t) % cap``, rotates by ``pos_dev[b] + t`` and sees what a stream at that position sees -- at position 0 nothing of what
+    its ring held before.  Row ``b`` equals row ``b`` of ``attention_step`` launched at ``pos_dev[b]`` on the same ring, bit for bit."""
+    for t, n in ((qkv, "qkv"), (k, "k"), (v, "v")):
+        _chk(t, n)
+    _chk(pos_dev, "pos_dev", torch.int64)
+    B, T, E3 = qkv.shape
+    if pos_dev.dim() != 1 or pos_dev.numel() != B:
+        raise ValueError(f"rstnet_amd.ops: attention_step_ps takes one position per stream, int64 [{B}], got {tuple(pos_dev.shape)}")
+    D = E3 // (3 * H)
+    if k.shape != v.shape or k.shape[0] != B or k.shape[1] != H or k.shape[3] != D:
+        raise ValueError(f"rstnet_amd.ops: rings {tuple(k.shape)} / {tuple(v.shape)} do not belong to qkv {tuple(qkv.shape)} with {H} heads")
+    M = B * T
+    rows = _packed_row_count(M) if out_packed else 0
+    if out_packed and (M > SKINNY_F32_MAX_ROWS or (H * D) % 8):
+        raise ValueError(f"rstnet_amd.ops: a packed attention result needs <= {SKINNY_F32_MAX_ROWS} rows and H * D % 8 == 0 (rows {M}, H * D {H * D})")
+    out = torch.empty((rows, H * D) if out_packed else (B, T, H * D), device=qkv.device, dtype=torch.float32)
+    _lib.check(_lib.lib().rst_attention_step_ps_f32(_ptr(qkv), _ptr(k), _ptr(v), _ptr(out), _ptr(pos_dev), 1, B, T, H, D, k.shape[2],
+                                                    _ctx(context), int(rope), rope_coef(max_period, D), rows, _stream()))
     return PackedRows(out, (B, T, H * D)) if out_packed else out
 
 
@@ -881,6 +912,23 @@ def hist_update(x: torch.Tensor, hist_in: Optional[torch.Tensor], P_out: int) ->
     out = torch.empty(B, P_out, Cc, device=x.device, dtype=torch.float32)
     _lib.check(_lib.lib().rst_hist_update_f32(_ptr(x), _ptr(hist_in), _ptr(out), B, T, P_in, P_out, Cc, _stream()))
     return out
+
+
+@_on_tensor_device
+def hist_seed(x: Optional[torch.Tensor], hist: torch.Tensor, fresh: torch.Tensor, *, replicate: bool) -> None:
+    """Streams that start over inside a live batch (rst_hist_seed_f32): where ``fresh[b]`` (int32 ``[B]`` on the device) is set, the
+    history row ``hist[b]`` ``[P, C]`` becomes what a new session's first chunk finds -- ``P`` copies of ``x[b, 0]`` (``replicate``; ``x``
+    ``[B, T, C]`` is that chunk) or zeros -- and the flag is cleared; the other rows keep their bytes.  In place, one launch."""
+    _chk(x, "x")
+    _chk(hist, "hist")
+    _chk(fresh, "fresh", torch.int32)
+    B, P, Cc = hist.shape
+    if fresh.numel() != B or (x is not None and (x.dim() != 3 or x.shape[0] != B or x.shape[2] != Cc)):
+        raise ValueError(f"rstnet_amd.ops: hist_seed: history {tuple(hist.shape)} against flags {tuple(fresh.shape)} / chunk "
+                         f"{None if x is None else tuple(x.shape)}")
+    if replicate and (x is None or x.shape[1] < 1):
+        raise ValueError("rstnet_amd.ops: hist_seed: replicate padding needs the chunk's first step")
+    _lib.check(_lib.lib().rst_hist_seed_f32(_ptr(x), _ptr(hist), _ptr(fresh), B, 0 if x is None else x.shape[1], P, Cc, int(replicate), _stream()))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1755,7 +1803,8 @@ def lm_sample(logits: torch.Tensor, *, use_sampling: bool, temp: float, top_k: i
 def lm_ring_begin(cache: torch.Tensor, user_tokens: torch.Tensor, initial: torch.Tensor, delays: torch.Tensor,
                   offset_dev: torch.Tensor, first_user_k: int) -> torch.Tensor:
     """Start of an ``LMGen.step`` frame on the device (models/model.py:506-521): user streams into the token ring
-    ``cache [B, K, CT]`` at their delayed columns, initial tokens while ``offset <= delay``; returns the model input ``[B, K]``."""
+    ``cache [B, K, CT]`` at their delayed columns, initial tokens while ``offset <= delay``; returns the model input ``[B, K]``.
+    ``offset_dev``: the one frame counter of the batch (``numel() == 1``) or int64 ``[B]``, one per stream (rst_lm_ring_begin_ps_i64)."""
     for t, n in ((cache, "cache"), (user_tokens, "user_tokens"), (initial, "initial"), (offset_dev, "offset_dev")):
         _chk(t, n, torch.int64)
     _chk(delays, "delays", torch.int32)
@@ -1763,6 +1812,10 @@ def lm_ring_begin(cache: torch.Tensor, user_tokens: torch.Tensor, initial: torch
     Ki = user_tokens.shape[1]
     assert user_tokens.shape[0] == B and initial.numel() == K and delays.numel() == K
     out = torch.empty(B, K, device=cache.device, dtype=torch.int64)
+    if _pos_stride(offset_dev, B, "lm_ring_begin"):
+        _lib.check(_lib.lib().rst_lm_ring_begin_ps_i64(_ptr(cache), _ptr(user_tokens), _ptr(initial), _ptr(delays), _ptr(offset_dev), 1, _ptr(out),
+                                                      B, K, CT, Ki, first_user_k, _stream()))
+        return out
     _lib.check(_lib.lib().rst_lm_ring_begin_i64(_ptr(cache), _ptr(user_tokens), _ptr(initial), _ptr(delays), _ptr(offset_dev), _ptr(out),
                                                B, K, CT, Ki, first_user_k, _stream()))
     return out
@@ -1771,13 +1824,18 @@ def lm_ring_begin(cache: torch.Tensor, user_tokens: torch.Tensor, initial: torch
 @_on_tensor_device
 def lm_ring_commit(cache: torch.Tensor, tokens: torch.Tensor, delays: torch.Tensor, offset_dev: torch.Tensor, max_delay: int) -> torch.Tensor:
     """End of the frame (models/model.py:545-562): ``offset_dev += 1``, generated ``tokens [B, n]`` into the ring, returns the
-    delay-aligned gather ``[B, n]`` (meaningful once ``offset > max_delay``)."""
+    delay-aligned gather ``[B, n]`` (meaningful once ``offset > max_delay``).  ``offset_dev`` int64 ``[B]``: one counter per stream, each
+    incremented (rst_lm_ring_commit_ps_i64); row ``b`` is meaningful once ITS counter exceeds ``max_delay``."""
     for t, n in ((cache, "cache"), (tokens, "tokens"), (offset_dev, "offset_dev")):
         _chk(t, n, torch.int64)
     _chk(delays, "delays", torch.int32)
     B, K, CT = cache.shape
     n_out = tokens.shape[1]
     out = torch.empty(B, n_out, device=cache.device, dtype=torch.int64)
+    if _pos_stride(offset_dev, B, "lm_ring_commit"):
+        _lib.check(_lib.lib().rst_lm_ring_commit_ps_i64(_ptr(cache), _ptr(tokens), _ptr(delays), _ptr(offset_dev), 1, _ptr(out), B, K, CT, n_out,
+                                                       int(max_delay), _stream()))
+        return out
     _lib.check(_lib.lib().rst_lm_ring_commit_i64(_ptr(cache), _ptr(tokens), _ptr(delays), _ptr(offset_dev), _ptr(out), B, K, CT, n_out,
                                                 int(max_delay), _stream()))
     return out

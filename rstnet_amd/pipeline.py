@@ -7,22 +7,45 @@ cache) lives in the modules' streaming states on the device; the host only moves
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 from .codec.audio_resample import StreamResampler, stream_pair_geometry
 from .codec.mimi import MimiCodec
+from .codec.streaming import check_rows
 from .graphs import Graphed, RecaptureGate
 from .lm.model import LMGen
 
 CODEC_RATE = 24000
 
 
+def restart_schedule(frames: Sequence[int], awaiting: Sequence[int], max_delay: int) -> Tuple[List[int], List[int], List[int]]:
+    """The host side of one frame of a per-stream session, as a pure function.  ``frames[b]``: frames stream ``b`` has stepped since its
+    (re)start, BEFORE this frame; ``awaiting``: the restarted streams whose decoder side still has to be reset a second time.  ->
+    ``(reset_now, valid, awaiting_after)``:
+
+    * ``reset_now``: streams of ``awaiting`` whose decoder side is reset immediately before this frame -- the frame that produces their
+      first valid output (``frames[b] == max_delay``).  A new session does not run the decoder or the outgoing rate conversion during its
+      first ``max_delay`` frames; in a batch both run for every stream on every frame, so whatever a restarted stream's delay frames
+      left in its decoder state is wiped here.
+    * ``valid``: streams whose output of this frame is meaningful, ``frames[b] + 1 > max_delay``; the others' PCM is zero-filled.
+    * ``awaiting_after``: ``awaiting`` without ``reset_now``."""
+    reset_now = sorted(b for b in set(awaiting) if frames[b] == max_delay)
+    valid = [b for b, n in enumerate(frames) if n + 1 > max_delay]
+    return reset_now, valid, sorted(set(awaiting) - set(reset_now))
+
+
 class StreamingPipeline:
-    def __init__(self, mimi: MimiCodec, lm_gen: LMGen, batch_size: int, client_rate: Optional[int] = None):
+    def __init__(self, mimi: MimiCodec, lm_gen: LMGen, batch_size: int, client_rate: Optional[int] = None, per_stream: bool = False):
         assert mimi.quantizer.n_q >= lm_gen.lm_model.dep_q
         self.mimi, self.lm_gen, self.batch_size = mimi, lm_gen, batch_size
+        # per_stream: every stateful module of the frame keeps one position per stream, so `reset_streams(rows)` can start new conversations
+        # in single rows of the live batch while the others go on; `step` then returns PCM for all rows (zeros for rows inside their delay)
+        self.per_stream = bool(per_stream)
+        self._frames: List[int] = [0] * batch_size      # per-stream: frames each row has stepped since its (re)start
+        self._awaiting: List[int] = []                  # per-stream: restarted rows whose decoder side is reset once more (restart_schedule)
+        self.stream_valid: List[int] = []               # rows whose PCM of the last `step` is meaningful
         self.frame_size = mimi.frame_hop
         # a client at another sample rate: ``step`` takes and returns ``client_frame`` samples at ``client_rate``; the two conversions
         # (codec/audio_resample.py: StreamResampler, created per session) are part of the frame.  ValueError here, before any streaming
@@ -39,10 +62,15 @@ class StreamingPipeline:
 
     def __enter__(self):
         # encode touches only the encoder-side modules' states and decode only the decoder-side ones: one context serves both
-        self._mimi_ctx = self.mimi.streaming(self.batch_size)
+        self._mimi_ctx = self.mimi.streaming(self.batch_size, per_stream=True) if self.per_stream else self.mimi.streaming(self.batch_size)
         self._mimi_ctx.__enter__()
-        self._lm_ctx = self.lm_gen.streaming(self.batch_size)
-        self._lm_ctx.__enter__()
+        self._lm_ctx = self.lm_gen.streaming(self.batch_size, per_stream=True) if self.per_stream else self.lm_gen.streaming(self.batch_size)
+        try:
+            self._lm_ctx.__enter__()
+        except Exception:
+            self._mimi_ctx.__exit__(None, None, None)
+            raise
+        self._frames, self._awaiting, self.stream_valid = [0] * self.batch_size, [], []
         self._fused, self.last_codes = None, None     # a graph of an earlier session points at that session's states
         self._gate = RecaptureGate(self.lm_gen.lm_model.device, every_frame=True)
         if self.client_rate is not None:
@@ -68,7 +96,52 @@ class StreamingPipeline:
         codes = self.mimi.quantizer.encode_nlc(self.mimi.encode_latent(pcm))          # [B, K, 1]
         self.last_codes = codes         # (inside the graph: a static buffer every replay refills)
         out, _ = self.lm_gen._frame(codes[:, :self.n_user, 0].contiguous())            # [B, 1 + dep_q]
-        return self.mimi._decode(out[:, 1:].reshape(B, -1, 1))
+        audio = out[:, 1:]
+        if self.per_stream:
+            audio = self._decodable(audio)
+        return self.mimi._decode(audio.reshape(B, -1, 1))
+
+    def _decodable(self, audio_tokens: torch.Tensor) -> torch.Tensor:
+        """The decoder runs for every row of a per-stream batch on every frame; a row inside its delay still holds the ring's
+        ``ungenerated`` / initial ids (-2, ``card``), which are no codebook entries: clamp them into the codebook (identity on generated
+        tokens).  What such a row decodes to is never returned (``step`` zero-fills it) and is wiped from its state before its first valid frame."""
+        return audio_tokens.clamp(0, self.lm_gen.lm_model.card - 1)
+
+    def reset_streams(self, rows) -> None:
+        """Rows ``rows`` of a live per-stream session start a new conversation with the next frame: encoder side, LM and decoder side of
+        those rows become those of a new session, the other rows do not notice.  All of it is eager in-place writes between two frames;
+        state tensors keep their addresses, so the captured frame graph goes on replaying.  The rows' PCM is zero for their first
+        ``max_delay`` frames (``stream_valid`` lists who is past it); from then on it equals a new session's fed the same frames."""
+        if not self.per_stream:
+            raise ValueError("reset_streams needs StreamingPipeline(..., per_stream=True)")
+        if self.lm_gen._streaming_state is None:
+            raise RuntimeError("reset_streams outside the session: enter the pipeline first")
+        rows = check_rows(rows, self.batch_size)
+        if not rows:
+            return
+        self.mimi.reset_streams(rows, side="both")
+        self.lm_gen.reset_streams(rows)
+        if self._rs_in is not None:
+            self._rs_in.reset_rows(rows)
+            self._rs_out.reset_rows(rows)
+        for b in rows:
+            self._frames[b] = 0
+        self._awaiting = sorted(set(self._awaiting) | set(rows)) if self.lm_gen.max_delay > 0 else self._awaiting
+
+    def _reset_decoder_side(self, rows) -> None:
+        self.mimi.reset_streams(rows, side="decoder")
+        if self._rs_out is not None:
+            self._rs_out.reset_rows(rows)
+
+    def _finish(self, wav: Optional[torch.Tensor], valid: List[int]) -> Optional[torch.Tensor]:
+        """Per-stream: the frame's PCM with the rows inside their delay zero-filled (``wav`` is already this call's own copy)."""
+        self._frames = [n + 1 for n in self._frames]
+        self.stream_valid = valid
+        if wav is None:
+            return None
+        if len(valid) < self.batch_size:
+            wav[[b for b in range(self.batch_size) if b not in valid]] = 0.0
+        return wav
 
     def _frame_fn_rate(self, pcm: torch.Tensor) -> torch.Tensor:
         """``_frame_fn`` between the session's two rate conversions: client rate -> 24 kHz -> client rate, still one graph."""
@@ -87,6 +160,11 @@ class StreamingPipeline:
         assert pcm.shape == (self.batch_size, 1, self.client_frame), tuple(pcm.shape)
         gen = self.lm_gen
         state = gen._streaming_state
+        valid: List[int] = []
+        if self.per_stream:
+            reset_now, valid, self._awaiting = restart_schedule(self._frames, self._awaiting, gen.max_delay)
+            if reset_now:
+                self._reset_decoder_side(reset_now)
         fused_ok = (self.fuse and pcm.is_cuda and state is not None and state.offset >= gen.max_delay + 2 and not gen.check
                     and self.mimi.code_layout == "bkt")
         if fused_ok:
@@ -98,12 +176,20 @@ class StreamingPipeline:
             if not self._fused.disable:
                 wav = self._fused(pcm.contiguous())
                 state.offset += 1
+                if self.per_stream:
+                    state.frames = [n + 1 for n in state.frames]
+                    return self._finish(wav.clone(), valid)
                 return wav.clone()
         if rated:
             pcm = self._rs_in.step(pcm)
         codes = self.mimi.encode(pcm)                                   # [B, 8, 1]
         self.last_codes = codes
         tokens = self.lm_gen.step(codes[:, :self.n_user].contiguous())  # [B, 1 + dep_q, 1] or None
+        if self.per_stream:
+            if tokens is None:
+                return self._finish(None, valid)
+            wav = self.mimi.decode(self._decodable(tokens[:, 1:]).contiguous())
+            return self._finish(self._rs_out.step(wav).clone() if rated else wav, valid)
         if tokens is None:
             return None
         wav = self.mimi.decode(tokens[:, 1:].contiguous())
