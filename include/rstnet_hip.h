@@ -282,6 +282,27 @@ int rst_resample_sinc(const void* x, int x_dtype, int64_t x_row_stride, int T_in
  * bytes a tile of these rates stages its inputs in, or 0 when the span is too long and the kernel reads them from global memory. */
 int rst_resample_plan(int o, int n, int L, int* slab_bytes);
 
+/* Packed frame records: the two ends of a frame served to many clients at once (the role of the PCM accumulation and of
+ * opus_writer.append_pcm in MLLM_v2/moshi/server.py:113-136, for a whole batch in one upload and one download per frame).  A record
+ * buffer is uint8 [B][rec_stride], rec_stride a multiple of 16 and >= round_up(16 + 4 F, 16): a 16-byte header, then the payload.
+ * fmt is int32 [B], one transport per row: < 0 a free row, 1 = s16, anything else >= 0 = f32 (little-endian, as the device is).
+ *
+ * rst_frame_ingress: header word 0 of row b is `present`; the payload holds F samples in the row's transport.  pcm_out fp32 [B][F]:
+ *     pcm_out[b][i] = payload f32 bits unchanged            fmt[b] = 0
+ *                   = (float)s16 * 2^-15 (= x / 32768.0f, exact)   fmt[b] = 1
+ *                   = 0                                      present == 0 or fmt[b] < 0   (the payload is not read)
+ *
+ * rst_frame_egress: wav fp32 [B][F]; tokens int64, row b at tokens[b * tok_stride] (its first entry is the text token); offset_dev
+ * int64 [B], the per-stream frame counters AFTER the frame's commit.  Row b is valid iff fmt[b] >= 0 && offset_dev[b] > max_delay.
+ * Header: int32 valid; int32 text token (-1 when not valid); int32 payload_bytes (4 F, 2 F for s16, 0 when not valid); int32 0.
+ * Payload of a valid row: the f32 bits unchanged, or s16 = (int16)(clamp(x, -1, 1) * 32767.0f): ONE rounded fp32 multiply, converted
+ * with truncation toward zero; NaN encodes as 0.  Every other byte of the record -- an invalid row's payload, the padding up to
+ * rec_stride -- is written as zero: the buffer is deterministic byte for byte and needs no fill.
+ * < 0 (rst_last_error): B outside [0, 65535], F outside [1, 2^24], a bad record stride, a null or misaligned pointer (records 16 bytes). */
+int rst_frame_ingress(const uint8_t* staged, const int32_t* fmt, float* pcm_out, int B, int F, int64_t rec_stride, rst_stream_t stream);
+int rst_frame_egress(const float* wav, const int64_t* tokens, int tok_stride, const int64_t* offset_dev, int max_delay, const int32_t* fmt,
+                     uint8_t* out, int B, int F, int64_t rec_stride, rst_stream_t stream);
+
 /* Streaming history roll: hist_out [P_out steps] = last P_out steps of concat(hist_in [P_in steps], x [T_in steps])
  * (the `previous` buffer of RawStreamingConv1d, modules/streaming.py:224-236; conv-transpose keeps its input history the
  * same way instead of the reference's `partial` output buffer).  hist_out == hist_in (in-place roll, what a graph-replayed

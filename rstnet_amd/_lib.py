@@ -50,6 +50,8 @@ SIGNATURES = {
     "rst_convtr_depthwise_f32": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "rst_act_f32": [_p, _p, _l, _i, _p],
     "rst_transpose_f32": [_p, _p, _i, _i, _i, _p],
+    "rst_frame_ingress": [_p, _p, _p, _i, _i, _l, _p],
+    "rst_frame_egress": [_p, _p, _i, _p, _i, _p, _p, _i, _i, _l, _p],
     "rst_hist_update_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _p],
     "rst_hist_update_batch_f32": [C.POINTER(_p), C.POINTER(_p), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _i, _p],
     "rst_hist_seed_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _p],

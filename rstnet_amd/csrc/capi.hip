@@ -24,7 +24,7 @@ int rst_check_launch(const char* what) {
 
 extern "C" {
 
-int rst_version(void) { return 128; }      // 128: + rst_lm_attn_decode_ps_f32, rst_lm_rope_table_ps_f32, rst_lm_attn_prefill_ps_f32, rst_lm_ring_append_ps (per-stream ring positions, ragged append), rst_lm_sample_rows_f32, rst_depth_decode_frame_rows (per-row id limits); 127: + rst_lora_bank_shrink_f32, rst_lora_bank_expand_f32, rst_lora_bank_supported (per-row LoRA adapters from a device-resident bank); 126: + rst_resample_sinc, rst_resample_plan (sample-rate conversion of ragged batches and streams); 125: + rst_skinny_pack_weight_mxfp4w, rst_gemm_skinny_mxfp4w_f32 / _supported (MXFP4 weight-only skinny GEMM); 124: + rst_skinny_pack_weight_fp8w, rst_gemm_skinny_fp8w_f32 / _supported (fp8 weight-only skinny GEMM); 123: + rst_quant_blocks_mxfp4, rst_gemv_mxfp4w_f32 / _supported (MXFP4 weight-only GEMV); 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
+int rst_version(void) { return 129; }      // 129: + rst_frame_ingress, rst_frame_egress (packed frame records of a served batch); 128: + rst_lm_attn_decode_ps_f32, rst_lm_rope_table_ps_f32, rst_lm_attn_prefill_ps_f32, rst_lm_ring_append_ps (per-stream ring positions, ragged append), rst_lm_sample_rows_f32, rst_depth_decode_frame_rows (per-row id limits); 127: + rst_lora_bank_shrink_f32, rst_lora_bank_expand_f32, rst_lora_bank_supported (per-row LoRA adapters from a device-resident bank); 126: + rst_resample_sinc, rst_resample_plan (sample-rate conversion of ragged batches and streams); 125: + rst_skinny_pack_weight_mxfp4w, rst_gemm_skinny_mxfp4w_f32 / _supported (MXFP4 weight-only skinny GEMM); 124: + rst_skinny_pack_weight_fp8w, rst_gemm_skinny_fp8w_f32 / _supported (fp8 weight-only skinny GEMM); 123: + rst_quant_blocks_mxfp4, rst_gemv_mxfp4w_f32 / _supported (MXFP4 weight-only GEMV); 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
                                            // rst_rvq_search_chain_f32, rst_embed_sum_bf16(add_stride); 105: round 4
 const char* rst_last_error(void) { return g_err; }
 
@@ -398,6 +398,16 @@ int rst_gemv_mxfp4w_supported(int B, int N, int K) { return rst_gemv_mxfp4w_supp
 int rst_gemv_mxfp4w_f32(const float* x, const float* alpha, const uint8_t* q, const uint8_t* scale, const float* res, const float* bias,
                         float* y, int B, int N, int K, int ldx, int ldy, int prologue, float eps, int gate_out, rst_stream_t stream) {
     return rst_launch_gemv_mxfp4w(gemv_quant_params(x, alpha, q, scale, res, bias, y, B, N, K, ldx, ldy, prologue, eps, gate_out), (hipStream_t)stream);
+}
+
+int rst_frame_ingress(const uint8_t* staged, const int32_t* fmt, float* pcm_out, int B, int F, int64_t rec_stride, rst_stream_t stream) {
+    return rst_launch_frame_ingress(staged, fmt, pcm_out, B, F, (long)rec_stride, (hipStream_t)stream);
+}
+
+int rst_frame_egress(const float* wav, const int64_t* tokens, int tok_stride, const int64_t* offset_dev, int max_delay, const int32_t* fmt,
+                     uint8_t* out, int B, int F, int64_t rec_stride, rst_stream_t stream) {
+    return rst_launch_frame_egress(wav, (const long*)tokens, tok_stride, (const long*)offset_dev, max_delay, fmt, out, B, F, (long)rec_stride,
+                                   (hipStream_t)stream);
 }
 
 int rst_lora_bank_supported(int K, int r, int N) { return rst_lora_bank_supported_impl(K, r, N); }

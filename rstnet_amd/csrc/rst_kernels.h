@@ -149,6 +149,12 @@ int rst_launch_resample_sinc(const void* x, int x_dtype, long x_row_stride, int 
                              hipStream_t stream);
 int rst_resample_slab_bytes(int o, int n, int L);   // LDS bytes a tile stages its inputs in; 0 = read from global (span too long)
 
+// ---- frame_io.hip ------------------------------------------------------------------------------
+// packed frame records of a served batch, contracts at rst_frame_ingress / rst_frame_egress (include/rstnet_hip.h)
+int rst_launch_frame_ingress(const unsigned char* staged, const int* fmt, float* pcm_out, int B, int F, long rec_stride, hipStream_t stream);
+int rst_launch_frame_egress(const float* wav, const long* tokens, int tok_stride, const long* offset_dev, int max_delay, const int* fmt,
+                            unsigned char* out, int B, int F, long rec_stride, hipStream_t stream);
+
 // ---- lm_lora_bank.hip ---------------------------------------------------------------------------
 // per-row LoRA adapters from a bank, contract at rst_lora_bank_shrink_f32 / _expand_f32 (include/rstnet_hip.h)
 struct LoraBankShrinkParams {

@@ -20,6 +20,7 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from .slots import record_stride       # bytes between the records of a packed frame buffer (the layouts live in slots.py)
 
 ACT_NONE, ACT_ELU, ACT_GELU = 0, 1, 1   # act_in: 1 = ELU ; act_out: 1 = GELU
 ACT_ELU_OUT = 2                          # act_out: ELU applied last (after the residual)
@@ -857,6 +858,62 @@ def resample_sinc(x: torch.Tensor, in_lengths: Optional[torch.Tensor], filt: Opt
                                           int(lead), _ptr(out), y_stride, _ptr(out_lengths), B, T_out, _stream())
     if rc != 0:
         raise _lib.RstError(f"librstnet_hip error {rc}: {_lib.lib().rst_last_error().decode('utf-8', 'replace')}")
+    return out
+
+
+def _frame_records(buf: torch.Tensor, fmt: torch.Tensor, name: str, B: int, F: int) -> int:
+    _chk(buf, name, torch.uint8)
+    _chk(fmt, "fmt", torch.int32)
+    if buf.dim() != 2 or buf.shape[0] != B or buf.shape[1] < record_stride(F) or buf.shape[1] % 16:
+        raise ValueError(f"rstnet_amd.ops: `{name}` must be uint8 [{B}, REC] with REC a multiple of 16 and >= {record_stride(F)}, "
+                         f"got {tuple(buf.shape)}")
+    if tuple(fmt.shape) != (B,) or fmt.device != buf.device:
+        raise ValueError(f"rstnet_amd.ops: `fmt` must be int32 [{B}] on {buf.device}")
+    return int(buf.shape[1])
+
+
+@_on_tensor_device
+def frame_ingress(staged: torch.Tensor, fmt: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """Packed frame records -> the codec's input.  ``staged`` uint8 ``[B, REC]`` (per row: int32 ``present``, 12 reserved bytes, ``F``
+    samples in the row's transport), ``fmt`` int32 ``[B]`` (-1 free row, 0 f32, 1 s16), ``out`` fp32 ``[B, 1, F]``: f32 bits unchanged,
+    s16 as ``x / 32768``, zeros for a row without a frame or a free row (contract: ``rst_frame_ingress``, include/rstnet_hip.h)."""
+    _chk(out, "out")
+    if out.dim() != 3 or out.shape[1] != 1:
+        raise ValueError(f"rstnet_amd.ops: `out` must be fp32 [B, 1, F], got {tuple(out.shape)}")
+    B, _, F = out.shape
+    rec = _frame_records(staged, fmt, "staged", B, F)
+    if out.device != staged.device:
+        raise ValueError(f"rstnet_amd.ops: `out` is on {out.device}, `staged` on {staged.device}")
+    with _profiled("frame_ingress", 0.0, B * rec + 4 * B * F, (B, F)):
+        _lib.check(_lib.lib().rst_frame_ingress(_ptr(staged), _ptr(fmt), _ptr(out), B, F, rec, _stream()))
+    return out
+
+
+@_on_tensor_device
+def frame_egress(wav: torch.Tensor, tokens: torch.Tensor, offset_dev: torch.Tensor, max_delay: int, fmt: torch.Tensor,
+                 out: torch.Tensor) -> torch.Tensor:
+    """The frame's results -> packed records.  ``wav`` fp32 ``[B, 1, F]``, ``tokens`` int64 ``[B, 1 + dep_q]`` (rows of unit stride;
+    the text token first), ``offset_dev`` int64 ``[B]`` (the per-stream frame counters after the commit), ``out`` uint8 ``[B, REC]``.
+    A row is valid iff ``fmt[b] >= 0 and offset_dev[b] > max_delay``; header ``valid, text token or -1, payload bytes, 0``; payload f32
+    as it is or s16 as ``(int16)(clamp(x, -1, 1) * 32767)``; everything else zero (contract: ``rst_frame_egress``)."""
+    _chk(wav, "wav")
+    _chk(tokens, "tokens", torch.int64, contiguous=False)
+    _chk(offset_dev, "offset_dev", torch.int64)
+    if wav.dim() != 3 or wav.shape[1] != 1:
+        raise ValueError(f"rstnet_amd.ops: `wav` must be fp32 [B, 1, F], got {tuple(wav.shape)}")
+    B, _, F = wav.shape
+    rec = _frame_records(out, fmt, "out", B, F)
+    if tokens.dim() != 2 or tokens.shape[0] != B or tokens.shape[1] < 1 or tokens.stride(1) != 1 or (B > 1 and tokens.stride(0) < 1):
+        raise ValueError(f"rstnet_amd.ops: `tokens` must be int64 [{B}, n >= 1] rows of unit stride, got {tuple(tokens.shape)}")
+    if tuple(offset_dev.shape) != (B,):
+        raise ValueError(f"rstnet_amd.ops: `offset_dev` must be int64 [{B}] (a per-stream session), got {tuple(offset_dev.shape)}")
+    for t, name in ((tokens, "tokens"), (offset_dev, "offset_dev"), (out, "out")):
+        if t.device != wav.device:
+            raise ValueError(f"rstnet_amd.ops: `{name}` is on {t.device}, `wav` on {wav.device}")
+    tok_stride = tokens.stride(0) if B > 1 else tokens.shape[1]
+    with _profiled("frame_egress", 0.0, B * rec + 4 * B * F, (B, F)):
+        _lib.check(_lib.lib().rst_frame_egress(_ptr(wav), _ptr(tokens), int(tok_stride), _ptr(offset_dev), int(max_delay), _ptr(fmt),
+                                               _ptr(out), B, F, rec, _stream()))
     return out
 
 

@@ -13,6 +13,9 @@ memcpy.  ``/api/chat?pcm=opus`` selects ``OpusFramer`` -- the reference's ``sphn
 ``sphn`` package and says so when it is missing.  ``/api/chat?sr=<rate>`` (default: the codec's rate) lets a raw-PCM client send and receive
 at its own sample rate -- a browser's 48 kHz, telephony's 8 or 16 kHz -- in frames of ``client_geometry`` samples: the two conversions run on the
 device (``codec/audio_resample.py``: ``StreamResampler``), which is what the Opus library does for the reference's clients.
+
+``--slots N`` replaces the lock by N rows of one per-stream batch (``SlotServerState`` below): same protocol, N
+conversations at once, 503 instead of waiting when all rows are taken, one sample rate per server (``--client-rate``).
 """
 from __future__ import annotations
 
@@ -278,14 +281,276 @@ class ServerState:
         return ws
 
 
-def make_app(state: ServerState):
+class SlotServerState:
+    """``--slots N``: N conversations at once, each in one row of ONE ``StreamingPipeline(per_stream=True)`` of batch N that is entered
+    once and lives as long as the server.  A fixed clock runs one frame per codec frame period (sooner when every
+    occupied row already has its frame): ``tick`` applies the joins since the last tick in one ``reset_streams``, packs one record per
+    row from the inboxes, runs ``step_packed`` -- one upload, one graph replay, one download -- and turns the valid records into the
+    kind-1 / kind-2 messages of their slots.  A row without a frame at a tick is fed silence and counted (``underruns``); it is not
+    waited for.
+
+    Every GPU call is issued by ``tick`` (and ``warmup``), and ``tick`` runs on the event loop's own thread: ``join`` / ``push`` /
+    ``leave`` only touch host tables.  A frame blocks the loop for the ~8 ms of its graph out of an 80 ms period, in which nothing but
+    socket reads and writes would run; in exchange there is no second thread whose current stream, device guard or capture state could
+    differ from the one the graph was captured under, and the tables need no lock.
+
+    The driver API (``join`` / ``push`` / ``leave`` / ``tick``) works without sockets; ``handle_chat`` is a thin layer over it.
+    ``pipeline=``: anything with the pipeline's packed surface (the CPU tests pass a stand-in)."""
+
+    def __init__(self, mimi, lm, device, slots: int, client_rate: Optional[int] = None, text_tokenizer=None, lm_gen=None, pipeline=None,
+                 max_backlog: int = 4, **lm_gen_kwargs):
+        from . import slots as SL
+        if not 1 <= int(slots) <= 64:
+            raise ValueError(f"--slots takes 1 .. 64 rows, got {slots}")
+        self.SL, self.mimi, self.text_tokenizer, self.device, self.n = SL, mimi, text_tokenizer, device, int(slots)
+        self.codec_rate = int(getattr(mimi, "sample_rate", 24000))
+        self.frame_size = int(round(mimi.sample_rate / mimi.frame_rate)) if hasattr(mimi, "frame_rate") else mimi.frame_hop
+        self.period = self.frame_size / float(self.codec_rate)           # seconds per frame, from the codec (80 ms for Mimi)
+        self.client_rate = self.codec_rate if client_rate is None else int(client_rate)
+        if pipeline is None:
+            from .lm.model import LMGen
+            from .pipeline import StreamingPipeline
+            lm_gen = lm_gen if lm_gen is not None else LMGen(lm, **lm_gen_kwargs)
+            pipeline = StreamingPipeline(mimi, lm_gen, self.n, client_rate=None if self.client_rate == self.codec_rate else self.client_rate,
+                                         per_stream=True)
+            pipeline.__enter__()                                           # once: the session is the server's lifetime
+        self.pipe = pipeline
+        self.max_delay = int(self.pipe.lm_gen.max_delay)
+        self.F = int(self.pipe.client_frame)
+        self.table = SL.SlotTable(self.n)
+        self.max_backlog = int(max_backlog)
+        self.fmt: List[int] = [SL.FMT_FREE] * self.n                       # host mirror of the pipeline's fmt vector
+        self.inbox: List[Optional[object]] = [None] * self.n
+        self._freed: List[int] = []                                        # rows left since the last tick (their fmt word goes to -1 there)
+        self._on_live: dict = {}                                           # slot -> asyncio.Event set when its reset has been applied
+        self._outbox: dict = {}                                            # slot -> asyncio.Queue of (kind, payload)
+        self._staged = self.pipe.new_staged()
+        self._staged_np = self._staged.numpy()
+        self.ticks = 0
+        self._clock_task = None
+
+    def close(self) -> None:
+        """Ends the pipeline's session (its states and the captured frame are released).  The server process never needs to."""
+        self.pipe.__exit__(None, None, None)
+
+    # ---- driver API ----------------------------------------------------------------------------------------------------------------
+
+    def join(self, fmt: str) -> Optional[int]:
+        """Claims the lowest free row for a client whose transport is ``fmt`` (``"f32"`` / ``"s16"``); ``None`` when all are taken.  The
+        row starts its conversation at the next tick."""
+        SL = self.SL
+        if fmt not in SL.FMT_CODES:
+            raise ValueError(f"unknown pcm format {fmt!r}")
+        slot = self.table.acquire()
+        if slot is None:
+            return None
+        self.fmt[slot] = SL.FMT_CODES[fmt]
+        self.inbox[slot] = SL.Inbox(self.F * SL.sample_width(self.fmt[slot]), self.max_backlog)
+        return slot
+
+    def push(self, slot: int, payload: bytes) -> None:
+        """Incoming audio bytes of ``slot`` in its transport (any split; whole frames queue up, the oldest beyond ``max_backlog`` is dropped)."""
+        if self.table.state(slot) == self.SL.FREE:
+            raise ValueError(f"slot {slot} is free")
+        self.inbox[slot].push(payload)
+
+    def leave(self, slot: int) -> None:
+        """Frees the row.  It goes on computing (on silence) without anything being returned; it is reset when it is next acquired."""
+        self.table.release(slot)
+        self.fmt[slot] = self.SL.FMT_FREE
+        self._freed.append(slot)
+        self._on_live.pop(slot, None)
+        self._outbox.pop(slot, None)
+
+    def underruns(self, slot: int) -> int:
+        return self.inbox[slot].underruns
+
+    def dropped(self, slot: int) -> int:
+        return self.inbox[slot].dropped
+
+    def tick(self) -> dict:
+        """One frame for every row -> ``{slot: [(kind, payload bytes), ...]}`` for the rows that produced output."""
+        SL = self.SL
+        for b in self._freed:
+            if self.table.state(b) == SL.FREE:
+                self.pipe.set_row_format(b, SL.FMT_FREE)
+        self._freed = []
+        joined = self.table.rows(SL.JOINING)
+        if joined:
+            self.pipe.reset_streams(joined)                # ONE call for all of them: a reset's host cost does not grow with the row count
+            for b in joined:
+                self.pipe.set_row_format(b, self.fmt[b])
+                self.table.mark_live(b)
+        frames: List[Optional[bytes]] = [None] * self.n
+        for b in self.table.rows(SL.LIVE):
+            frames[b] = self.inbox[b].pop()
+            if frames[b] is None and b not in joined:      # (the tick that applies a join precedes the handshake: no frame is owed yet)
+                self.inbox[b].underruns += 1
+        SL.pack_staged(self._staged_np, frames, self.fmt, self.F)
+        records = self.pipe.step_packed(self._staged)
+        self.ticks += 1
+        out: dict = {}
+        live = set(self.table.rows(SL.LIVE))
+        for b, rec in enumerate(SL.parse_records(records.numpy(), self.F)):
+            if rec is None or b not in live:
+                continue
+            token, payload = rec
+            msgs = [(KIND_AUDIO, payload)]
+            piece = self.text_piece(token)
+            if piece is not None:
+                msgs.append((KIND_TEXT, piece.encode("utf8")))
+            out[b] = msgs
+        for b in joined:
+            ev = self._on_live.get(b)
+            if ev is not None:
+                ev.set()
+        return out
+
+    text_piece = ServerState.text_piece
+
+    def warmup(self) -> None:
+        """``max_delay + 3`` silent frames with every row free: the modules' eager frames, then the capture -- before the first client."""
+        with torch.no_grad():
+            for _ in range(self.max_delay + 3):
+                self.tick()
+        fused = getattr(self.pipe, "_fused", None)
+        wants_graph = getattr(self.pipe, "fuse", False) and torch.device(self.device).type == "cuda"
+        if wants_graph and not (fused is not None and fused.disable):
+            assert fused is not None and fused.graph is not None, "the served frame was not captured during warm-up"
+
+    # ---- sockets -------------------------------------------------------------------------------------------------------------------
+
+    async def clock(self) -> None:
+        """The one place frames are run from: polls the inboxes and runs ``tick`` when ``slots.tick_due`` says so."""
+        SL = self.SL
+        loop = asyncio.get_running_loop()
+        last = loop.time()
+        while True:
+            await asyncio.sleep(0.002)
+            occupied = self.table.occupied()
+            # a joining row waits for nothing but its reset: it counts as ready
+            ready = [b for b in occupied if self.table.state(b) == SL.JOINING or len(self.inbox[b]) > 0]
+            now = loop.time()
+            if not SL.tick_due(ready, occupied, now - last, self.period):
+                if not occupied:
+                    last = now
+                continue
+            last = now
+            with torch.no_grad():
+                msgs = self.tick()
+            for slot, items in msgs.items():
+                q = self._outbox.get(slot)
+                if q is not None:
+                    for item in items:
+                        q.put_nowait(item)
+
+    async def start_clock(self, app=None) -> None:
+        self._clock_task = asyncio.get_running_loop().create_task(self.clock())
+
+    async def stop_clock(self, app=None) -> None:
+        if self._clock_task is not None:
+            self._clock_task.cancel()
+            try:
+                await self._clock_task
+            except asyncio.CancelledError:
+                pass
+            self._clock_task = None
+
+    async def handle_chat(self, request):
+        from aiohttp import WSMsgType, web
+        # everything that can refuse a client is settled BEFORE the upgrade: transport and rate (400), a free row (503)
+        try:
+            rate, client_frame = client_geometry(request.query.get("sr"), self.codec_rate, self.frame_size)
+            if rate != self.client_rate:
+                raise ValueError(f"this server serves clients at {self.client_rate} Hz (--client-rate); ?sr={rate} is another rate")
+            kind = request.query.get("pcm", "f32")
+            framer = make_framer(self.F, kind, rate) if kind == "opus" else None
+            if kind != "opus" and kind not in self.SL.FMT_CODES:
+                raise ValueError(f"unknown pcm format {kind!r}")
+        except (ValueError, RuntimeError) as e:
+            raise web.HTTPBadRequest(text=str(e))
+        slot = self.join("f32" if framer is not None else kind)        # an Opus client's row runs as f32 behind its own host framer
+        if slot is None:
+            raise web.HTTPServiceUnavailable(text=f"all {self.n} slots are taken; try again when a conversation has ended")
+        live, outbox = asyncio.Event(), asyncio.Queue()
+        self._on_live[slot], self._outbox[slot] = live, outbox
+        close = False
+        try:
+            ws = web.WebSocketResponse()
+            await ws.prepare(request)
+
+            async def recv_loop():
+                nonlocal close
+                try:
+                    async for message in ws:
+                        if message.type == WSMsgType.ERROR:
+                            log("error", f"{ws.exception()}")
+                            break
+                        if message.type in (WSMsgType.CLOSED, WSMsgType.CLOSE):
+                            break
+                        if message.type != WSMsgType.BINARY:
+                            log("error", f"unexpected message type {message.type}")
+                            continue
+                        data = message.data
+                        if len(data) == 0:
+                            log("warning", "empty message")
+                            continue
+                        if data[0] != KIND_AUDIO:
+                            log("warning", f"unknown message kind {data[0]}")
+                        elif framer is None:
+                            self.push(slot, data[1:])
+                        else:
+                            framer.append_bytes(data[1:])
+                            for pcm in framer.frames():
+                                self.push(slot, np.asarray(pcm, dtype="<f4").tobytes())
+                finally:
+                    close = True
+                    log("info", f"slot {slot}: connection closed")
+
+            async def send_loop():
+                while not close or not outbox.empty():
+                    try:
+                        kind_out, payload = await asyncio.wait_for(outbox.get(), timeout=0.005)
+                    except asyncio.TimeoutError:
+                        continue
+                    if framer is not None and kind_out == KIND_AUDIO:
+                        payload = framer.encode(np.frombuffer(payload, dtype="<f4"))
+                        if len(payload) == 0:           # (an Opus writer hands out whole pages: nothing yet is not a message)
+                            continue
+                    try:
+                        await ws.send_bytes(bytes([kind_out]) + payload)
+                    except (ConnectionError, RuntimeError):
+                        return
+
+            log("info", f"slot {slot}: accepted connection")
+            await live.wait()                           # the row's reset has been applied: the conversation starts with the next frame
+            await ws.send_bytes(bytes([KIND_HANDSHAKE]))
+            await asyncio.gather(recv_loop(), send_loop())
+        finally:
+            self.leave(slot)
+        log("info", f"slot {slot}: done with connection")
+        return ws
+
+
+def make_app(state):
     from aiohttp import web
     app = web.Application()
     app.router.add_get("/api/chat", state.handle_chat)
+    if isinstance(state, SlotServerState):
+        app.on_startup.append(state.start_clock)
+        app.on_cleanup.append(state.stop_clock)
     return app
 
 
-def build_state(args, log_fn: Callable[[str, str], None] = log) -> ServerState:
+def make_state(mimi, lm, device, args, text_tokenizer=None):
+    """``ServerState`` (one session behind a lock, the reference's loop) unless ``--slots N`` asks for the slot server."""
+    slots = getattr(args, "slots", None)
+    if slots is None:
+        return ServerState(mimi, lm, device, text_tokenizer=text_tokenizer)
+    return SlotServerState(mimi, lm, device, slots=slots, client_rate=getattr(args, "client_rate", None), text_tokenizer=text_tokenizer)
+
+
+def build_state(args, log_fn: Callable[[str, str], None] = log):
     """Models for the CLI: checkpoints (``--mimi-weight`` / ``--moshi-weight``, safetensors or torch files) or ``--synthetic``
     seeded random-init weights of the real shapes (there is no hub access in this image)."""
     from . import synth
@@ -293,6 +558,8 @@ def build_state(args, log_fn: Callable[[str, str], None] = log) -> ServerState:
     from .lm.model import LMModel
     device = torch.device(args.device)
     if device.type == "cuda":
+        if device.index is None:         # the default `--device cuda`: set_device wants an index
+            device = torch.device("cuda", torch.cuda.current_device())
         torch.cuda.set_device(device)
     cfg = dict(synth.LM_MOSHI_7B if args.lm_config == "moshi7b" else synth.LM_TINY_16Q)
     if args.synthetic:
@@ -309,7 +576,7 @@ def build_state(args, log_fn: Callable[[str, str], None] = log) -> ServerState:
         import sentencepiece
         tok = sentencepiece.SentencePieceProcessor(args.tokenizer)
     log_fn("info", "models loaded")
-    return ServerState(mimi, lm, device, text_tokenizer=tok)
+    return make_state(mimi, lm, device, args, text_tokenizer=tok)
 
 
 def main(argv=None) -> None:
@@ -331,7 +598,16 @@ def main(argv=None) -> None:
     p.add_argument("--lm-mxfp4-batched", action="store_true",
                    help="with --lm-weights mxfp4: stream the MXFP4 copies above two streams too (weight-only MXFP4 skinny GEMM) instead of "
                         "reading those matrices as bf16 there; same values, a quarter of the bytes, no packed bf16 copies (opt-in)")
+    p.add_argument("--slots", type=int, default=None,
+                   help="serve up to N conversations at once (1 .. 64), each in one row of a per-stream batch of N behind one frame graph; a "
+                        "client beyond N is refused with 503.  Without it: one session at a time behind a lock, as the reference serves")
+    p.add_argument("--client-rate", type=int, default=None,
+                   help="with --slots: the one sample rate of every raw-PCM client (default: the codec's); another ?sr= is refused with 400")
     args = p.parse_args(argv)
+    if args.slots is not None and not 1 <= args.slots <= 64:
+        p.error("--slots takes 1 .. 64")
+    if args.client_rate is not None and args.slots is None:
+        p.error("--client-rate needs --slots (without it every client names its own rate with ?sr=)")
     if args.lm_mxfp4_batched and args.lm_weights != "mxfp4":
         p.error("--lm-mxfp4-batched needs --lm-weights mxfp4")
     if not args.synthetic and not (args.moshi_weight and args.mimi_weight):
