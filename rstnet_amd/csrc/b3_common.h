@@ -20,6 +20,31 @@ __device__ __forceinline__ unsigned b3_peel(f32x2& v) {
     return h;
 }
 
+// the fp32 values of a staged row piece as two pairs, ready to peel: padding cleared (MK: mask is all ones for data, zero for padding),
+// ELU applied
+template <bool MK, bool ELU>
+__device__ __forceinline__ void b3_take_a(const f32x4 src, const int mask, f32x2 (&v)[2]) {
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    f32x4 x = src;
+    if (MK) x = __builtin_bit_cast(f32x4, __builtin_bit_cast(i32x4, x) & mask);
+    if (ELU) {
+        x[0] = rst_elu(x[0]); x[1] = rst_elu(x[1]); x[2] = rst_elu(x[2]); x[3] = rst_elu(x[3]);
+    }
+    v[0] = f32x2{x[0], x[1]};
+    v[1] = f32x2{x[2], x[3]};
+}
+
+// the accumulators of a wave's TM x TN blocks of 32 x 32, at the start of a tile
+template <int TM, int TN>
+__device__ __forceinline__ void b3_clear(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+}
+
 // ---- window-sharing tiles of the conv GEMMs (gemm_win_b3_stream_shared_kernel) --------------------------------------------------------
 // A causal convolution whose window is R groups of G = S * C floats (K = R * G, left padding (R - 1) * S frames) reads, for output
 // row t of an utterance, the groups t - (R - 1) .. t of that utterance's flat activations.  A row tile stages 128 consecutive groups

@@ -458,14 +458,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KB == 16 ? 
     };
 
     f32x16 acc[TM][TN];
-    auto clear = [&]() {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-    };
     auto mma_tile = [&](int buf, int ks0, int ks1) {
         const float* a = As + buf * BM * LDS_LD + (wm * TM * 32 + frag_row) * LDS_LD + frag_k;
         const float* b = Bs + buf * BN * LDS_LD + (wn * TN * 32 + frag_row) * LDS_LD + frag_k;
@@ -526,7 +518,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KB == 16 ? 
         const int m0n = (tile_n / tiles_n) * BM, n0n = (tile_n % tiles_n) * BN;
         bool fast_n = false;
         if (fast) {
-            clear();
+            b3_clear(acc);
             int lkt = 2;                 // k-tile the next request fetches
             for (int kt = 0; kt < nk; ++kt) {
                 if (lkt == nk) {
@@ -566,38 +558,42 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KB == 16 ? 
 // (tests: <= 2e-6 of the fp64 value's scale, the same bound the f32-instruction path meets; RVQ codes as exact as with it) at
 // 6 x 32 = 192 matrix-pipe cycles per 32x32x16 block instead of 8 x 64 = 512.
 // Weights are split once on the host side of the ABI (rst_gemm_win_b3_pack_weight) into matrix-instruction operand order
-// [block of 32 rows][K / 16][plane][64 lanes][8 k] (round 5, DIRW below: every wave requests the fragments of its own columns from
-// L2 straight into registers; the tools build keeps the round-3 form, [n tile of 128][K / 16][plane][128 row slots][16 k] staged through
-// LDS, for the A/B of DESIGN.md 3.1b); activations stay fp32 in HBM
-// and are split on their way into LDS (v_cvt_pk_bf16_f32 + subtractions, ~4.5 VALU per element).  LDS rows are 16 bf16 + 8 pad
-// = 48 bytes: the 16 lanes of a ds_read_b128 group hold rows that are distinct mod 16, and 3 * row mod 16 is a bijection, so every
-// group covers 16 distinct 16-byte slots.  Two buffers of 128 activation rows x 3 planes: 36 KB (staged form: (128 + BN) rows, 72 /
-// 108 KB).  Rows whose window leaves the utterance are masked inside the kernel (below); only
-// launches with a history buffer / replicate padding / K % 64 != 0 run on the f32-instruction kernels above.
+// [block of 32 rows][K / 16][plane][64 lanes][8 k]: every wave requests the fragments of its own columns from L2 straight into
+// registers (below).  Activations stay fp32 in HBM and are split on their way into LDS (v_cvt_pk_bf16_f32 + subtractions, ~4.5 VALU
+// per element).  LDS rows are 16 bf16 + 8 pad = 48 bytes: the 16 lanes of a ds_read_b128 group hold rows that are distinct mod 16, and
+// 3 * row mod 16 is a bijection, so every group covers 16 distinct 16-byte slots.  Two buffers of 128 activation rows x 3 planes:
+// 36 KB.  Rows whose window leaves the utterance are masked inside the kernel (below); only launches with a history buffer /
+// replicate padding / K % 64 != 0 run on the f32-instruction kernels above.
 
 constexpr int B3_SETS_A = 4;                  // k-tiles of activations / of weights held in registers ahead of the one being multiplied
 constexpr int B3_SETS_B = 2;
 constexpr int B3_KB = 16;                     // k per stage (one bf16 matrix instruction deep)
 constexpr int B3_RS = 24;                     // shorts per LDS row (16 + 8 pad)
-constexpr int B3_WTILE = 3 * 128 * B3_KB;     // shorts per packed (n tile, k tile) piece of the weights
 
 template <int V>
 struct b3_int { static constexpr int value = V; };
 
-// LDS rows are 48 bytes apart, so the rows whose 32-byte (activations: 4 lanes x 8 bytes; weights: 2 lanes x 16) pieces tile a
-// 128-byte bank window are r, r + 2, r + 4, r + 6: a write group (16 / 8 consecutive lanes = four consecutive row slots) is given
-// exactly those.  Slot g of a pass therefore stages row b3_row(g) (and the packed weights hold row b3_row(g) at slot g): with the
-// identity map every write group ran 2-way conflicted, a third of the kernel's LDS cycles (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE).
+// LDS rows are 48 bytes apart, so the rows whose 32-byte pieces (4 lanes x 8 bytes) tile a 128-byte bank window are r, r + 2, r + 4,
+// r + 6: a write group (16 consecutive lanes = four consecutive row slots) is given exactly those.  Slot g of a pass therefore stages
+// row b3_row(g): with the identity map every write group ran 2-way conflicted, a third of the kernel's LDS cycles
+// (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE).
 __host__ __device__ __forceinline__ constexpr int b3_row(int g) { return (g & ~7) | (2 * (g & 3) + ((g >> 2) & 1)); }
-__host__ __device__ __forceinline__ constexpr int b3_slot(int r) { return (r & ~7) | (((r & 7) >> 1) + 4 * (r & 1)); }
 
 // The stream of k-tiles (tile after tile, as in gemm_win_stream_kernel) is a software pipeline in registers.  A stage (768 matrix-pipe
 // cycles, ~0.35 us) is shorter than a loaded round trip to L2 / HBM, so the loads run several stages ahead: the fp32 activation rows
-// of k-tile g + 4 and the weight planes (L2-resident) of k-tile g + 2 are requested at the top of stage g, four / two register sets
-// rotate, and the rotation is written out (b3_int<0..3>; K is a multiple of 64, so every tile starts on set 0).  While k-tile g is
-// multiplied out of one LDS buffer, k-tile g + 1 is split and written to the other buffer BETWEEN this stage's matrix instructions -- one 4-instruction peel
-// or one LDS write behind every second one, pinned there with scheduling fences: the wave issues in order, and whatever sits in
-// front of the first matrix instruction is time the pipe idles.
+// of k-tile g + 4 are requested at the top of stage g, the weight planes (L2-resident) of k-tile g + 2 inside it, four / two register
+// sets rotate, and the rotation is written out (b3_int<0..3>; K is a multiple of 64, so every tile starts on set 0).  While k-tile g
+// is multiplied out of one LDS buffer, k-tile g + 1 is split and written to the other buffer BETWEEN this stage's matrix instructions
+// -- one 4-instruction peel or one LDS write behind every second one, pinned there with scheduling fences: the wave issues in order,
+// and whatever sits in front of the first matrix instruction is time the pipe idles.
+// The weight fragments never pass through LDS.  The packed weights are in matrix-instruction operand order ([32-column
+// block][k-tile][plane][64 lanes][8 bf16]: a wave-level load is one contiguous KB, as in lm_skinny.hip) and every wave requests the
+// fragments of its own 64 columns straight into the registers the matrix instructions read -- two k-tiles ahead, each plane into
+// the registers its last product of the current k-tile has just released.  LDS holds the split activations only: against staging the
+// weight planes too, a third of the write instructions and half of the fragment reads of a stage are gone (what the ablation table
+// prices highest), at the cost of the weights crossing the L1 once per wave row (twice per workgroup) instead of once.  (The form of
+// rounds 3 / 4 that staged the weight planes through LDS lost on all 22 layers, profiles/r05_b3_direct_vs_staged.txt and
+// profiles/r06_b3_ablation.txt; commit 486b2d9 is the last that contains it.)
 // MASK: the launch has rows whose window reaches into the zero padding in front of / behind an utterance, or ragged last tiles.
 // Since C % 16 == 0, a window leaves its utterance on a k-tile boundary: every row carries the range [klo, khi) of k-tiles it really
 // reads, a k-tile outside it is loaded from a valid address of the same row and cleared when it is consumed (a bit per row travels
@@ -607,20 +603,14 @@ __host__ __device__ __forceinline__ constexpr int b3_slot(int r) { return (r & ~
 // (VALU + LDS writes) per matrix instruction: measured (tools build, RST_B3_DBG) that work is what the 128-wide form spends most on.
 // DBG (tools build only, WRONG results): 1 = no split / LDS writes, 2 = no global loads, 3 = matrix instructions only, 4 = no barriers,
 // 5 = LDS writes of unsplit bits (what activations handed over already split would cost)
-// DIRW: the weight fragments never pass through LDS.  The packed weights are then in matrix-instruction operand order ([32-column
-// block][k-tile][plane][64 lanes][8 bf16]: a wave-level load is one contiguous KB, as in lm_skinny.hip) and every wave requests the
-// fragments of its own 64 columns straight into the registers the matrix instructions read -- two k-tiles ahead, each plane into
-// the registers its last product of the current k-tile has just released.  LDS then holds the split activations only: a third of
-// the write instructions and half of the fragment reads of a stage are gone (what the ablation table prices highest), at the cost
-// of the weights crossing the L1 once per wave row (twice per workgroup) instead of once.
-template <bool ELU, bool MASK, int NWN, int DBG = 0, bool BUFL = true, bool DIRW = false>
+template <bool ELU, bool MASK, int NWN, int DBG = 0>
 __global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_win_b3_stream_kernel(const GemmWinParams p, const int tiles) {
     constexpr int TM = 2, TN = 2;
     constexpr int NT = 128 * NWN;                  // threads
     constexpr int BM = 128, BN = 64 * NWN;
     constexpr int RA = 512 / NT;                   // activation row passes: NT / 4 row slots x 4 threads (16 bytes of fp32 each) per pass
-    constexpr int A_PLANE = BM * B3_RS, W_PLANE = DIRW ? 0 : BN * B3_RS;          // shorts per plane in LDS
-    constexpr int BUF = 3 * (A_PLANE + W_PLANE);                       // shorts per buffer: activation planes 0..2, weight planes 0..2
+    constexpr int A_PLANE = BM * B3_RS;            // shorts per plane in LDS
+    constexpr int BUF = 3 * A_PLANE;               // shorts per buffer: the three activation planes
     constexpr int NSA = B3_SETS_A, NSB = B3_SETS_B;
     static_assert(NSA == 4 && NSB == 2, "the rotation below is written out for four activation sets and two weight sets");
     static_assert(NWN == 2 || NWN == 4, "two or four waves along N");
@@ -676,24 +666,18 @@ __global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2)
             c.ao[j] = (unsigned)(off * 4);
         }
     };
-    // this thread's 16 bytes of plane 0 of the tile's first k-tile: the packed weights come in 128-row tiles of [k-tile][plane][128][16]
-    // DIRW: [32-column block][k-tile][plane][64 lanes][8]: 3 KB per (block, k-tile); the wave's first block is part of the lane offset
-    auto w_tile = [&](int n0) {
-        return DIRW ? (unsigned)(n0 / 32) * (unsigned)nk * 3072u : (unsigned)(n0 / 128) * (unsigned)nk * (unsigned)(B3_WTILE * 2);
-    };      // (bytes, uniform; the thread's part is wo)
-    const unsigned wo = DIRW ? (unsigned)(wn * TN) * (unsigned)nk * 3072u + (unsigned)lane * 16u
-                             : (unsigned)(((long)(tid >> 8) * nk * B3_WTILE + (tid & 255) * 8) * 2);      // bytes
-    const unsigned wo_blk = (unsigned)nk * 3072u;       // DIRW: from one 32-column block to the next
+    // the packed weights, [32-column block][k-tile][plane][64 lanes][8]: 3 KB per (block, k-tile).  w_tile: the tile's first block
+    // (bytes, uniform); the wave's first block inside the tile is part of the lane offset wo
+    auto w_tile = [&](int n0) { return (unsigned)(n0 / 32) * (unsigned)nk * 3072u; };
+    const unsigned wo = (unsigned)(wn * TN) * (unsigned)nk * 3072u + (unsigned)lane * 16u;      // bytes
+    const unsigned wo_blk = (unsigned)nk * 3072u;       // from one 32-column block to the next
 
     f32x4 ra[NSA][RA];
     int rm[NSA][RA];                 // MASK: all ones where row j of the set is real data, zero where it is padding
-    u32x4 rb[NSB][3];                // !DIRW: the thread's staging pieces of a k-tile's three weight planes
-    u32x4 rw[NSB][TN][3];            // DIRW: the wave's weight fragments (32-column block j, plane q) of k-tiles g, g + 1 (sets g % 2)
-    // LDS destinations of this thread's pieces (shorts from the start of a buffer)
+    u32x4 rw[NSB][TN][3];            // the wave's weight fragments (32-column block j, plane q) of k-tiles g, g + 1 (sets g % 2)
+    // LDS position of this thread's staged piece and of its fragments (shorts from the start of a buffer)
     const int a_dst = lrow * B3_RS + lk;
-    const int b_dst = 3 * A_PLANE + ((tid >> 8) * 128 + b3_row((tid & 255) >> 1)) * B3_RS + (tid & 1) * 8;
     const int a_frag = (wm * TM * 32 + frag_row) * B3_RS + frag_k;
-    const int b_frag = 3 * A_PLANE + (wn * TN * 32 + frag_row) * B3_RS + frag_k;
 
     // Requests go out as buffer loads: resource (base pointer) and the k-tile's byte offset in scalar registers, the thread's own
     // offset a 32-bit vector register set up once per tile -- no address arithmetic on the vector unit in the K loop (the launcher
@@ -709,120 +693,64 @@ __global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2)
                 const bool ok = d < (unsigned)c.kn[j];
                 mask[j] = ok ? -1 : 0;
                 const unsigned vo = c.ao[j] + (ok ? d : 0u) * (B3_KB * 4);
-                if (BUFL) dst[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, vo, 0, 0));
-                else dst[j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(p.x) + vo);
+                dst[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, vo, 0, 0));
             } else {
-                if (BUFL) dst[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, c.ao[j], kt * (B3_KB * 4), 0));
-                else dst[j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(p.x) + (long)kt * (B3_KB * 4) + c.ao[j]);
+                dst[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, c.ao[j], kt * (B3_KB * 4), 0));
             }
         }
     };
-    // wb: byte offset of the tile's first k-tile inside the packed weights (uniform)
-    auto load_w = [&](const unsigned wb, const int kt, u32x4 (&dst)[3]) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const unsigned so = wb + (unsigned)kt * (B3_WTILE * 2) + q * (128 * B3_KB * 2);
-            if (BUFL) dst[q] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, wo, so, 0);
-            else dst[q] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(p.w3) + so + wo);
-        }
-    };
-    // DIRW: plane q of the wave's TN blocks of k-tile kt (stream position relative to wb) into set U
+    // plane q of the wave's TN blocks of k-tile kt (stream position relative to wb, the byte offset of the tile's first k-tile inside
+    // the packed weights, uniform) into set U
     auto load_wq = [&](auto UU, auto QQ, const unsigned wb, const int kt) {
         constexpr int U = decltype(UU)::value, q = decltype(QQ)::value;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const unsigned so = wb + (unsigned)kt * 3072u + q * 1024u;
-            if (BUFL) rw[U][j][q] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, wo + j * wo_blk, so, 0);
-            else rw[U][j][q] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(p.w3) + so + wo + j * wo_blk);
+            rw[U][j][q] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, wo + j * wo_blk, so, 0);
         }
-    };
-    // the fp32 values of a staged row piece as two pairs: padding cleared (MASK), ELU applied
-    auto take_a = [&](auto MM, const f32x4 src, const int mask, f32x2 (&v)[2]) {
-        typedef int i32x4 __attribute__((ext_vector_type(4)));
-        f32x4 x = src;
-        if (decltype(MM)::value != 0) x = __builtin_bit_cast(f32x4, __builtin_bit_cast(i32x4, x) & mask);
-        if (ELU) {
-            x[0] = rst_elu(x[0]); x[1] = rst_elu(x[1]); x[2] = rst_elu(x[2]); x[3] = rst_elu(x[3]);
-        }
-        v[0] = f32x2{x[0], x[1]};
-        v[1] = f32x2{x[2], x[3]};
     };
 
     f32x16 acc[TM][TN];
-    auto clear = [&]() {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-    };
 
     // one stage: the k-tile of LDS buffer `buf` into the accumulators; register sets S -- the k-tile after it -- into buffer buf ^ 1;
     // the requests of the stream positions ahead (activations: context c, k-tile kta; weights: bp, ktb) into the sets just freed
     auto stage = [&](auto SS, auto MM, const Ctx& c, const int kta, const unsigned bp, const int ktb, const int buf) {
         constexpr int S = decltype(SS)::value;
-        constexpr int F = (S + 3) % 4, SB = S % 2, FB = (S + 1) % 2;
-        if (DBG != 2 && DBG != 3) {
-            // weights first: the wait for them counts requests in order, and must leave the younger activation requests in flight
-            if (!DIRW) {
-                load_w(bp, ktb, rb[FB]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            load_a(MM, c, kta, ra[F], rm[F]);
-        }
-        bf16x8 fa[TM][3], fb[TN][3];
+        constexpr int F = (S + 3) % 4, SB = S % 2;
+        if (DBG != 2 && DBG != 3) load_a(MM, c, kta, ra[F], rm[F]);
+        bf16x8 fa[TM][3];
         const short* rd = lds + buf * BUF;
         short* wr = lds + (buf ^ 1) * BUF;
-        // fragments in the order the products below consume them
-        // !DIRW: smallest terms first: lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi.  DIRW: the three products of weight plane 0 first,
-        // then plane 2, then plane 1 -- a plane's registers are re-requested (k-tile g + 2) as soon as its last product has issued, which
-        // gives every request >= 1.5 stages; the order inside a k-tile moves the result by roundings of the running sum only
-        constexpr int QA[6] = {2, DIRW ? 1 : 0, DIRW ? 0 : 1, DIRW ? 0 : 1, DIRW ? 1 : 0, 0};
-        constexpr int QB[6] = {0, DIRW ? 0 : 2, DIRW ? 0 : 1, DIRW ? 2 : 0, 1, DIRW ? 1 : 0};
-        if (DIRW && DBG != 3) {
+        // fragments in the order the products below consume them: the three products of weight plane 0 first, then plane 2, then
+        // plane 1 -- a plane's registers are re-requested (k-tile g + 2) as soon as its last product has issued, which gives every
+        // request >= 1.5 stages; the order inside a k-tile moves the result by roundings of the running sum only
+        constexpr int QA[6] = {2, 1, 0, 0, 1, 0};
+        constexpr int QB[6] = {0, 0, 0, 2, 1, 1};
+        if (DBG != 3) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) fa[i][2] = *reinterpret_cast<const bf16x8*>(rd + a_frag + 2 * A_PLANE + i * 32 * B3_RS);
 #pragma unroll
             for (int i = 0; i < TM; ++i) fa[i][1] = *reinterpret_cast<const bf16x8*>(rd + a_frag + A_PLANE + i * 32 * B3_RS);
 #pragma unroll
             for (int i = 0; i < TM; ++i) fa[i][0] = *reinterpret_cast<const bf16x8*>(rd + a_frag + i * 32 * B3_RS);
-        } else if (DBG != 3) {
+        } else {        // matrix instructions only: whatever bits the registers of set S hold
 #pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j][0] = *reinterpret_cast<const bf16x8*>(rd + b_frag + j * 32 * B3_RS);
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i][2] = *reinterpret_cast<const bf16x8*>(rd + a_frag + 2 * A_PLANE + i * 32 * B3_RS);
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i][0] = *reinterpret_cast<const bf16x8*>(rd + a_frag + i * 32 * B3_RS);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j][2] = *reinterpret_cast<const bf16x8*>(rd + b_frag + 2 * W_PLANE + j * 32 * B3_RS);
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i][1] = *reinterpret_cast<const bf16x8*>(rd + a_frag + A_PLANE + i * 32 * B3_RS);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j][1] = *reinterpret_cast<const bf16x8*>(rd + b_frag + W_PLANE + j * 32 * B3_RS);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
+            for (int q = 0; q < 3; ++q)
 #pragma unroll
                 for (int i = 0; i < TM; ++i) fa[i][q] = __builtin_bit_cast(bf16x8, ra[S][0]);
-#pragma unroll
-                for (int jj = 0; jj < TN; ++jj) fb[jj][q] = __builtin_bit_cast(bf16x8, rb[SB][q]);
-            }
         }
         __builtin_amdgcn_sched_barrier(0);
 
         f32x2 v[RA][2];
         u32x2 h[RA];
         constexpr bool SIDE = DBG != 1 && DBG != 3;
-        // side work, one small piece per slot: 0..2 the weight planes' LDS writes; then per plane q: 2 * RA half-row peels (4 VALU
-        // each) and the plane's LDS write
-        constexpr int PB = 2 * RA + 1, WOPS = DIRW ? 0 : 3, NOPS = WOPS + 3 * PB;       // 18 (RA = 2: slots 1 .. 18) or 12 (RA = 1: the odd slots); DIRW: 15 / 9
+        // side work, one small piece per slot: per plane q 2 * RA half-row peels (4 VALU each) and the plane's LDS write
+        constexpr int PB = 2 * RA + 1, NOPS = 3 * PB;       // 15 (RA = 2: slots 1 .. 15) or 9 (RA = 1: the odd slots)
 #pragma unroll
         for (int m = 0; m < 24; ++m) {
             const int t = m >> 2, i = (m >> 1) & 1, j = m & 1;
-            if (DIRW && DBG != 3) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][QA[t]], __builtin_bit_cast(bf16x8, rw[SB][j][QB[t]]), acc[i][j], 0, 0, 0);
-            else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][QA[t]], fb[j][QB[t]], acc[i][j], 0, 0, 0);
-            if (DIRW && DBG != 2 && DBG != 3) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][QA[t]], __builtin_bit_cast(bf16x8, rw[SB][j][QB[t]]), acc[i][j], 0, 0, 0);
+            if (DBG != 2 && DBG != 3) {
                 // a weight plane's last product of this k-tile has issued: its registers take the plane of k-tile g + 2 (same set)
                 if (m == 11) load_wq(b3_int<SB>{}, b3_int<0>{}, bp, ktb);
                 if (m == 15) load_wq(b3_int<SB>{}, b3_int<2>{}, bp, ktb);
@@ -830,22 +758,17 @@ __global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2)
             }
             if (SIDE && m == 0) {
 #pragma unroll
-                for (int r = 0; r < RA; ++r) take_a(MM, ra[S][r], rm[S][r], v[r]);
+                for (int r = 0; r < RA; ++r) b3_take_a<decltype(MM)::value != 0, ELU>(ra[S][r], rm[S][r], v[r]);
             }
             const int op = RA == 2 ? m - 1 : ((m & 1) ? (m - 1) >> 1 : -1);
             if (SIDE && op >= 0 && op < NOPS) {
-                if (op < WOPS) {
-                    *reinterpret_cast<u32x4*>(wr + b_dst + op * W_PLANE) = rb[SB][op];
+                const int q = op / PB, w = op % PB;
+                if (w < 2 * RA) {
+                    if (DBG == 5) h[w >> 1][w & 1] = __builtin_bit_cast(unsigned, v[w >> 1][w & 1][0]) + q;
+                    else h[w >> 1][w & 1] = b3_peel(v[w >> 1][w & 1]);
                 } else {
-                    const int u = op - WOPS;
-                    const int q = u / PB, w = u % PB;
-                    if (w < 2 * RA) {
-                        if (DBG == 5) h[w >> 1][w & 1] = __builtin_bit_cast(unsigned, v[w >> 1][w & 1][0]) + q;
-                        else h[w >> 1][w & 1] = b3_peel(v[w >> 1][w & 1]);
-                    } else {
 #pragma unroll
-                        for (int r = 0; r < RA; ++r) *reinterpret_cast<u32x2*>(wr + a_dst + q * A_PLANE + r * (NT / 4) * B3_RS) = h[r];
-                    }
+                    for (int r = 0; r < RA; ++r) *reinterpret_cast<u32x2*>(wr + a_dst + q * A_PLANE + r * (NT / 4) * B3_RS) = h[r];
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -853,19 +776,18 @@ __global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2)
         if (DBG != 4) __syncthreads();
     };
 
-    // start of the run: k-tile 0 of the first tile to LDS, activations of k-tiles 1 .. 3 to sets 0 .. 2, weights of k-tile 1 to set 0
+    // start of the run: k-tile 0 of the first tile to LDS, activations of k-tiles 1 .. 3 to sets 0 .. 2, the wave's weight fragments
+    // of k-tiles 0 and 1 to sets 0 and 1
     auto prime = [&](const Ctx& c, const unsigned bp, int buf) {
         short* wr = lds + buf * BUF;
         {
             f32x4 xa[RA];
             int xm[RA];
-            u32x4 xb[3];
             load_a(b3_int<MASK>{}, c, 0, xa, xm);
-            if (!DIRW) load_w(bp, 0, xb);
 #pragma unroll
             for (int j = 0; j < RA; ++j) {
                 f32x2 v[2];
-                take_a(b3_int<MASK>{}, xa[j], xm[j], v);
+                b3_take_a<MASK, ELU>(xa[j], xm[j], v);
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
                     u32x2 hh;
@@ -874,17 +796,9 @@ __global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2)
                     *reinterpret_cast<u32x2*>(wr + a_dst + q * A_PLANE + j * (NT / 4) * B3_RS) = hh;
                 }
             }
-            if (!DIRW) {
-#pragma unroll
-                for (int q = 0; q < 3; ++q) *reinterpret_cast<u32x4*>(wr + b_dst + q * W_PLANE) = xb[q];
-            }
         }
-        if (DIRW) {         // k-tiles 0 and 1 of the wave's fragments into sets 0 and 1
-            load_wq(b3_int<0>{}, b3_int<0>{}, bp, 0); load_wq(b3_int<0>{}, b3_int<2>{}, bp, 0); load_wq(b3_int<0>{}, b3_int<1>{}, bp, 0);
-            load_wq(b3_int<1>{}, b3_int<0>{}, bp, 1); load_wq(b3_int<1>{}, b3_int<2>{}, bp, 1); load_wq(b3_int<1>{}, b3_int<1>{}, bp, 1);
-        } else {
-            load_w(bp, 1, rb[0]);
-        }
+        load_wq(b3_int<0>{}, b3_int<0>{}, bp, 0); load_wq(b3_int<0>{}, b3_int<2>{}, bp, 0); load_wq(b3_int<0>{}, b3_int<1>{}, bp, 0);
+        load_wq(b3_int<1>{}, b3_int<0>{}, bp, 1); load_wq(b3_int<1>{}, b3_int<2>{}, bp, 1); load_wq(b3_int<1>{}, b3_int<1>{}, bp, 1);
 #pragma unroll
         for (int g = 1; g < 4; ++g) load_a(b3_int<MASK>{}, c, g, ra[g - 1], rm[g - 1]);
         __syncthreads();
@@ -903,7 +817,7 @@ __global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2)
         const bool has_next = ln < count;
         const int tile_n = first + ln;
         const int m0n = (tile_n / tiles_n) * BM, n0n = (tile_n % tiles_n) * BN;
-        clear();
+        b3_clear(acc);
         // request cursors: activations four k-tiles ahead, weights two; each crosses into the next tile on its own stage (at the end of
         // the run: harmless re-loads of this tile's first k-tiles)
         int kf = 4;
@@ -1070,25 +984,8 @@ __global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2)
             rw[u][j][q] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, wo + j * wo_blk, so, 0);
         }
     };
-    auto take_a = [&](const f32x4 src, const int mask, f32x2 (&v)[2]) {
-        typedef int i32x4 __attribute__((ext_vector_type(4)));
-        f32x4 x = __builtin_bit_cast(f32x4, __builtin_bit_cast(i32x4, src) & mask);
-        if (ELU) {
-            x[0] = rst_elu(x[0]); x[1] = rst_elu(x[1]); x[2] = rst_elu(x[2]); x[3] = rst_elu(x[3]);
-        }
-        v[0] = f32x2{x[0], x[1]};
-        v[1] = f32x2{x[2], x[3]};
-    };
 
     f32x16 acc[TM][TN];
-    auto clear = [&]() {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-    };
 
     // one stage: group k-tile kt of LDS buffer `buf` into the accumulators, once per tap; register set S -- the k-tile after it -- into
     // buffer buf ^ 1; the activation request four k-tiles ahead (context c, k-tile kta) into the set just freed; the weight units two
@@ -1134,7 +1031,7 @@ __global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2)
             }
             if (mm == 0) {
 #pragma unroll
-                for (int r = 0; r < RA; ++r) take_a(ra[S][r], rm[S][r], v[r]);
+                for (int r = 0; r < RA; ++r) b3_take_a<true, ELU>(ra[S][r], rm[S][r], v[r]);
             }
             const int op = (mm >= 1 && (mm - 1) % SP == 0) ? (mm - 1) / SP : -1;
             if (op >= 0 && op < NOPS) {
@@ -1172,7 +1069,7 @@ __global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2)
 #pragma unroll
         for (int j = 0; j < RA; ++j) {
             f32x2 v[2];
-            take_a(xa[j], xm[j], v);
+            b3_take_a<true, ELU>(xa[j], xm[j], v);
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 u32x2 hh;
@@ -1192,7 +1089,7 @@ __global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2)
         const bool has_next = ln < count;
         const int tile_n = first + ln;
         const B3SharedTile ti = b3_shared_tile(tile / tiles_n, R, p.T_out);
-        clear();
+        b3_clear(acc);
         // the activation request cursor crosses into the next tile four k-tiles before the end (at the end of the run: harmless re-loads
         // of this tile's first k-tiles), the weight unit stream on the last stage
         int kf = 4;
@@ -1221,9 +1118,10 @@ __global__ __launch_bounds__(128 * NWN) __attribute__((amdgpu_waves_per_eu(2, 2)
     }
 }
 
-// w fp32 [N][K] -> the three bf16 planes in staging order (rows past N: zeros); one thread per four k of one row
-// DIRW: operand order [32-row block][k-tile][plane][64 lanes][8] instead -- lane (n % 32) + 32 * (k % 16 / 8) of the block holds k % 8 ..
-template <bool DIRW>
+// w fp32 [N][K] -> the three bf16 planes in matrix-instruction operand order [32-row block][k-tile][plane][64 lanes][8] (rows past N:
+// zeros): lane (n % 32) + 32 * (k % 16 / 8) of the block holds k % 8 .., so a wave's fragment load is one contiguous KB that never has
+// to pass through LDS (the layout of the retired form that staged the planes there: see gemm_win_b3_stream_kernel).  One thread per
+// four k of one row.
 __global__ __launch_bounds__(256) void gemm_win_b3_pack_kernel(const float* __restrict__ w, short* __restrict__ w3, int N, int K, long total) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
@@ -1233,25 +1131,16 @@ __global__ __launch_bounds__(256) void gemm_win_b3_pack_kernel(const float* __re
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (n < N) v = *reinterpret_cast<const f32x4*>(w + (long)n * K + k);
     f32x2 v0 = {v[0], v[1]}, v1 = {v[2], v[3]};
-    short* dst = DIRW ? w3 + ((long)(n / 32) * (K / B3_KB) + k / B3_KB) * (3 * 512) + ((n % 32) + 32 * ((k % B3_KB) / 8)) * 8 + k % 8
-                      : w3 + ((long)(n / 128) * (K / B3_KB) + k / B3_KB) * B3_WTILE + b3_slot(n % 128) * B3_KB + k % B3_KB;     // slot g holds row b3_row(g)
+    short* dst = w3 + ((long)(n / 32) * (K / B3_KB) + k / B3_KB) * (3 * 512) + ((n % 32) + 32 * ((k % B3_KB) / 8)) * 8 + k % 8;
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
         u32x2 h;
         h[0] = b3_peel(v0);
         h[1] = b3_peel(v1);
-        *reinterpret_cast<u32x2*>(dst + q * (DIRW ? 512 : 128 * B3_KB)) = h;
+        *reinterpret_cast<u32x2*>(dst + q * 512) = h;
     }
 }
 
-// Which of the two weight layouts / kernel forms the library runs (one answer per process: the pack routine and the GEMM must agree).
-// The tools build reads RST_B3_DIRW for A/B measurements.
-// The shipped library runs the direct form only; the staged form (weights through LDS) is compiled into the tools build for the A/B of
-// DESIGN.md 3.1b (RST_B3_DIRW=0).
-static bool b3_dirw() {
-    static const int v = rst_knob("RST_B3_DIRW", 1);
-    return v != 0;
-}
 // (Round 5 also built the same stream with NO barrier per stage: the split activation planes in a ring of four LDS slots, every
 // condition a barrier enforces checked against per-slot arrival counters in LDS with a full stage of slack.  Parity-green and 5 - 15 %
 // SLOWER on every layer (181 vs 196 TFLOP/s, profiles/r05_b3_ring_vs_barrier.txt): waves that drift apart no longer share the weight
@@ -1352,8 +1241,7 @@ int launch_stream_b3_cfg(const GemmWinParams& p, hipStream_t stream) {
         rst_set_error("gemm_win: too many tiles (%ld)", tiles);
         return RST_ERR_UNSUPPORTED;
     }
-    const bool dirw = b3_dirw();
-    const size_t lds = 2 * 3 * (128 + (dirw ? 0 : BN)) * B3_RS * sizeof(short);       // 73 728 / 110 592 bytes; 36 864 without the weight planes
+    const size_t lds = 2 * 3 * 128 * B3_RS * sizeof(short);       // 36 864 bytes
     static const int per_cu = rst_knob("RST_B3_WGS", NWN == 2 ? 2 : 1);      // tools build only
     const long resident = (long)per_cu * gw_cu_count();
     const unsigned grid = (unsigned)(tiles < resident ? tiles : resident);
@@ -1372,31 +1260,13 @@ int launch_stream_b3_cfg(const GemmWinParams& p, hipStream_t stream) {
     // its spills cost on a shape that never takes an edge path?  (VERDICT r5 #6d; profiles/r06_b3_masked_vs_lean.txt)
     static const int force_mask = rst_knob("RST_B3_FORCE_MASK", 0);
     if (force_mask) lean = false;
-    // (the ablation instances of the SHIPPED form: weight fragments direct; RST_B3_DIRW=0 has no ablation instances)
+    // RST_B3_DBG (tools build): the ablation instances of the kernel -- WRONG RESULTS by construction
     static const int dbg = rst_knob("RST_B3_DBG", 0);
-    if (dirw && dbg == 1) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 1, true, true>>{}); return rst_check_launch("gemm_win_b3"); }
-    if (dirw && dbg == 2) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 2, true, true>>{}); return rst_check_launch("gemm_win_b3"); }
-    if (dirw && dbg == 3) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 3, true, true>>{}); return rst_check_launch("gemm_win_b3"); }
-    if (dirw && dbg == 4) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 4, true, true>>{}); return rst_check_launch("gemm_win_b3"); }
-    if (dirw && dbg == 5) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 5, true, true>>{}); return rst_check_launch("gemm_win_b3"); }
-    static const int bufl = rst_knob("RST_B3_BUF", 1);        // 0: plain global loads (64-bit addresses on the vector unit)
-    if (!bufl && dirw && p.act_in != 1) {
-        if (lean) go(RstKernel<gemm_win_b3_stream_kernel<false, false, NWN, 0, false, true>>{});
-        else go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 0, false, true>>{});
-        return rst_check_launch("gemm_win_b3");
-    }
-#endif
-#ifdef RST_ABLATION
-    if (!dirw) {
-        if (p.act_in == 1) {
-            if (lean) go(RstKernel<gemm_win_b3_stream_kernel<true, false, NWN>>{});
-            else go(RstKernel<gemm_win_b3_stream_kernel<true, true, NWN>>{});
-        } else {
-            if (lean) go(RstKernel<gemm_win_b3_stream_kernel<false, false, NWN>>{});
-            else go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN>>{});
-        }
-        return rst_check_launch("gemm_win_b3");
-    }
+    if (dbg == 1) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 1>>{}); return rst_check_launch("gemm_win_b3"); }
+    if (dbg == 2) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 2>>{}); return rst_check_launch("gemm_win_b3"); }
+    if (dbg == 3) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 3>>{}); return rst_check_launch("gemm_win_b3"); }
+    if (dbg == 4) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 4>>{}); return rst_check_launch("gemm_win_b3"); }
+    if (dbg == 5) { go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 5>>{}); return rst_check_launch("gemm_win_b3"); }
 #endif
     // convolutions of two / three taps: every staged group serves all taps of the tile (tools build: RST_B3_SHARE=0 keeps the form below)
     static const int share = rst_knob("RST_B3_SHARE", 1);
@@ -1406,11 +1276,11 @@ int launch_stream_b3_cfg(const GemmWinParams& p, hipStream_t stream) {
         if (taps == 3) return launch_shared_b3_cfg<NWN, 3>(p, stream);
     }
     if (p.act_in == 1) {
-        if (lean) go(RstKernel<gemm_win_b3_stream_kernel<true, false, NWN, 0, true, true>>{});
-        else go(RstKernel<gemm_win_b3_stream_kernel<true, true, NWN, 0, true, true>>{});
+        if (lean) go(RstKernel<gemm_win_b3_stream_kernel<true, false, NWN>>{});
+        else go(RstKernel<gemm_win_b3_stream_kernel<true, true, NWN>>{});
     } else {
-        if (lean) go(RstKernel<gemm_win_b3_stream_kernel<false, false, NWN, 0, true, true>>{});
-        else go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN, 0, true, true>>{});
+        if (lean) go(RstKernel<gemm_win_b3_stream_kernel<false, false, NWN>>{});
+        else go(RstKernel<gemm_win_b3_stream_kernel<false, true, NWN>>{});
     }
     return rst_check_launch("gemm_win_b3");
 }
@@ -1529,12 +1399,6 @@ int rst_launch_gemm_win_b3_pack(const float* w, unsigned short* w3, int N, int K
     RST_REQUIRE(w && w3 && N > 0 && K > 0 && K % 16 == 0, "gemm_win_b3_pack_weight: bad arguments (K %% 16 == 0 required, N=%d K=%d)", N, K);
     RST_REQUIRE((uintptr_t)w % 16 == 0 && (uintptr_t)w3 % 16 == 0, "gemm_win_b3_pack_weight: pointers must be 16-byte aligned");
     const long total = (long)((N + 255) / 256) * 256 * (K / 4);
-#ifdef RST_ABLATION
-    if (!b3_dirw()) {
-        hipLaunchKernelGGL(gemm_win_b3_pack_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, reinterpret_cast<short*>(w3), N, K, total);
-        return rst_check_launch("gemm_win_b3_pack_weight");
-    }
-#endif
-    hipLaunchKernelGGL(gemm_win_b3_pack_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, reinterpret_cast<short*>(w3), N, K, total);
+    hipLaunchKernelGGL(gemm_win_b3_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, reinterpret_cast<short*>(w3), N, K, total);
     return rst_check_launch("gemm_win_b3_pack_weight");
 }
