@@ -1,6 +1,7 @@
 // extern "C" boundary of librstnet_hip.so -- argument checking and parameter marshalling only.
 #include "../../include/rstnet_hip.h"
 #include "rst_kernels.h"
+#include "persist.h"
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -486,7 +487,7 @@ int rst_depth_decode_frame_rows(const uint16_t* const* in_proj, const uint16_t* 
     }
     p.h_all = h_all; p.tokens = reinterpret_cast<long*>(tokens); p.noise = noise; p.v_limit = v_limit_dev; p.v_limit_stride = v_limit_stride;
     p.gran = static_cast<unsigned long long*>(workspace); p.status = status;
-    p.hist_solo = workspace ? reinterpret_cast<float*>(p.gran + 2 * rst_depth_frame_workspace_granules(B, E, Hd, card)) : nullptr;
+    p.hist_solo = workspace ? reinterpret_cast<float*>(static_cast<char*>(workspace) + df_both_sets_bytes(rst_depth_frame_workspace_granules(B, E, Hd, card))) : nullptr;
     p.B = B; p.E = E; p.H = H; p.D = E / H; p.Hd = Hd; p.card = card; p.dep_q = dep_q; p.L = L; p.ld_h = ld_h; p.tok_stride = tok_stride;
     p.noise_stride = noise_stride; p.top_k = top_k; p.use_sampling = use_sampling; p.context = context; p.ring_cap = ring_cap; p.eps = eps; p.temp = temp;
     return rst_launch_depth_frame(p, (hipStream_t)stream);
@@ -506,7 +507,7 @@ int rst_depth_decode_frame(const uint16_t* const* in_proj, const uint16_t* const
 
 int rst_temporal_frame_workspace_bytes(int E, int Hd, int H) {
     if (H <= 0 || E % H) return -1;
-    return (int)(2 * rst_temporal_frame_workspace_granules(E, Hd, H, E / H) * 8);
+    return (int)df_both_sets_bytes(rst_temporal_frame_workspace_granules(E, Hd, H, E / H));
 }
 
 int rst_temporal_frame_supported(int E, int H, int Hd, int L, int cap, int kv_bf16) {
@@ -529,7 +530,7 @@ int rst_temporal_decode_frame(const uint64_t* dev_tables, const float* x, float*
     return rst_launch_temporal_frame(p, (hipStream_t)stream);
 }
 
-int rst_codec_transformer_workspace_bytes(int rows, int E, int F) { return (int)(rst_codec_tr_workspace_granules(rows, E, F) * 16); }
+int rst_codec_transformer_workspace_bytes(int rows, int E, int F) { return (int)df_both_sets_bytes(rst_codec_tr_workspace_granules(rows, E, F)); }
 
 int rst_codec_transformer_supported(int B, int T, int E, int H, int F, int L, int cap) { return rst_codec_tr_grid(B, T, E, H, F, L, cap); }
 

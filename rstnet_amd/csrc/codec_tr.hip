@@ -426,8 +426,10 @@ extern "C" int rst_debug_codec_tr_stamps(unsigned long long* out, int n) {
 
 namespace {
 
-int ct_cu_count() {
-    return rst_cu_count();       // per device (rst_common.h)
+// R = B * T rows, D = E / H
+size_t ct_lds_bytes(int R, int T, int E, int F, int D, int cap) {
+    const int XW = E > F ? E : F;
+    return ((size_t)DF_HDR_FLOATS + (size_t)R * XW + (size_t)R * E + (size_t)T * 3 * D + 2 * (size_t)R * (cap + 16384 / D) + (size_t)(1024 + 2 * DF_WAVES) * R) * sizeof(float);
 }
 
 }  // namespace
@@ -444,26 +446,15 @@ int rst_codec_tr_grid(int B, int T, int E, int H, int F, int L, int cap) {
         return 0;
     const int D = E / H;
     if (!(D >= 16 && D % 16 == 0 && D <= 256 && (64 % (D / 16)) == 0)) return 0;
-    const int XW = E > F ? E : F;
-    const size_t lds = ((size_t)DF_HDR_FLOATS + (size_t)R * XW + (size_t)R * E + (size_t)T * 3 * D + 2 * (size_t)R * (cap + 16384 / D) + (size_t)(1024 + 2 * DF_WAVES) * R) * sizeof(float);
-    if (lds > 150 * 1024) return 0;
-    int G = df_grid_for_rows(ct_cu_count(), min(3 * E, F));
+    if (ct_lds_bytes(R, T, E, F, D, cap) > DF_LDS_LIMIT) return 0;
+    int G = df_grid_for_rows(rst_cu_count(), min(3 * E, F));
     // tools build only -- RST_CTR_GRID=n (RST_DF_GRID for the depth frame): at most n workgroups (fewer participants per all-to-all hand-off against fewer CUs
     // streaming the weights: the measurement behind DESIGN.md 6)
     static const int gcap = rst_knob("RST_CTR_GRID", 0);
     if (gcap > 0 && G > gcap) G = gcap;
     if (B * H > G) return 0;
-    static signed char fits_dev[RST_MAX_DEVICES];        // per device: 0 = not asked yet, 1 = fits, -1 = does not
-    signed char uncached = 0;
-    signed char& fits = rst_device_cell(fits_dev, 1, uncached);
-    if (fits == 0) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(codec_tr_kernel<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        int nb = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, codec_tr_kernel<4, false>, DF_THREADS, 150 * 1024);
-        (void)hipGetLastError();
-        fits = (e == hipSuccess && nb >= 1) ? 1 : -1;
-    }
-    return fits > 0 ? G : 0;
+    // probe: the four-row instance stands for all row counts, at the limit
+    return df_fits_cu<codec_tr_kernel<4, false>>(DF_THREADS, DF_LDS_LIMIT) ? G : 0;
 }
 
 int rst_launch_codec_tr(const CodecTrParams& p, hipStream_t stream) {
@@ -475,24 +466,12 @@ int rst_launch_codec_tr(const CodecTrParams& p, hipStream_t stream) {
     for (int l = 0; l < p.L; ++l)
         RST_REQUIRE(p.in_proj[l] && p.out_proj[l] && p.lin1[l] && p.lin2[l] && p.n1g[l] && p.n1b[l] && p.n2g[l] && p.n2b[l] && p.kc[l] && p.vc[l],
                     "codec_tr: layer %d pointers", l);
-    const int XW = p.E > p.F ? p.E : p.F;
-    const size_t lds = ((size_t)DF_HDR_FLOATS + (size_t)R * XW + (size_t)R * p.E + (size_t)p.T * 3 * p.D + 2 * (size_t)R * (p.cap + 16384 / p.D) + (size_t)(1024 + 2 * DF_WAVES) * R) * sizeof(float);
-    // both granule sets (persistent launch | repair launch) start at zero in every call
-    if (hipMemsetAsync(p.gran, 0, (size_t)rst_codec_tr_workspace_granules(R, p.E, p.F) * 16, stream) != hipSuccess) {
-        rst_set_error("codec_tr: workspace memset failed");
-        return RST_ERR_LAUNCH;
-    }
-    auto go = [&](auto k, int grid) {
-        constexpr auto kern = decltype(k)::fn;
-        rst_allow_dynamic_lds<kern>(150 * 1024);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(DF_THREADS), lds, stream, p);
-    };
-    // the persistent launch, then its one-workgroup repair launch (a no-op unless a hand-off timed out: persist.h)
+    const size_t lds = ct_lds_bytes(R, p.T, p.E, p.F, p.D, p.cap);
+    const long n = rst_codec_tr_workspace_granules(R, p.E, p.F);
     switch (R) {
-        case 1: go(RstKernel<codec_tr_kernel<1, false>>{}, G); go(RstKernel<codec_tr_kernel<1, true>>{}, 1); break;
-        case 2: go(RstKernel<codec_tr_kernel<2, false>>{}, G); go(RstKernel<codec_tr_kernel<2, true>>{}, 1); break;
-        case 3: go(RstKernel<codec_tr_kernel<3, false>>{}, G); go(RstKernel<codec_tr_kernel<3, true>>{}, 1); break;
-        default: go(RstKernel<codec_tr_kernel<4, false>>{}, G); go(RstKernel<codec_tr_kernel<4, true>>{}, 1); break;
+        case 1: return df_launch_pair<codec_tr_kernel<1, false>, codec_tr_kernel<1, true>>("codec_tr", p, G, DF_THREADS, lds, p.gran, n, stream);
+        case 2: return df_launch_pair<codec_tr_kernel<2, false>, codec_tr_kernel<2, true>>("codec_tr", p, G, DF_THREADS, lds, p.gran, n, stream);
+        case 3: return df_launch_pair<codec_tr_kernel<3, false>, codec_tr_kernel<3, true>>("codec_tr", p, G, DF_THREADS, lds, p.gran, n, stream);
+        default: return df_launch_pair<codec_tr_kernel<4, false>, codec_tr_kernel<4, true>>("codec_tr", p, G, DF_THREADS, lds, p.gran, n, stream);
     }
-    return rst_check_launch("codec_tr");
 }

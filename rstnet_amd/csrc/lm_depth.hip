@@ -397,10 +397,6 @@ extern "C" int rst_debug_depth_frame_stamps(unsigned long long* out, int n) {
 
 namespace {
 
-int df_cu_count() {
-    return rst_cu_count();       // per device (rst_common.h)
-}
-
 size_t df_lds_bytes(const DepthFrameParams& p) {
     const int XW = p.E > p.Hd ? p.E : p.Hd;
     static_assert(sizeof(DfShared) <= DF_HDR_FLOATS * 2 && sizeof(SampleShared<DF_THREADS>) <= DF_HDR_FLOATS * 2, "LDS header too small");
@@ -416,7 +412,7 @@ long rst_depth_frame_workspace_granules(int B, int E, int Hd, int card) { return
 
 // workspace: granules of the persistent launch | granules of the repair launch | KV history of the repair launch (fp32, all heads)
 long rst_depth_frame_workspace_bytes_impl(int B, int E, int Hd, int card) {
-    return 2 * rst_depth_frame_workspace_granules(B, E, Hd, card) * 8 + (long)RST_DEPTH_MAX_L * RST_DEPTH_MAX_Q * B * 2 * E * 4;
+    return (long)df_both_sets_bytes(rst_depth_frame_workspace_granules(B, E, Hd, card)) + (long)RST_DEPTH_MAX_L * RST_DEPTH_MAX_Q * B * 2 * E * 4;
 }
 
 // Workgroups of the persistent launch for a shape, 0 if it is not served: every workgroup must own a row of the in-projection
@@ -427,28 +423,16 @@ int rst_depth_frame_grid(const DepthFrameParams& p) {
           p.card <= 16 * DF_THREADS && p.dep_q >= 1 && p.dep_q <= RST_DEPTH_MAX_Q && p.L >= 1 && p.L <= RST_DEPTH_MAX_L))
         return 0;
     const size_t lds = df_lds_bytes(p);
-    if (lds > 150 * 1024) return 0;
-    const int rows = min(min(3 * p.E, p.Hd), p.card);
-    int G = df_grid_for_rows(df_cu_count(), rows);
+    if (lds > DF_LDS_LIMIT) return 0;
+    int G = df_grid_for_rows(rst_cu_count(), min(min(3 * p.E, p.Hd), p.card));
     static const int cap = rst_knob("RST_DF_GRID", 0);      // tools build only (see codec_tr.hip)
     if (cap > 0 && G > cap) G = cap;
     if (p.H > G) return 0;
-    // residency: all G workgroups must run at once, one per CU -- ask the runtime whether a CU takes a workgroup of this footprint
-    static signed char fits[RST_MAX_DEVICES][2][2];      // [device][B - 1][lds > 64 KB]: 0 = not asked yet, 1 = fits, -1 = does not; the
-                                                         // answer does not change within a footprint class
-    signed char uncached = 0;
-    signed char& f = rst_device_cell(&fits[0][p.B - 1][lds > 64 * 1024], 4, uncached);
-    if (f == 0) {
-        const void* kern = p.B == 1 ? reinterpret_cast<const void*>(depth_frame_kernel<1, false>) : reinterpret_cast<const void*>(depth_frame_kernel<2, false>);
-        (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        int nb = 0;
-        const size_t probe = lds > 64 * 1024 ? 150 * 1024 : 64 * 1024;
-        const hipError_t e = p.B == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, depth_frame_kernel<1, false>, DF_THREADS, probe)
-                                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, depth_frame_kernel<2, false>, DF_THREADS, probe);
-        (void)hipGetLastError();
-        f = (e == hipSuccess && nb >= 1) ? 1 : -1;
-    }
-    return f > 0 ? G : 0;
+    // probe: the instance of this batch size; two footprint classes, up to 64 KiB probed with 64 KiB and beyond it with the limit
+    const bool big = lds > 64 * 1024;
+    const size_t probe = big ? DF_LDS_LIMIT : 64 * 1024;
+    const bool fits = p.B == 1 ? df_fits_cu<depth_frame_kernel<1, false>, 2>(DF_THREADS, probe, big) : df_fits_cu<depth_frame_kernel<2, false>, 2>(DF_THREADS, probe, big);
+    return fits ? G : 0;
 }
 
 int rst_launch_depth_frame(const DepthFrameParams& p, hipStream_t stream) {
@@ -464,18 +448,7 @@ int rst_launch_depth_frame(const DepthFrameParams& p, hipStream_t stream) {
     }
     for (int k = 0; k < p.dep_q; ++k) RST_REQUIRE(p.heads[k] && p.emb[k] && p.emb_rows[k] >= 1, "depth_frame: head / embedding of step %d", k);
     const size_t lds = df_lds_bytes(p);
-    // every polled word (both granule sets) starts at zero in EVERY launch (a memset node when captured): epochs count from 1
-    if (hipMemsetAsync(p.gran, 0, (size_t)rst_depth_frame_workspace_granules(p.B, p.E, p.Hd, p.card) * 16, stream) != hipSuccess) {
-        rst_set_error("depth_frame: workspace memset failed");
-        return RST_ERR_LAUNCH;
-    }
-    auto go = [&](auto k, int grid) {
-        constexpr auto kern = decltype(k)::fn;
-        rst_allow_dynamic_lds<kern>(150 * 1024);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(DF_THREADS), lds, stream, p);
-    };
-    // the persistent launch, then its one-workgroup repair launch (a no-op unless a hand-off timed out: persist.h)
-    if (p.B == 1) { go(RstKernel<depth_frame_kernel<1, false>>{}, G); go(RstKernel<depth_frame_kernel<1, true>>{}, 1); }
-    else { go(RstKernel<depth_frame_kernel<2, false>>{}, G); go(RstKernel<depth_frame_kernel<2, true>>{}, 1); }
-    return rst_check_launch("depth_frame");
+    const long n = rst_depth_frame_workspace_granules(p.B, p.E, p.Hd, p.card);
+    if (p.B == 1) return df_launch_pair<depth_frame_kernel<1, false>, depth_frame_kernel<1, true>>("depth_frame", p, G, DF_THREADS, lds, p.gran, n, stream);
+    return df_launch_pair<depth_frame_kernel<2, false>, depth_frame_kernel<2, true>>("depth_frame", p, G, DF_THREADS, lds, p.gran, n, stream);
 }

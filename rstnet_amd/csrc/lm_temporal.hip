@@ -852,8 +852,6 @@ extern "C" int rst_debug_temporal_frame_wstamps(unsigned long long* out) {
 namespace {
 #endif
 
-int tf_cu_count() { return rst_cu_count(); }
-
 size_t tf_lds_bytes(const TemporalFrameParams& p) {
     const int EP = (p.E + 4095) & ~4095, HdP = (p.Hd + 4095) & ~4095;
     static_assert(sizeof(TfShared) <= TF_HDR * 4, "LDS header too small");
@@ -871,60 +869,37 @@ int rst_temporal_frame_grid(const TemporalFrameParams& p) {
           p.L >= 1 && p.L <= RST_TEMPORAL_MAX_L && p.cap >= 1))
         return 0;
     const size_t lds = tf_lds_bytes(p);
-    if (lds > 150 * 1024) return 0;
+    if (lds > DF_LDS_LIMIT) return 0;
     // every weight wave owns a row of the narrowest all-to-all op (E rows); every head needs a workgroup
-    int G = tf_cu_count();
+    int G = rst_cu_count();
     if (G > p.E / TF_WW) G = p.E / TF_WW;
     static const int cap = rst_knob("RST_TF_GRID", 0);      // tools build only
     if (cap > 0 && G > cap) G = cap;
     if (G < 1 || p.H > G) return 0;
-    static signed char fits[RST_MAX_DEVICES][2];            // [device][kv_bf16]
-    signed char uncached = 0;
-    signed char& f = rst_device_cell(&fits[0][p.kv_bf16 ? 1 : 0], 2, uncached);
-    if (f == 0) {
-        const void* kern = p.kv_bf16 ? reinterpret_cast<const void*>(temporal_frame_kernel<true, 128, false>)
-                                     : reinterpret_cast<const void*>(temporal_frame_kernel<false, 128, false>);
-        (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        int nb = 0;
-        const hipError_t e = p.kv_bf16 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, temporal_frame_kernel<true, 128, false>, TF_THREADS, 150 * 1024)
-                                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, temporal_frame_kernel<false, 128, false>, TF_THREADS, 150 * 1024);
-        (void)hipGetLastError();
-        f = (e == hipSuccess && nb >= 1) ? 1 : -1;
-    }
-    return f > 0 ? G : 0;
+    // probe: the head-dim-128 instance of the ring's precision stands for both head dims, at the limit
+    const bool fits = p.kv_bf16 ? df_fits_cu<temporal_frame_kernel<true, 128, false>>(TF_THREADS, DF_LDS_LIMIT)
+                                : df_fits_cu<temporal_frame_kernel<false, 128, false>>(TF_THREADS, DF_LDS_LIMIT);
+    return fits ? G : 0;
 }
-
-namespace {
-template <auto KERN>
-void tf_launch(const TemporalFrameParams& pk, int grid, size_t lds, hipStream_t stream) {
-    rst_allow_dynamic_lds<KERN>(150 * 1024);
-    hipLaunchKernelGGL(KERN, dim3(grid), dim3(TF_THREADS), lds, stream, pk);
-}
-}  // namespace
 
 int rst_launch_temporal_frame(const TemporalFrameParams& p, hipStream_t stream) {
     RST_REQUIRE(p.tab && p.x && p.y && p.pos_dev && p.gran && p.status, "temporal_frame: null buffers");
     const int G = rst_temporal_frame_grid(p);
     RST_REQUIRE(G > 0, "temporal_frame: unsupported shape (E=%d Hd=%d H=%d D=%d L=%d cap=%d) or no resident grid for it", p.E, p.Hd, p.H, p.D, p.L, p.cap);
-    const size_t lds = tf_lds_bytes(p);
     TemporalFrameParams pk = p;
     static const int thin = rst_knob("RST_TF_THIN", 0);      // tools build only (A/B)
     pk.thin = thin;
-    if (hipMemsetAsync(p.gran, 0, (size_t)rst_temporal_frame_workspace_granules(p.E, p.Hd, p.H, p.D) * 16, stream) != hipSuccess) {
-        rst_set_error("temporal_frame: workspace memset failed");
-        return RST_ERR_LAUNCH;
-    }
-    static const int no_repair = rst_knob("RST_TF_NO_REPAIR", 0);      // tools build only
-    auto go = [&](auto KV16, auto D) {      // the persistent launch and, behind it in the stream, its one-workgroup repair launch
-        tf_launch<temporal_frame_kernel<decltype(KV16)::value, decltype(D)::value, false>>(pk, G, lds, stream);
-        if (!no_repair) tf_launch<temporal_frame_kernel<decltype(KV16)::value, decltype(D)::value, true>>(pk, 1, lds, stream);
+    static const int no_repair = rst_knob("RST_TF_NO_REPAIR", 0);      // tools build only: the persistent launch without its repair launch
+    auto go = [&](auto KV16, auto D) {
+        constexpr bool kv16 = decltype(KV16)::value;
+        constexpr int d = decltype(D)::value;
+        return df_launch_pair<temporal_frame_kernel<kv16, d, false>, temporal_frame_kernel<kv16, d, true>>(
+            "temporal_frame", pk, G, TF_THREADS, tf_lds_bytes(p), p.gran, rst_temporal_frame_workspace_granules(p.E, p.Hd, p.H, p.D), stream, !no_repair);
     };
-    const int key = (p.kv_bf16 ? 2 : 0) + (p.D == 128 ? 1 : 0);
-    switch (key) {
-        case 3: go(std::true_type{}, std::integral_constant<int, 128>{}); break;
-        case 2: go(std::true_type{}, std::integral_constant<int, 64>{}); break;
-        case 1: go(std::false_type{}, std::integral_constant<int, 128>{}); break;
-        default: go(std::false_type{}, std::integral_constant<int, 64>{}); break;
+    switch ((p.kv_bf16 ? 2 : 0) + (p.D == 128 ? 1 : 0)) {
+        case 3: return go(std::true_type{}, std::integral_constant<int, 128>{});
+        case 2: return go(std::true_type{}, std::integral_constant<int, 64>{});
+        case 1: return go(std::false_type{}, std::integral_constant<int, 128>{});
+        default: return go(std::false_type{}, std::integral_constant<int, 64>{});
     }
-    return rst_check_launch("temporal_frame");
 }

@@ -1,4 +1,5 @@
-// In-launch all-to-all hand-offs of the persistent frame kernels (lm_depth.hip, codec_tr.hip): an op's output vector lives in a
+// In-launch all-to-all hand-offs of the persistent frame kernels (lm_depth.hip, lm_temporal.hip, codec_tr.hip) and, below the device
+// helpers, the host half of their launches: residency probe and launch pair.  An op's output vector lives in a
 // global array of 8-byte {epoch tag, fp32 value} granules, each written by ONE relaxed agent-scope (sc1, write-through) store;
 // a consuming workgroup sweeps the granules it needs with relaxed agent-scope loads until every tag equals the op's epoch and
 // stages the values in LDS (cdna_hip_programming.md Guideline 16, form R2: the data is the flag -- no fence, no dispatch-order or
@@ -89,10 +90,54 @@ __device__ __forceinline__ void df_solo_done(unsigned* status) {
     }
 }
 
+// ---- host half: the launch contract of the three persistent kernels (lm_depth.hip, lm_temporal.hip, codec_tr.hip) ---------------
+// A shape is served when its LDS footprint is within DF_LDS_LIMIT, its grid (at most one workgroup per CU, every workgroup owning rows
+// of every all-to-all op) has a workgroup per head, and one workgroup of that footprint fits a CU (df_fits_cu).  A call enqueues
+// three stream operations (df_launch_pair): the memset of BOTH granule sets, the grid, the one-workgroup repair launch.
+constexpr size_t DF_LDS_LIMIT = 150 * 1024;    // dynamic LDS the kernels opt in to: the gate of every shape, the probe, the launch
+
+// The workspace holds two sets of `n` granules: the persistent launch's, then the repair launch's (the kernels: gran + SOLO * n).
+inline size_t df_both_sets_bytes(long n) { return 2 * (size_t)n * sizeof(u64); }
+
 // Largest grid (<= `cus`) in which every workgroup (4 waves, row r -> wave r mod 4G) owns a row of an op with `min_rows` rows.
 inline int df_grid_for_rows(int cus, int min_rows) {
     const int g = (min_rows + DF_WAVES - 1) / DF_WAVES;
     return g < cus ? (g < 1 ? 1 : g) : cus;
+}
+
+// Residency: all workgroups of a persistent launch must run at once, one per CU -- whether a CU of the current device takes one workgroup
+// of KERN with `probe_bytes` of dynamic LDS.  Asked once per (device, kernel instance, footprint class `cls` < CLASSES: the answer does
+// not change within a class); a device ordinal the table does not cover is asked every time (rst_device_cell).
+template <auto KERN, int CLASSES = 1>
+bool df_fits_cu(int threads, size_t probe_bytes, int cls = 0) {
+    static signed char fits[RST_MAX_DEVICES][CLASSES];      // 0 = not asked yet, 1 = fits, -1 = does not
+    signed char uncached = 0;
+    signed char& f = rst_device_cell(&fits[0][cls], CLASSES, uncached);
+    if (f == 0) {
+        rst_allow_dynamic_lds<KERN>((int)DF_LDS_LIMIT);
+        int nb = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KERN, threads, probe_bytes);
+        (void)hipGetLastError();
+        f = (e == hipSuccess && nb >= 1) ? 1 : -1;
+    }
+    return f > 0;
+}
+
+// One persistent call: every polled word of both granule sets starts at zero in EVERY launch (a memset node when captured: epochs count
+// from 1), then PERSISTENT on `grid` workgroups and, behind it in the stream, SOLO as one workgroup (a no-op unless a hand-off timed out).
+template <auto PERSISTENT, auto SOLO, typename P>
+int df_launch_pair(const char* what, const P& p, int grid, int threads, size_t lds, u64* gran, long granules, hipStream_t stream, bool repair = true) {
+    if (hipMemsetAsync(gran, 0, df_both_sets_bytes(granules), stream) != hipSuccess) {
+        rst_set_error("%s: workspace memset failed", what);
+        return RST_ERR_LAUNCH;
+    }
+    rst_allow_dynamic_lds<PERSISTENT>((int)DF_LDS_LIMIT);
+    hipLaunchKernelGGL(PERSISTENT, dim3(grid), dim3(threads), lds, stream, p);
+    if (repair) {
+        rst_allow_dynamic_lds<SOLO>((int)DF_LDS_LIMIT);
+        hipLaunchKernelGGL(SOLO, dim3(1), dim3(threads), lds, stream, p);
+    }
+    return rst_check_launch(what);
 }
 
 }  // namespace

@@ -20,6 +20,8 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from .persistent import (_persist_off, _persist_pending, _persist_status, depth_frame_enabled, new_persistent_status,  # noqa: F401
+                         persistent_epoch, persistent_poll, persistent_rearm, persistent_repairs, persistent_retired)
 from .slots import record_stride       # bytes between the records of a packed frame buffer (the layouts live in slots.py)
 
 ACT_NONE, ACT_ELU, ACT_GELU = 0, 1, 1   # act_in: 1 = ELU ; act_out: 1 = GELU
@@ -1898,146 +1900,44 @@ def lm_ring_commit(cache: torch.Tensor, tokens: torch.Tensor, delays: torch.Tens
     return out
 
 
-
-
 # ----------------------------------------------------------------------------------------------------------------------
-# The depth phase of a frame as ONE persistent launch (rst_depth_decode_frame)
+# The three persistent frame launches (csrc/persist.h): the depth phase, the batch-1 temporal transformer, a Mimi transformer step
 # ----------------------------------------------------------------------------------------------------------------------
-DEPTH_FRAME_MAX_L, DEPTH_FRAME_MAX_Q = 8, 8
-_depth_ws: dict = {}
-
-# ---- health of the persistent launches (csrc/persist.h).  A launch whose workgroups are not all resident (device shared with other
-# work) times out and is repaired in-stream by its one-workgroup twin: outputs stay right, but a repaired frame costs >= 0.1 s.  Every
-# launcher's status words are registered here; `persistent_poll` reads their repair counters WITHOUT synchronising (async copy into
-# pinned memory, evaluated on the next poll) and retires the persistent path on a device that had to repair -- sessions then
-# re-capture their frame graphs on the launch-per-op chain (`persistent_epoch` changes).
-PERSISTENT_MAX_REPAIRS = 0          # repairs tolerated per device before the launch-per-op chain takes over
-_persist_status: dict = {}          # device -> list of weakrefs of status tensors (int32 [4])
-_persist_off: dict = {}             # device -> reason string
-_persist_epoch: dict = {}           # device -> int, bumped when the device's persistent path is retired
-_persist_pending: dict = {}         # device -> (event, [pinned int32 [4] copies])
-_persist_seen: dict = {}            # device -> repairs counted by the last completed poll
-
-
-def new_persistent_status(device) -> torch.Tensor:
-    """The 4 status words of a persistent launcher (time-out codes in flight | frames repaired | OR of repaired codes | reserved),
-    registered for `persistent_poll`."""
-    import weakref
-    device = torch.device(device)
-    st = torch.zeros(4, device=device, dtype=torch.int32)
-    _persist_status.setdefault(device, []).append(weakref.ref(st))
-    return st
-
-
-def persistent_epoch(device) -> int:
-    return _persist_epoch.get(torch.device(device), 0)
-
-
-def persistent_repairs(device, synchronize: bool = True) -> int:
-    """Frames / codec steps of `device` that the repair launches had to recompute so far.  ``synchronize=True`` reads the device words
-    now (a device-to-host copy: waits for the stream); ``False`` returns the count seen by the last completed `persistent_poll` copy
-    without touching the device (0 before the first one)."""
-    device = torch.device(device)
-    if not synchronize:
-        pend = _persist_pending.get(device)
-        if pend is not None and pend[0].query():
-            _persist_seen[device] = int(sum(int(c[1]) for c in pend[1]))
-        return _persist_seen.get(device, 0)
-    alive = [r() for r in _persist_status.get(device, [])]
-    n = int(sum(int(t[1].item()) for t in alive if t is not None))
-    _persist_seen[device] = n
-    return n
-
-
-def persistent_rearm(device) -> None:
-    """Gives `device` its persistent frame launches back after `persistent_poll` retired them (e.g. the process that shared the GPU
-    has gone): clears the repair counters, bumps the epoch so that sessions re-capture their graphs.  The in-stream repair launch
-    keeps every frame correct either way; this is about speed only.
-
-    Call it with NO frame in flight on `device`: the status words are shared with captured graphs and per-session streams, and a
-    repair launch's atomics racing with the reset would lose or mis-count a repair.  The whole device is therefore drained first
-    (every stream, not only the current one), and the counters are zeroed on a quiet device."""
-    device = torch.device(device)
-    if device.type == "cuda":
-        torch.cuda.synchronize(device)
-    for r in _persist_status.get(device, []):
-        t = r()
-        if t is not None:
-            t.zero_()
-    _persist_pending.pop(device, None)
-    _persist_seen.pop(device, None)
-    if _persist_off.pop(device, None) is not None:
-        _persist_epoch[device] = _persist_epoch.get(device, 0) + 1
-
-
-def _retire_persistent(device, reason: str) -> None:
-    import warnings
-    if device not in _persist_off:
-        _persist_off[device] = reason
-        _persist_epoch[device] = _persist_epoch.get(device, 0) + 1
-        warnings.warn(f"rstnet_amd: persistent frame launches retired on {device}: {reason}; the launch-per-op chain takes over "
-                      "(outputs were repaired in-stream, nothing wrong left the device)", RuntimeWarning)
-
-
-def persistent_poll(device, synchronize: bool = False) -> None:
-    """Looks at the repair counters of `device` (the copy requested by the PREVIOUS call unless `synchronize`), retires the persistent
-    path beyond PERSISTENT_MAX_REPAIRS repairs and requests the next copy.  Cheap enough for once every few dozen frames; never
-    called inside a graph capture."""
-    device = torch.device(device)
-    if device.type != "cuda" or device in _persist_off or torch.cuda.is_current_stream_capturing():
-        return
-    if synchronize:
-        n = persistent_repairs(device)
-        if n > PERSISTENT_MAX_REPAIRS:
-            _retire_persistent(device, f"{n} frame(s) needed the one-workgroup repair launch (hand-offs timed out: not all workgroups were resident)")
-        return
-    pend = _persist_pending.get(device)
-    if pend is not None:
-        ev, copies = pend
-        if not ev.query():
-            return
-        n = int(sum(int(c[1]) for c in copies))
-        _persist_seen[device] = n
-        _persist_pending.pop(device, None)
-        if n > PERSISTENT_MAX_REPAIRS:
-            _retire_persistent(device, f"{n} frame(s) needed the one-workgroup repair launch (hand-offs timed out: not all workgroups were resident)")
-            return
-    refs = _persist_status.get(device, [])
-    alive = [t for t in (r() for r in refs) if t is not None]
-    _persist_status[device] = [r for r in refs if r() is not None]
-    if not alive:
-        return
-    with torch.cuda.device(device):
-        copies = [torch.empty(4, dtype=torch.int32).pin_memory() for _ in alive]
-        for c, t in zip(copies, alive):
-            c.copy_(t, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-    _persist_pending[device] = (ev, copies)
-
-
-def depth_frame_enabled(device=None) -> bool:
-    """RST_DEPTH_FRAME=0 keeps the launch-per-op depth phase / codec transformer layers (A/B measurements, or a device known to be
-    shared with other work); a device whose persistent launches needed repairs is retired automatically (`persistent_poll`)."""
-    import os
-    if os.environ.get("RST_DEPTH_FRAME", "1") in ("0", ""):
-        return False
-    return device is None or torch.device(device) not in _persist_off
-
-
-@functools.lru_cache(maxsize=256)
-def _depth_frame_grid(dev: int, B: int, E: int, H: int, Hd: int, card: int, dep_q: int, L: int, top_k: int) -> int:
-    # keyed by the device ordinal: the answer embeds that device's CU count and its occupancy query
-    with torch.cuda.device(dev):
-        return int(_lib.lib().rst_depth_frame_supported(B, E, H, Hd, card, dep_q, L, top_k))
-
-
 def _device_index(device=None) -> int:
     """Ordinal of ``device`` (a torch device / int / None = the current device): the key of every per-device cache."""
     if device is None:
         return torch.cuda.current_device()
     d = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
     return d.index if d.index is not None else torch.cuda.current_device()
+
+
+@functools.lru_cache(maxsize=512)
+def _frame_grid(entry: str, dev: int, *shape: int) -> int:
+    """Workgroups the library's ``entry`` (an ``rst_*_supported``) grants ``shape`` on device ``dev``, 0 = not served.  Keyed by the
+    device ordinal and asked with that device current: the answer embeds its CU count and its occupancy query."""
+    with torch.cuda.device(dev):
+        return int(getattr(_lib.lib(), entry)(*shape))
+
+
+_frame_ws: dict = {"depth_frame": {}, "temporal_frame": {}, "codec_transformer": {}}          # kind -> `_scratch` cache
+_depth_ws, _temporal_ws = _frame_ws["depth_frame"], _frame_ws["temporal_frame"]          # read by the test helpers of earlier revisions
+
+
+def _frame_workspace(kind: str, device, shape: tuple) -> torch.Tensor:
+    """The granule workspace (int64 words, ``rst_<kind>_workspace_bytes(*shape)``) of a persistent launcher, through `_scratch`."""
+    return _scratch(_frame_ws[kind], device, shape,
+                    lambda: torch.zeros(int(getattr(_lib.lib(), f"rst_{kind}_workspace_bytes")(*shape)) // 8, device=device, dtype=torch.int64))
+
+
+def frame_workspace(kind: str, shape: tuple, device=None) -> Optional[torch.Tensor]:
+    """The workspace an EAGER launch of ``kind`` ("depth_frame": ``(B, E, Hd, card)``, "temporal_frame": ``(E, Hd, H)``,
+    "codec_transformer": ``(rows, E, F)``) used for ``shape`` on ``device``, None before the first one (tests read the hand-offs)."""
+    dev = _device_index(device)
+    return next((ws for k, ws in _frame_ws[kind].items() if k[0].index == dev and k[1] != "graph" and k[2:] == tuple(shape)), None)
+
+
+# ---- the depth phase of a frame (rst_depth_decode_frame) ---------------------------------------------------------------------------------
+DEPTH_FRAME_MAX_L, DEPTH_FRAME_MAX_Q = 8, 8
 
 
 def depth_frame_supported(B: int, E: int, H: int, Hd: int, card: int, dep_q: int, L: int, top_k: int, device=None) -> bool:
@@ -2047,7 +1947,7 @@ def depth_frame_supported(B: int, E: int, H: int, Hd: int, card: int, dep_q: int
     instead of catching an error."""
     if not (1 <= B <= 2 and 1 <= dep_q <= DEPTH_FRAME_MAX_Q and 1 <= L <= DEPTH_FRAME_MAX_L and H >= 1 and E % max(H, 1) == 0):
         return False
-    return _depth_frame_grid(_device_index(device), B, E, H, Hd, card, dep_q, L, top_k if 0 < top_k < card else card) > 0
+    return _frame_grid("rst_depth_frame_supported", _device_index(device), B, E, H, Hd, card, dep_q, L, top_k if 0 < top_k < card else card) > 0
 
 
 @_on_tensor_device
@@ -2077,9 +1977,7 @@ def depth_decode_frame(tables, h_all: torch.Tensor, tokens: torch.Tensor, noise:
         if noise is None or not noise.is_cuda or noise.dtype != torch.float32 or noise.dim() != 2 or noise.stride(1) != 1 or \
                 noise.shape[0] != B or noise.shape[1] < t.dep_q * top_k:
             raise ValueError("rstnet_amd.ops: `noise` must be float32 CUDA/HIP [B, >= dep_q * top_k] with unit column stride")
-    ws = _scratch(_depth_ws, h_all.device, (B, t.E, t.Hd, t.card),
-                  lambda: torch.zeros(int(_lib.lib().rst_depth_frame_workspace_bytes(B, t.E, t.Hd, t.card)) // 8, device=h_all.device,
-                                      dtype=torch.int64))
+    ws = _frame_workspace("depth_frame", h_all.device, (B, t.E, t.Hd, t.card))
     n_w = t.dep_q * (t.L * (3 * t.E * t.E + t.E * t.E + 3 * t.Hd * t.E) + t.card * t.E)      # weight elements read once per frame
     with _profiled("depth_frame", 2.0 * B * n_w, 2 * n_w + 4 * h_all.numel(), (B, t.dep_q, t.L)):
         _lib.check(fn(
@@ -2090,9 +1988,7 @@ def depth_decode_frame(tables, h_all: torch.Tensor, tokens: torch.Tensor, noise:
             _ctx(context), int(ring_cap) if ring_cap else t.dep_q, _stream()))
 
 
-# ----------------------------------------------------------------------------------------------------------------------
-# The temporal transformer of a batch-1 LM step as ONE persistent launch (rst_temporal_decode_frame)
-# ----------------------------------------------------------------------------------------------------------------------
+# ---- the temporal transformer of a batch-1 LM step (rst_temporal_decode_frame) ----------------------------------------------------------
 # "auto": the persistent launch once the temporal rings hold at least TEMPORAL_FRAME_AUTO_POS steps.  Measured per frame (lm_b1, launch per
 # op vs persistent, profiles/r06_temporal_persistent.txt): ring offset 0: 3.78 / 3.78 ms, 500: 3.90 / 3.95, 1000: 4.02 / 3.99, 2000: 4.08 /
 # 4.08, 3000 (full): 4.20 / 4.14 -- the ring rows are part of its weight stream, so it gains where they are many.  True / False: always /
@@ -2109,13 +2005,6 @@ def temporal_frame_wanted(host_pos: int) -> bool:
 
 
 TEMPORAL_FRAME_MAX_L = 40
-_temporal_ws: dict = {}
-
-
-@functools.lru_cache(maxsize=64)
-def _temporal_frame_grid(dev: int, E: int, H: int, Hd: int, L: int, cap: int, kv16: int) -> int:
-    with torch.cuda.device(dev):
-        return int(_lib.lib().rst_temporal_frame_supported(E, H, Hd, L, cap, kv16))
 
 
 def temporal_frame_supported(B: int, E: int, H: int, Hd: int, L: int, cap: int, kv_bf16: bool, device=None) -> bool:
@@ -2123,7 +2012,7 @@ def temporal_frame_supported(B: int, E: int, H: int, Hd: int, L: int, cap: int, 
     LDS footprint, a workgroup per head, the occupancy query) -- on a device whose persistent launches have not been retired."""
     if not (TEMPORAL_FRAME and depth_frame_enabled(device) and B == 1 and 1 <= L <= TEMPORAL_FRAME_MAX_L and H >= 1 and E % max(H, 1) == 0):
         return False
-    return _temporal_frame_grid(_device_index(device), E, H, Hd, L, cap, int(kv_bf16)) > 0
+    return _frame_grid("rst_temporal_frame_supported", _device_index(device), E, H, Hd, L, cap, int(kv_bf16)) > 0
 
 
 class TemporalFrameTables:
@@ -2175,8 +2064,7 @@ def temporal_decode_frame(tables: "TemporalFrameTables", x: torch.Tensor, pos_de
     t = tables
     assert x.shape == (1, t.E)
     y = torch.empty_like(x)
-    ws = _scratch(_temporal_ws, x.device, (t.E, t.Hd, t.H),
-                  lambda: torch.zeros(int(_lib.lib().rst_temporal_frame_workspace_bytes(t.E, t.Hd, t.H)) // 8, device=x.device, dtype=torch.int64))
+    ws = _frame_workspace("temporal_frame", x.device, (t.E, t.Hd, t.H))
     n_w = t.L * (4 * t.E * t.E + 3 * t.Hd * t.E)
     with _profiled("temporal_frame", 2.0 * n_w, 2 * n_w, (1, t.L, t.E)):
         _lib.check(_lib.lib().rst_temporal_decode_frame(
@@ -2185,17 +2073,8 @@ def temporal_decode_frame(tables: "TemporalFrameTables", x: torch.Tensor, pos_de
     return y
 
 
-# ----------------------------------------------------------------------------------------------------------------------
-# One streaming step of a Mimi transformer as ONE persistent launch (rst_codec_transformer_frame)
-# ----------------------------------------------------------------------------------------------------------------------
-_ctr_ws: dict = {}
+# ---- one streaming step of a Mimi transformer (rst_codec_transformer_frame) -------------------------------------------------------------
 _ctr_status: dict = {}
-
-
-@functools.lru_cache(maxsize=256)
-def _codec_tr_grid(dev: int, B: int, T: int, E: int, H: int, F: int, L: int, cap: int) -> int:
-    with torch.cuda.device(dev):
-        return int(_lib.lib().rst_codec_transformer_supported(B, T, E, H, F, L, cap))
 
 
 def codec_transformer_frame_supported(B: int, T: int, E: int, H: int, F: int, L: int, cap: int, device=None) -> bool:
@@ -2204,7 +2083,7 @@ def codec_transformer_frame_supported(B: int, T: int, E: int, H: int, F: int, L:
     grid with rows for every workgroup and a workgroup per (stream, head), the occupancy query)."""
     if not (depth_frame_enabled(device) and B >= 1 and 1 <= T <= 4 and B * T <= 4 and H >= 1 and E % max(H, 1) == 0):
         return False
-    return _codec_tr_grid(_device_index(device), B, T, E, H, F, L, cap) > 0
+    return _frame_grid("rst_codec_transformer_supported", _device_index(device), B, T, E, H, F, L, cap) > 0
 
 
 def codec_transformer_status(device) -> torch.Tensor:
@@ -2239,8 +2118,7 @@ def codec_transformer_frame(x: torch.Tensor, layers: Sequence[dict], pos_dev: to
         return (C.c_void_p * L)(*[_ptr(ly.get(name)) for ly in layers])
     has_scale = layers[0].get("scale1") is not None
     y = torch.empty_like(x)
-    ws = _scratch(_ctr_ws, x.device, (B * T, E, F_),
-                  lambda: torch.zeros(int(_lib.lib().rst_codec_transformer_workspace_bytes(B * T, E, F_)) // 8, device=x.device, dtype=torch.int64))
+    ws = _frame_workspace("codec_transformer", x.device, (B * T, E, F_))
     D = E // H
     _lib.check(_lib.lib().rst_codec_transformer_frame(
         table("in_proj"), table("out_proj"), table("linear1"), table("linear2"), table("norm1_w"), table("norm1_b"), table("norm2_w"),

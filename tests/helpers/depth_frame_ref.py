@@ -394,7 +394,7 @@ def emulate_sampler(logits, noise, limits, case, defect=None):
 # ---- the hand-off workspace ---------------------------------------------------------------------------------------------------------------
 def workspace(ops, B, E, Hd, card):
     """The eager workspace ops.depth_decode_frame launched a shape on (int64 granules)."""
-    return [v for k, v in ops._depth_ws.items() if k[-4:] == (B, E, Hd, card) and k[1] != "graph"][0]
+    return ops.frame_workspace("depth_frame", (B, E, Hd, card))
 
 
 def read_handoff(ws, case, B, solo=False):

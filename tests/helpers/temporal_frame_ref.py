@@ -459,7 +459,7 @@ def accept(got, ref64, tol, case):
 # ---- the hand-off workspace ---------------------------------------------------------------------------------------------------------------
 def workspace(ops, case):
     """The eager workspace ops.temporal_decode_frame launched a shape on (int64 granules)."""
-    return [v for k, v in ops._temporal_ws.items() if k[-3:] == (case.E, case.Hd, case.H) and k[1] != "graph"][0]
+    return ops.frame_workspace("temporal_frame", (case.E, case.Hd, case.H))
 
 
 def read_handoff(ws, case, solo=False):

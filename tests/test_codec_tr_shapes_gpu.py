@@ -31,13 +31,16 @@ def _state(E, H, F, L, seed, layer_scale):
     return sd
 
 
-@pytest.mark.parametrize("E,H,F,L,cap,B,chunks", [
+STREAM_SHAPES = [          # E, H, F, L, cap, B, chunks (tests/test_persistent_host_gpu.py asks the launcher's grid for them too)
     (128, 8, 512, 3, 20, 2, (2, 1, 2, 2, 1) * 6),        # D = 16: lane groups of 4, 64 slot classes
     (256, 8, 512, 2, 37, 1, (3, 4, 1, 2) * 5),           # D = 32; 3 and 4 positions per step
     (512, 4, 1024, 2, 250, 1, (4,) * 66),                # D = 128: two batches of slots once the ring fills (264 positions: past the wrap)
     (512, 2, 512, 2, 150, 2, (2,) * 80),                 # D = 256: 64 slots per batch -> three batches, a full wave per slot
     (512, 8, 2048, 8, 24, 4, (1,) * 30),                 # Mimi's layer shape, four streams of one position, a short ring
-])
+]
+
+
+@pytest.mark.parametrize("E,H,F,L,cap,B,chunks", STREAM_SHAPES)
 def test_frame_vs_oracle_stream(E, H, F, L, cap, B, chunks):
     D = E // H
     assert ops.codec_transformer_frame_supported(B, max(chunks), E, H, F, L, cap, device=DEV)

@@ -23,14 +23,7 @@ DEV = "cuda:0"
 @pytest.fixture
 def clean_health():
     yield
-    torch.cuda.synchronize()
-    ops._persist_off.clear()
-    ops._persist_pending.clear()
-    for refs in ops._persist_status.values():          # the repair counters of this test must not retire the path for later tests
-        for r in refs:
-            t = r()
-            if t is not None:
-                t.zero_()
+    ops.persistent_rearm(DEV)          # the repair counters of this test must not retire the path for later tests
 
 
 _BUILT = {}

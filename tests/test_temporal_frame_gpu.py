@@ -14,14 +14,7 @@ def clean_health():
     """The repair counters these tests provoke must not retire the device's persistent launches for the tests that follow."""
     yield
     from rstnet_amd import ops
-    torch.cuda.synchronize()
-    ops._persist_off.clear()
-    ops._persist_pending.clear()
-    for refs in ops._persist_status.values():
-        for r in refs:
-            t = r()
-            if t is not None:
-                t.zero_()
+    ops.persistent_rearm("cuda:0")
 
 
 def _transformer(layers, kvd):

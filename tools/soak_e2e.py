@@ -61,8 +61,8 @@ def main():
         pos = int(model.transformer._streaming_state.pos)
     print(f"{args.frames} frames, {B} stream(s): temporal ring position {pos} (capacity {cfg['context']}), non-finite samples {bad}, "
           f"peak |wav| {peak:.3f}, frames repaired by the persistent launches' repair paths {ops.persistent_repairs(dev)}, "
-          f"persistent path retired: {dev in ops._persist_off}")
-    assert bad == 0 and ops.persistent_repairs(dev) == 0 and dev not in ops._persist_off
+          f"persistent path retired: {ops.persistent_retired(dev) is not None}")
+    assert bad == 0 and ops.persistent_repairs(dev) == 0 and ops.persistent_retired(dev) is None
 
 
 if __name__ == "__main__":
