@@ -757,6 +757,23 @@ int rst_lm_sample_f32(const float* logits, const float* noise, int64_t* tokens, 
 int rst_lm_sample_rows_f32(const float* logits, const float* noise, int64_t* tokens, int B, int V, int ld, int top_k,
                            int noise_stride, int tok_stride, int use_sampling, float temp, int v_limit, const int32_t* v_limit_dev,
                            int v_limit_stride, float top_p, void* workspace, int64_t workspace_bytes, rst_stream_t stream);
+/* The same with one temperature and one top-k per row: row b reads temp_dev[b * param_stride] (<= 0: the row is greedy and reads no
+ * noise) and top_k_dev[b * param_stride], which the kernel clamps into [1, top_k] -- the scalar top_k is then the CAP: it sizes the
+ * candidate list and is the row's noise width (noise_stride >= min(top_k, V)), so no table entry indexes past either.  use_sampling and
+ * temp are not read.  Served by the one-level top-k kernel only: V <= 32768 and top_p == 0, anything else is refused with an error.
+ * temp_dev == NULL and top_k_dev == NULL is rst_lm_sample_rows_f32, which forwards here. */
+int rst_lm_sample_ps_f32(const float* logits, const float* noise, int64_t* tokens, int B, int V, int ld, int top_k,
+                         int noise_stride, int tok_stride, int use_sampling, float temp, int v_limit, const int32_t* v_limit_dev,
+                         int v_limit_stride, float top_p, void* workspace, int64_t workspace_bytes, rst_stream_t stream,
+                         const float* temp_dev, const int32_t* top_k_dev, int param_stride);
+/* Exp(1) noise for the samplers as a counter-based stream: noise[b * noise_stride + c], c < n_cols, = -logf(u), u = ((x >> 9) + 0.5) *
+ * 2^-23 (exact in fp32, in [2^-24, 1 - 2^-24]: the noise is finite, > 0 and at most 16.64), x = word c & 3 of Philox4x32-10 (multipliers
+ * 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) with key (lo32, hi32) of seed_dev[b] and counter (c >> 2, 0, lo32(f),
+ * hi32(f)), f = frame_dev[b * frame_stride] (frame_stride == 0: one counter for the batch).  A pure function of (seed, frame, column):
+ * no generator state, nothing written at columns >= n_cols; seeds and counters are read from device memory, so a captured launch
+ * stays valid as the counters advance and reset.  Refused: B <= 0, n_cols <= 0, noise_stride < n_cols, a NULL pointer. */
+int rst_noise_exp_ps_f32(float* noise, int B, int n_cols, int noise_stride, const uint64_t* seed_dev, const int64_t* frame_dev,
+                         int frame_stride, rst_stream_t stream);
 
 /* LMGen.step's token ring and delay pattern (models/model.py:506-562) on the device.  cache int64 [B][K][CT] (CT = max_delay
  * + 2), delays int32 [K] and the frame counter offset_dev (int64 scalar) stay in HBM, so that a frame is one captured graph.

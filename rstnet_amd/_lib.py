@@ -123,6 +123,8 @@ SIGNATURES = {
     "rst_lm_sample_workspace_bytes": [_i, _i, _i, _i],
     "rst_lm_sample_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p, _f, _p, _l, _p],
     "rst_lm_sample_rows_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p, _i, _f, _p, _l, _p],
+    "rst_lm_sample_ps_f32": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p, _i, _f, _p, _l, _p, _p, _p, _i],
+    "rst_noise_exp_ps_f32": [_p, _i, _i, _i, _p, _p, _i, _p],
     "rst_lm_ring_begin_i64": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "rst_lm_ring_commit_i64": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "rst_lm_ring_begin_ps_i64": [_p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p],

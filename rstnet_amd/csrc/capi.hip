@@ -25,7 +25,7 @@ int rst_check_launch(const char* what) {
 
 extern "C" {
 
-int rst_version(void) { return 129; }      // 129: + rst_frame_ingress, rst_frame_egress (packed frame records of a served batch); 128: + rst_lm_attn_decode_ps_f32, rst_lm_rope_table_ps_f32, rst_lm_attn_prefill_ps_f32, rst_lm_ring_append_ps (per-stream ring positions, ragged append), rst_lm_sample_rows_f32, rst_depth_decode_frame_rows (per-row id limits); 127: + rst_lora_bank_shrink_f32, rst_lora_bank_expand_f32, rst_lora_bank_supported (per-row LoRA adapters from a device-resident bank); 126: + rst_resample_sinc, rst_resample_plan (sample-rate conversion of ragged batches and streams); 125: + rst_skinny_pack_weight_mxfp4w, rst_gemm_skinny_mxfp4w_f32 / _supported (MXFP4 weight-only skinny GEMM); 124: + rst_skinny_pack_weight_fp8w, rst_gemm_skinny_fp8w_f32 / _supported (fp8 weight-only skinny GEMM); 123: + rst_quant_blocks_mxfp4, rst_gemv_mxfp4w_f32 / _supported (MXFP4 weight-only GEMV); 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
+int rst_version(void) { return 130; }      // 130: + rst_noise_exp_ps_f32, rst_lm_sample_ps_f32 (per-stream sampling parameters and counter-based noise); 129: + rst_frame_ingress, rst_frame_egress (packed frame records of a served batch); 128: + rst_lm_attn_decode_ps_f32, rst_lm_rope_table_ps_f32, rst_lm_attn_prefill_ps_f32, rst_lm_ring_append_ps (per-stream ring positions, ragged append), rst_lm_sample_rows_f32, rst_depth_decode_frame_rows (per-row id limits); 127: + rst_lora_bank_shrink_f32, rst_lora_bank_expand_f32, rst_lora_bank_supported (per-row LoRA adapters from a device-resident bank); 126: + rst_resample_sinc, rst_resample_plan (sample-rate conversion of ragged batches and streams); 125: + rst_skinny_pack_weight_mxfp4w, rst_gemm_skinny_mxfp4w_f32 / _supported (MXFP4 weight-only skinny GEMM); 124: + rst_skinny_pack_weight_fp8w, rst_gemm_skinny_fp8w_f32 / _supported (fp8 weight-only skinny GEMM); 123: + rst_quant_blocks_mxfp4, rst_gemv_mxfp4w_f32 / _supported (MXFP4 weight-only GEMV); 122: + rst_quant_rows_fp8, rst_gemv_fp8w_f32 / _supported (fp8 weight-only GEMV); 121: + rst_linear_few_rows_f32, rst_attention_step_f32 / _supported; 120 = round 6: + rst_temporal_decode_frame / _supported / _workspace_bytes, rst_build_id, rst_rvq_chain_supported; 110 = round 5: three-plane weights in operand order (re-pack!), + rst_attention_qkv_f32 / rst_rope_table_f32,
                                            // rst_rvq_search_chain_f32, rst_embed_sum_bf16(add_stride); 105: round 4
 const char* rst_last_error(void) { return g_err; }
 
@@ -794,15 +794,31 @@ int rst_lm_sample_workspace_bytes(int B, int V, int top_k, int top_p_mode) {
     return n > 0x7fffffffL ? -1 : (int)n;
 }
 
-int rst_lm_sample_rows_f32(const float* logits, const float* noise, int64_t* tokens, int B, int V, int ld, int top_k,
-                           int noise_stride, int tok_stride, int use_sampling, float temp, int v_limit, const int32_t* v_limit_dev,
-                           int v_limit_stride, float top_p, void* workspace, int64_t workspace_bytes, rst_stream_t stream) {
+int rst_lm_sample_ps_f32(const float* logits, const float* noise, int64_t* tokens, int B, int V, int ld, int top_k,
+                         int noise_stride, int tok_stride, int use_sampling, float temp, int v_limit, const int32_t* v_limit_dev,
+                         int v_limit_stride, float top_p, void* workspace, int64_t workspace_bytes, rst_stream_t stream,
+                         const float* temp_dev, const int32_t* top_k_dev, int param_stride) {
     RST_REQUIRE(v_limit_stride >= 0 && (v_limit_stride == 0 || v_limit_dev), "lm_sample: limit row stride %d", v_limit_stride);
     LmSampleParams p{};
     p.v_limit = v_limit; p.v_limit_dev = v_limit_dev; p.v_limit_stride = v_limit_stride; p.top_p = top_p; p.ws = workspace; p.ws_bytes = workspace ? workspace_bytes : 0;
     p.logits = logits; p.noise = noise; p.tokens = (long*)tokens; p.B = B; p.V = V; p.ld = ld; p.top_k = top_k;
     p.noise_stride = noise_stride; p.tok_stride = tok_stride; p.use_sampling = use_sampling; p.temp = temp;
-    return rst_launch_lm_sample(p, (hipStream_t)stream);
+    return rst_launch_lm_sample(p, (hipStream_t)stream, LmSampleRows{temp_dev, top_k_dev, param_stride});
+}
+
+int rst_lm_sample_rows_f32(const float* logits, const float* noise, int64_t* tokens, int B, int V, int ld, int top_k,
+                           int noise_stride, int tok_stride, int use_sampling, float temp, int v_limit, const int32_t* v_limit_dev,
+                           int v_limit_stride, float top_p, void* workspace, int64_t workspace_bytes, rst_stream_t stream) {
+    return rst_lm_sample_ps_f32(logits, noise, tokens, B, V, ld, top_k, noise_stride, tok_stride, use_sampling, temp, v_limit, v_limit_dev,
+                                v_limit_stride, top_p, workspace, workspace_bytes, stream, nullptr, nullptr, 0);
+}
+
+int rst_noise_exp_ps_f32(float* noise, int B, int n_cols, int noise_stride, const uint64_t* seed_dev, const int64_t* frame_dev,
+                         int frame_stride, rst_stream_t stream) {
+    LmNoiseParams p{};
+    p.noise = noise; p.seed_dev = (const unsigned long long*)seed_dev; p.frame_dev = (const long*)frame_dev;
+    p.B = B; p.n_cols = n_cols; p.noise_stride = noise_stride; p.frame_stride = frame_stride;
+    return rst_launch_lm_noise(p, (hipStream_t)stream);
 }
 
 int rst_lm_sample_f32(const float* logits, const float* noise, int64_t* tokens, int B, int V, int ld, int top_k,

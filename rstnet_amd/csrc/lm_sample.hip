@@ -13,13 +13,23 @@
 namespace {
 
 template <int NT, int EPT>
-__global__ __launch_bounds__(NT) void sample_kernel(const LmSampleParams p) {
+__global__ __launch_bounds__(NT) void sample_kernel(const LmSampleParams p, const LmSampleRows r) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long comp[];   // [k rounded up to 8] candidates
     __shared__ SampleShared<NT> sh;
     const long b = blockIdx.x;
     const int limit = p.v_limit_dev ? p.v_limit_dev[b * p.v_limit_stride] : p.v_limit;
-    const int tok = sample_row<NT, EPT>(p.logits + b * p.ld, p.noise ? p.noise + b * p.noise_stride : nullptr, p.V, p.top_k,
-                                        p.use_sampling && p.temp > 0.f, p.temp, limit, comp, sh);
+    // per-row parameters (rst_lm_sample_ps_f32): the row's own temperature (<= 0: greedy) and top-k, the latter clamped into
+    // [1, cap = p.top_k] -- the launcher sized `comp` and the noise row by the cap, so no table entry can index past either
+    float temp = p.temp;
+    int top_k = p.top_k;
+    bool sampling = p.use_sampling && p.temp > 0.f;
+    if (r.temp_dev) {
+        temp = r.temp_dev[b * r.param_stride];
+        top_k = min(max(r.top_k_dev[b * r.param_stride], 1), p.top_k);
+        sampling = temp > 0.f;
+    }
+    const int tok = sample_row<NT, EPT>(p.logits + b * p.ld, p.noise ? p.noise + b * p.noise_stride : nullptr, p.V, top_k,
+                                        sampling, temp, limit, comp, sh);
     if (threadIdx.x == 0) p.tokens[b * p.tok_stride] = tok;
 }
 
@@ -455,9 +465,26 @@ long rst_lm_sample_workspace_bytes_impl(int B, int V, int top_k, int top_p_mode)
     return chunks ? (long)B * chunks * (sizeof(SplitRec) + (long)k * 8) : 0;
 }
 
-int rst_launch_lm_sample(const LmSampleParams& p, hipStream_t stream) {
+int rst_launch_lm_sample(const LmSampleParams& p, hipStream_t stream, const LmSampleRows& r) {
     RST_REQUIRE(p.logits && p.tokens && p.B >= 1 && p.V > 0 && p.V <= (1 << 20), "lm_sample: bad arguments");
     RST_REQUIRE(!p.use_sampling || p.temp <= 0.f || p.noise, "lm_sample: sampling needs the exponential noise tensor");
+    if (r.temp_dev || r.top_k_dev) {
+        // per-row parameters: the one-level top-k kernel with `top_k` as the cap; every other form is refused, none is substituted
+        RST_REQUIRE(r.temp_dev && r.top_k_dev && r.param_stride >= 0, "lm_sample: per-row parameters need both tables (temp_dev, top_k_dev) and a stride >= 0");
+        RST_REQUIRE(!(p.top_p > 0.f), "lm_sample: per-row parameters are not served with top_p (nucleus sampling keeps scalar parameters)");
+        RST_REQUIRE(p.V <= 32768, "lm_sample: per-row parameters are served by the one-level kernel only (V = %d > 32768)", p.V);
+        RST_REQUIRE(p.noise && p.top_k >= 1, "lm_sample: per-row parameters need the noise tensor and a top-k cap >= 1 (got %d)", p.top_k);
+        const int cap = p.top_k < p.V ? p.top_k : p.V;
+        RST_REQUIRE(cap <= 8192, "lm_sample: top-k cap %d exceeds the 8192 candidate stage", cap);
+        RST_REQUIRE(p.B == 1 || p.noise_stride >= cap, "lm_sample: noise row stride %d < top-k cap %d", p.noise_stride, cap);
+        LmSampleParams q = p;
+        q.top_k = cap;
+        const size_t lds = (size_t)((cap + 7) & ~7) * 8;
+        if (p.V <= 2048) hipLaunchKernelGGL((sample_kernel<256, 8>), dim3(p.B), dim3(256), lds, stream, q, r);
+        else if (p.V <= 4096) hipLaunchKernelGGL((sample_kernel<256, 16>), dim3(p.B), dim3(256), lds, stream, q, r);
+        else hipLaunchKernelGGL((sample_kernel<1024, 32>), dim3(p.B), dim3(1024), lds, stream, q, r);
+        return rst_check_launch("lm_sample");
+    }
     const bool sampling = p.use_sampling && p.temp > 0.f;
     if (sampling && p.top_p > 0.f) {
         // nucleus sampling takes precedence over top-k, as in sample_token (utils/sampling.py:96-99)
@@ -470,9 +497,9 @@ int rst_launch_lm_sample(const LmSampleParams& p, hipStream_t stream) {
     const int k = p.top_k > 0 && p.top_k < p.V ? p.top_k : p.V;
     RST_REQUIRE(!sampling || k <= 8192, "lm_sample: top-k %d exceeds the 8192 candidate stage", k);
     const size_t lds = sampling ? (size_t)((k + 7) & ~7) * 8 : 0;      // greedy keeps no candidate list
-    if (p.V <= 2048) hipLaunchKernelGGL((sample_kernel<256, 8>), dim3(p.B), dim3(256), lds, stream, p);
-    else if (p.V <= 4096) hipLaunchKernelGGL((sample_kernel<256, 16>), dim3(p.B), dim3(256), lds, stream, p);
-    else if (p.V <= 32768) hipLaunchKernelGGL((sample_kernel<1024, 32>), dim3(p.B), dim3(1024), lds, stream, p);
+    if (p.V <= 2048) hipLaunchKernelGGL((sample_kernel<256, 8>), dim3(p.B), dim3(256), lds, stream, p, r);
+    else if (p.V <= 4096) hipLaunchKernelGGL((sample_kernel<256, 16>), dim3(p.B), dim3(256), lds, stream, p, r);
+    else if (p.V <= 32768) hipLaunchKernelGGL((sample_kernel<1024, 32>), dim3(p.B), dim3(1024), lds, stream, p, r);
     else {
         RST_REQUIRE(!sampling || k <= 1024, "lm_sample: top-k %d > 1024 for a vocabulary of %d", k, p.V);
         const int kc = sampling ? k : 1;

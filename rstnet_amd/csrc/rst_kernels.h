@@ -355,8 +355,25 @@ struct LmSampleParams {
     void* ws;                  // scratch of rst_lm_sample_workspace_bytes_impl bytes: chunk records + candidates of the two-level form
     long ws_bytes;             // for V > 32768, the sort buffer of top_p; NULL: one-level kernels only (top_p then refused)
 };
+// per-row parameters (rst_lm_sample_ps_f32; one-level top-k kernel only, its second argument -- LmSampleParams keeps its layout, and with
+// it every other sampling kernel its code): row b reads temp_dev[b * param_stride] (<= 0: greedy, reads no noise) and
+// top_k_dev[b * param_stride], clamped into [1, top_k] -- LmSampleParams::top_k is then the cap that sizes `comp` and the noise row
+struct LmSampleRows {
+    const float* temp_dev;     // both NULL: the scalar temp / top_k / use_sampling hold for every row
+    const int* top_k_dev;
+    long param_stride;
+};
 long rst_lm_sample_workspace_bytes_impl(int B, int V, int top_k, int top_p_mode);
-int rst_launch_lm_sample(const LmSampleParams& p, hipStream_t stream);
+int rst_launch_lm_sample(const LmSampleParams& p, hipStream_t stream, const LmSampleRows& rows = LmSampleRows{nullptr, nullptr, 0});
+
+// ---- lm_noise.hip: counter-based Exp(1) noise, one Philox4x32-10 stream per (seed, frame counter)
+struct LmNoiseParams {
+    float* noise;                        // [B][noise_stride], columns < n_cols written
+    const unsigned long long* seed_dev;  // [B]
+    const long* frame_dev;               // stream b reads frame_dev[b * frame_stride]
+    int B, n_cols, noise_stride, frame_stride;
+};
+int rst_launch_lm_noise(const LmNoiseParams& p, hipStream_t stream);
 
 // ---- lm_depth.hip: the depth phase of a frame as one persistent launch
 #define RST_DEPTH_MAX_L 8

@@ -142,19 +142,24 @@ class DepthDecoder:
 
     def decode_frame(self, tokens: torch.Tensor, h: torch.Tensor, noise: Optional[torch.Tensor], pos: torch.Tensor, *, use_sampling: bool,
                      temp: float, top_k: int, limits: Optional[torch.Tensor] = None, rings=None, w8: Optional[tuple] = None, keep=None,
-                     persistent: bool = True) -> None:
+                     persistent: bool = True, temps: Optional[torch.Tensor] = None, top_ks: Optional[torch.Tensor] = None) -> None:
         """The whole phase IN PLACE on ``tokens`` (int64 ``[B, >= dep_q + 1]``, any row stride): column 0 holds the text token, step k embeds
         column k and samples column k + 1.  ``h`` fp32 ``[B, dim]``; ``noise``: Exp(1) draws ``[B, dep_q * top_k]`` or None (greedy); ``pos``:
         int64 ``arange(dep_q)`` on the device (the steps are positions 0 .. dep_q - 1 of a ring that restarts every frame, as constant device
         scalars: no counter to zero and bump); ``limits`` int32 ``[dep_q]``: per-step id blanking, or ``[B, dep_q]``: per stream and step; ``w8``: the fp8 copy of ``in_all()``.
         ``rings``, the KV rings of the launch-per-op chain -- None: those installed on the transformer; a state: swapped in for the call; a
         callable ``B -> state``: called only if the chain runs.  ``keep``: the object whose ``tables`` attribute keeps the pointer tables
-        alive (a captured frame embeds their device pointers).  ``persistent=False`` keeps the call off the one-launch route."""
+        alive (a captured frame embeds their device pointers).  ``persistent=False`` keeps the call off the one-launch route.  ``temps`` fp32
+        ``[B]`` with ``top_ks`` int32 ``[B]``: one temperature (<= 0: greedy) and top-k per stream for every step's sampler (``ops.lm_sample_ps``;
+        ``top_k`` is then the cap and the width of a step's noise block).  The persistent launch keeps scalar parameters, so such a call
+        takes the launch-per-op chain at every batch size."""
         dep, Q = self.dep, len(self.heads)
         B, dev = tokens.shape[0], h.device
         h_all = ops.lm_linear(h, self.in_all(), w8=w8)      # the in-projections of all dep_q steps: one 8 x larger launch instead of eight
         Hd, card = dep.layers[0].gating[0].linear_out.weight.shape[1], self.heads[0].weight.shape[0]
-        if ops.depth_frame_enabled(dev) and persistent and \
+        if (temps is None) != (top_ks is None):
+            raise ValueError("decode_frame: per-stream sampling parameters come as a pair (temps, top_ks)")
+        if ops.depth_frame_enabled(dev) and persistent and temps is None and \
                 ops.depth_frame_supported(B, dep.d_model, dep.num_heads, Hd, card, Q, len(dep.layers), top_k, device=dev):
             # batch 1 / 2: the whole phase (dep_q x (L layers + head + sampler)) is ONE persistent launch whose ops hand their vectors
             # over in-kernel, on a dense [B, dep_q + 1] buffer; the slot -> position map follows the capacity of the rings in use
@@ -174,8 +179,11 @@ class DepthDecoder:
         try:
             for k in range(Q):
                 logits = self.step_logits(k, tokens, k, None, h_all=h_all, pos=pos[k:k + 1], step_index=k)
-                ops.lm_sample(logits, use_sampling=use_sampling, temp=temp, top_k=top_k, out=tokens[:, k + 1],
-                              noise=None if noise is None else noise[:, k * top_k:(k + 1) * top_k],
-                              limit_dev=None if limits is None else (limits[k:k + 1] if limits.dim() == 1 else limits[:, k]))
+                nz = None if noise is None else noise[:, k * top_k:(k + 1) * top_k]
+                limit_dev = None if limits is None else (limits[k:k + 1] if limits.dim() == 1 else limits[:, k])
+                if temps is not None:
+                    ops.lm_sample_ps(logits, top_k=top_k, noise=nz, temps=temps, top_ks=top_ks, out=tokens[:, k + 1], limit_dev=limit_dev)
+                else:
+                    ops.lm_sample(logits, use_sampling=use_sampling, temp=temp, top_k=top_k, out=tokens[:, k + 1], noise=nz, limit_dev=limit_dev)
         finally:
             dep._streaming_state = saved

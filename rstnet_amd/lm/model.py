@@ -14,6 +14,7 @@ environment flag ``NO_CUDA_GRAPH`` disables that (``compile.py:168-174``).
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Dict, List, Optional
 
@@ -637,6 +638,68 @@ def prefill_token_plan(cache: torch.Tensor, offset: int, user: torch.Tensor, own
     return line[:, :, :T], ring
 
 
+SAMPLING_KEYS = ("use_sampling", "temp", "temp_text", "top_k", "top_k_text", "seed")
+
+
+def check_sampling(values: dict, top_k_cap: int, top_k_text_cap: int) -> dict:
+    """One stream's sampling settings as ``set_stream_sampling`` takes them -> the same with every value in its type; ``ValueError`` for an
+    unknown key, a temperature that is negative or not finite, a top-k outside ``1 .. cap``, a seed outside ``0 .. 2^64 - 1``.  ``None``
+    entries are dropped.  Host arithmetic only (the slot server validates a client's settings with it before the upgrade)."""
+    out = {}
+    for key, v in values.items():
+        if key not in SAMPLING_KEYS:
+            raise ValueError(f"unknown sampling setting {key!r} (known: {', '.join(SAMPLING_KEYS)})")
+        if v is None:
+            continue
+        if key == "use_sampling":
+            out[key] = bool(v)
+        elif key in ("temp", "temp_text"):
+            t = float(v)
+            if not math.isfinite(t) or t < 0.0:
+                raise ValueError(f"{key} = {v!r}: a temperature is a finite number >= 0")
+            out[key] = t
+        elif key in ("top_k", "top_k_text"):
+            cap = top_k_cap if key == "top_k" else top_k_text_cap
+            if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= cap:
+                raise ValueError(f"{key} = {v!r}: an integer in 1 .. {cap} (the cap is the session's {key})")
+            out[key] = int(v)
+        else:
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < 1 << 64:
+                raise ValueError(f"seed = {v!r}: an integer in 0 .. 2^64 - 1")
+            out[key] = int(v)
+    return out
+
+
+def _draw_seeds(n: int) -> List[int]:
+    """``n`` seeds from torch's default CPU generator (``torch.manual_seed`` makes a run repeatable)."""
+    return [int(v) for v in torch.randint(0, 1 << 62, (n,), dtype=torch.int64).tolist()]
+
+
+class _StreamSampling:
+    """Per-stream sampling of a per-stream session: the device tables the frame's samplers and its noise launch read,
+    their host mirror, and the persistent noise buffer.  The captured frame holds the tables' addresses; ``write`` updates them in place."""
+
+    def __init__(self, B: int, device, defaults: dict, n_noise: int):
+        self.rows = [dict(defaults, seed=s) for s in _draw_seeds(B)]
+        self.temp_text = torch.zeros(B, device=device, dtype=torch.float32)
+        self.temp = torch.zeros(B, device=device, dtype=torch.float32)
+        self.top_k_text = torch.ones(B, device=device, dtype=torch.int32)
+        self.top_k = torch.ones(B, device=device, dtype=torch.int32)
+        self.seed = torch.zeros(B, device=device, dtype=torch.int64)          # uint64 bit patterns
+        self.noise = torch.zeros(B, n_noise, device=device, dtype=torch.float32)
+        self.write(("temp", "temp_text", "top_k", "top_k_text", "seed"))
+
+    def write(self, fields) -> None:
+        """The named tables from the host mirror: one whole-table copy per table (B values), whatever the number of rows changed."""
+        for f in fields:
+            if f in ("temp", "temp_text"):
+                getattr(self, f).copy_(torch.tensor([r[f] if r["use_sampling"] else 0.0 for r in self.rows], dtype=torch.float32))
+            elif f in ("top_k", "top_k_text"):
+                getattr(self, f).copy_(torch.tensor([r[f] for r in self.rows], dtype=torch.int32))
+            else:
+                self.seed.copy_(torch.tensor([s - (1 << 64) if s >= 1 << 63 else s for s in (r["seed"] for r in self.rows)], dtype=torch.int64))
+
+
 @dataclass
 class _LMGenState:
     cache: torch.Tensor            # int64 [B, K, max_delay + 2] token ring
@@ -650,6 +713,7 @@ class _LMGenState:
     temporal_base: Optional[int] = None    # host-side position of the temporal rings at frame 0 of this session
     temporal_choice: Optional[bool] = None  # whether the captured frame takes the persistent temporal launch
     frames: Optional[List[int]] = None     # per-stream session: host mirror of `offset_dev`, frames each stream has stepped since its (re)start
+    sampling: Optional[_StreamSampling] = None   # LMGen(per_stream_sampling=True) on a per-stream session: the tables the frame samples by
 
     def reset(self) -> None:
         self.offset = 0
@@ -665,12 +729,17 @@ class LMGen(StreamingModule[_LMGenState]):
     ring commit + delayed gather -- is ONE captured graph fed by a single copy of the user tokens."""
 
     def __init__(self, lm_model: LMModel, use_sampling: bool = True, temp: float = 0.8, temp_text: float = 0.7,
-                 top_k: int = 250, top_k_text: int = 25, check: bool = False):
+                 top_k: int = 250, top_k_text: int = 25, check: bool = False, per_stream_sampling: bool = False):
         assert not lm_model.training, "generation shouldn't be used in training mode."
         super().__init__()
         self.lm_model = lm_model
         self.use_sampling, self.temp, self.temp_text = use_sampling, temp, temp_text
         self.top_k, self.top_k_text, self.check = top_k, top_k_text, check
+        # per_stream_sampling (DESIGN.md §3.24): in a per-stream session every stream samples by its own temperatures, top-k and seed, read
+        # from device tables (`set_stream_sampling`); the constructor's values are the defaults, its two top-k the caps
+        self.per_stream_sampling = bool(per_stream_sampling)
+        if self.per_stream_sampling:
+            check_sampling(self.default_sampling(), max(int(top_k), 1), max(int(top_k_text), 1))    # (a top-k <= 0, "all ids", is no cap)
         self.max_delay = max(lm_model.delays)
         self.delays_cuda = torch.tensor(lm_model.delays, device=lm_model.device, dtype=torch.long)
         self._delays_i32 = self.delays_cuda.to(torch.int32)
@@ -682,9 +751,66 @@ class LMGen(StreamingModule[_LMGenState]):
                            dtype=torch.long)
         disable = lm.device.type != "cuda"
         per_stream = self._streaming_per_stream
+        sampling = None
+        if per_stream and self.per_stream_sampling:
+            sampling = _StreamSampling(batch_size, lm.device, self.default_sampling(), self.top_k_text + lm.dep_q * self.top_k)
         return _LMGenState(cache, lm._get_initial_token(), torch.zeros(batch_size if per_stream else 1, device=lm.device, dtype=torch.long),
                            _Graphed(self._frame, disable=disable), RecaptureGate(lm.device),
-                           depth=lm.depformer._init_streaming_state(batch_size), frames=[0] * batch_size if per_stream else None)
+                           depth=lm.depformer._init_streaming_state(batch_size), frames=[0] * batch_size if per_stream else None,
+                           sampling=sampling)
+
+    def default_sampling(self) -> dict:
+        """The constructor's sampling settings: what every stream of a ``per_stream_sampling`` session starts with."""
+        return dict(use_sampling=bool(self.use_sampling), temp=float(self.temp), temp_text=float(self.temp_text), top_k=int(self.top_k),
+                    top_k_text=int(self.top_k_text))
+
+    def _sampling_state(self) -> _StreamSampling:
+        state = self._streaming_state
+        if state is None:
+            raise RuntimeError("You should wrap those calls with a `with lm_gen.streaming(): ...`.")
+        if state.sampling is None:
+            raise ValueError("per-stream sampling needs LMGen(..., per_stream_sampling=True) and a session opened with "
+                             "streaming(batch_size, per_stream=True)")
+        return state.sampling
+
+    def set_stream_sampling(self, rows, *, use_sampling=None, temp=None, temp_text=None, top_k=None, top_k_text=None, seed=None) -> None:
+        """Streams ``rows`` sample by these settings from the next frame on; ``None`` leaves a setting as it is.  A value holds for every
+        row of ``rows``, or is a sequence with one value per row (in the order of ``rows``).  ``top_k`` / ``top_k_text`` lie in 1 .. the
+        constructor's value (the cap: it fixes the noise layout, so one stream's top-k moves nobody's draws); a temperature is finite and
+        >= 0 (0: greedy); ``use_sampling=False`` makes the stream greedy and keeps its temperatures for a later ``True``; ``seed``
+        (0 .. 2^64 - 1) starts the stream's noise over as ``(seed, its own frame counter)``.  Everything is validated on the host before
+        anything is written; the writes are eager in-place copies between two frames, like ``reset_streams``: the captured frame reads the
+        tables from device memory and stays valid."""
+        sp = self._sampling_state()
+        order = [int(b) for b in rows]
+        check_rows(order, len(sp.rows))
+        if len(set(order)) != len(order):
+            raise ValueError(f"set_stream_sampling: rows {order} name a stream twice")
+        given = dict(use_sampling=use_sampling, temp=temp, temp_text=temp_text, top_k=top_k, top_k_text=top_k_text, seed=seed)
+        new = [dict() for _ in order]
+        for key, v in given.items():
+            if v is None:
+                continue
+            vals = list(v) if isinstance(v, (list, tuple)) else [v] * len(order)
+            if len(vals) != len(order):
+                raise ValueError(f"set_stream_sampling: {key} has {len(vals)} values for {len(order)} rows")
+            for d, x in zip(new, vals):
+                d[key] = x
+        cap, cap_text = max(int(self.top_k), 1), max(int(self.top_k_text), 1)
+        new = [check_sampling(d, cap, cap_text) for d in new]
+        touched = set()
+        for b, d in zip(order, new):
+            sp.rows[b].update(d)
+            touched |= set(d)
+        if "use_sampling" in touched:
+            touched |= {"temp", "temp_text"}
+        sp.write(sorted(touched - {"use_sampling"}))
+
+    def stream_sampling(self, b: int) -> dict:
+        """Stream ``b``'s sampling settings (from the host mirror of the device tables)."""
+        sp = self._sampling_state()
+        (b,) = check_rows([b], len(sp.rows))
+        return dict(sp.rows[b])
 
     def reset_streams(self, rows) -> None:
         """Streams ``rows`` of a per-stream session (``streaming(batch_size, per_stream=True)``) start a new conversation with the next
@@ -709,6 +835,11 @@ class LMGen(StreamingModule[_LMGenState]):
             tst.pos[rows] = 0
         for b in rows:
             state.frames[b] = 0
+        if state.sampling is not None:
+            # a new conversation draws a new seed (default CPU generator); its settings stay until set_stream_sampling changes them
+            for b, s in zip(rows, _draw_seeds(len(rows))):
+                state.sampling.rows[b]["seed"] = s
+            state.sampling.write(("seed",))
 
     def stream_valid(self) -> List[int]:
         """The streams whose last ``step`` output is meaningful: those whose own frame count exceeds ``max_delay`` (a scalar session:
@@ -734,16 +865,26 @@ class LMGen(StreamingModule[_LMGenState]):
         input_ = ops.lm_ring_begin(state.cache, user_tokens, state.initial.reshape(-1), self._delays_i32, state.offset_dev,
                                    lm.dep_q + 1)
         # one draw of Exp(1) noise per frame for the text sampler and the dep_q audio samplers (utils/sampling.py:44-46)
-        noise = self._noise(B, self.top_k_text + lm.dep_q * self.top_k)
+        sp = state.sampling
+        if sp is not None:
+            # per-stream sampling: the same columns (text, then dep_q blocks of top_k) from each stream's own (seed, frame counter) stream,
+            # read here, before lm_ring_commit moves the counters
+            noise = ops.noise_exp_rows(sp.seed, state.offset_dev, sp.noise.shape[1], out=sp.noise)
+        else:
+            noise = self._noise(B, self.top_k_text + lm.dep_q * self.top_k)
         transformer_out, text_logits = lm.forward_text(input_.view(B, -1, 1))
         tokens = torch.empty(B, lm.dep_q + 1, device=input_.device, dtype=torch.long)
-        ops.lm_sample(text_logits.view(B, -1), use_sampling=self.use_sampling, temp=self.temp_text, top_k=self.top_k_text,
-                      noise=None if noise is None else noise[:, :self.top_k_text], out=tokens[:, 0])
-        self._depth(tokens, transformer_out.view(B, lm.dim).contiguous(), None if noise is None else noise[:, self.top_k_text:])
+        if sp is not None:
+            ops.lm_sample_ps(text_logits.view(B, -1), top_k=self.top_k_text, noise=noise[:, :self.top_k_text], temps=sp.temp_text,
+                             top_ks=sp.top_k_text, out=tokens[:, 0])
+        else:
+            ops.lm_sample(text_logits.view(B, -1), use_sampling=self.use_sampling, temp=self.temp_text, top_k=self.top_k_text,
+                          noise=None if noise is None else noise[:, :self.top_k_text], out=tokens[:, 0])
+        self._depth(tokens, transformer_out.view(B, lm.dim).contiguous(), None if noise is None else noise[:, self.top_k_text:], sp)
         out = ops.lm_ring_commit(state.cache, tokens, self._delays_i32, state.offset_dev, self.max_delay)
         return out, input_
 
-    def _depth(self, tokens: torch.Tensor, h_t: torch.Tensor, noise: Optional[torch.Tensor]) -> None:
+    def _depth(self, tokens: torch.Tensor, h_t: torch.Tensor, noise: Optional[torch.Tensor], sp: Optional[_StreamSampling] = None) -> None:
         """The ``dep_q`` sequential depth-transformer steps (models/model.py:564-597): ``tokens[:, 0]`` is the text token,
         step ``cb`` embeds ``tokens[:, cb]`` and samples ``tokens[:, cb + 1]`` in place.  The depth KV rings are persistent
         buffers; the steps are positions 0 .. dep_q - 1 of a ring that restarts every frame (= the reference's fresh
@@ -752,9 +893,11 @@ class LMGen(StreamingModule[_LMGenState]):
         # the chain's rings belong to the session (so that a frame graph captured by another live session keeps valid pointers and
         # exiting `streaming()` releases them); a bare `depformer_step` call outside any session gets throw-away rings
         mine = state is not None and state.depth is not None and state.depth.k[0].shape[0] == B
+        # (``sp``, the session's per-stream sampling tables: the persistent launch keeps scalar parameters, so the chain runs at every batch size)
         lm.depth_decoder.decode_frame(
             tokens, h_t, noise, self._depth_pos, use_sampling=self.use_sampling, temp=self.temp, top_k=self.top_k, keep=state,
-            rings=state.depth if mine else lm.depformer._init_streaming_state, w8=lm.depformer_in_all_w8(), persistent=h_t.is_cuda)
+            rings=state.depth if mine else lm.depformer._init_streaming_state, w8=lm.depformer_in_all_w8(),
+            persistent=h_t.is_cuda and sp is None, temps=None if sp is None else sp.temp, top_ks=None if sp is None else sp.top_k)
 
     @torch.no_grad()
     def step(self, input_tokens: torch.Tensor) -> Optional[torch.Tensor]:

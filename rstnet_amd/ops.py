@@ -1828,7 +1828,8 @@ def lm_sample(logits: torch.Tensor, *, use_sampling: bool, temp: float, top_k: i
     (or the int32 device scalar ``limit_dev``; int32 ``[B]``, any element stride, e.g. a column of a ``[B, n]`` table: one limit per row,
     rst_lm_sample_rows_f32): ids >= limit are never drawn when sampling.  ``top_p > 0``: nucleus sampling
     (utils/sampling.py:66-82) instead of top-k; ``noise`` is then ``[B, V]`` (one draw per sorted position).  ``two_level=False``
-    keeps the one-workgroup-per-row kernel for vocabularies above 32768 (A/B measurements, tests)."""
+    keeps the one-workgroup-per-row kernel for vocabularies above 32768 (A/B measurements, tests).  One temperature and top-k per row:
+    ``lm_sample_ps``."""
     _chk(logits, "logits")
     _chk(limit_dev, "limit_dev", torch.int32, contiguous=False)
     B, V = logits.shape
@@ -1856,6 +1857,77 @@ def lm_sample(logits: torch.Tensor, *, use_sampling: bool, temp: float, top_k: i
     tail = (float(top_p) if nucleus else 0.0, _ptr(ws), nbytes, _stream())
     _lib.check(_lib.lib().rst_lm_sample_rows_f32(*head, limit_dev.stride(0), *tail) if rows else _lib.lib().rst_lm_sample_f32(*head, *tail))
     return out
+
+
+@_on_tensor_device
+def lm_sample_ps(logits: torch.Tensor, *, top_k: int, noise: Optional[torch.Tensor], temps: Optional[torch.Tensor],
+                 top_ks: Optional[torch.Tensor], out: Optional[torch.Tensor] = None, limit: int = 0,
+                 limit_dev: Optional[torch.Tensor] = None, top_p: float = 0.0) -> torch.Tensor:
+    """``lm_sample`` with one temperature and one top-k per row (rst_lm_sample_ps_f32): ``temps`` fp32 ``[B]`` (<= 0: that
+    row is greedy and reads no noise) with ``top_ks`` int32 ``[B]``, device tensors of one common element stride (e.g. two columns of
+    ``[B, n]`` tables).  ``top_k`` is the CAP: the kernel clamps every row's value into 1 .. cap, and ``noise`` is ``[B, >= cap]``.  Served by the
+    one-level top-k kernel only; refused, never substituted: ``top_p > 0`` and V > 32768.  (Its own entry point so that ``lm_sample`` keeps
+    the signature its callers and their recorded launch plans know.)"""
+    _chk(logits, "logits")
+    _chk(limit_dev, "limit_dev", torch.int32, contiguous=False)
+    B, V = logits.shape
+    if temps is None or top_ks is None:
+        raise ValueError("rstnet_amd.ops: lm_sample: per-row parameters come as a pair, `temps` fp32 [B] and `top_ks` int32 [B]")
+    _chk(temps, "temps", torch.float32, contiguous=False)
+    _chk(top_ks, "top_ks", torch.int32, contiguous=False)
+    if temps.dim() != 1 or top_ks.dim() != 1 or temps.numel() != B or top_ks.numel() != B:
+        raise ValueError(f"rstnet_amd.ops: lm_sample: `temps` / `top_ks` hold one value per row ([{B}]); got {tuple(temps.shape)} / {tuple(top_ks.shape)}")
+    stride = temps.stride(0) if B > 1 else 1
+    if B > 1 and top_ks.stride(0) != stride:
+        raise ValueError(f"rstnet_amd.ops: lm_sample: `temps` and `top_ks` need one common element stride, got {temps.stride(0)} and {top_ks.stride(0)}")
+    if top_p > 0.0:
+        raise ValueError("rstnet_amd.ops: lm_sample: per-row parameters are not served with top_p > 0 (nucleus sampling keeps scalar parameters)")
+    if V > 32768:
+        raise ValueError(f"rstnet_amd.ops: lm_sample: per-row parameters are served by the one-level kernel only (V <= 32768), got V = {V}")
+    cap = min(int(top_k), V)
+    if cap < 1:
+        raise ValueError(f"rstnet_amd.ops: lm_sample: with per-row parameters `top_k` is the cap of every row's top-k: >= 1, got {top_k}")
+    if noise is None or not noise.is_cuda or noise.dtype != torch.float32 or noise.dim() != 2 or noise.stride(1) != 1 \
+            or noise.shape[0] != B or noise.shape[1] < cap:
+        raise ValueError(f"rstnet_amd.ops: lm_sample: per-row parameters need `noise` float32 [B, >= {cap}] with unit column stride")
+    if limit_dev is not None and limit_dev.numel() != 1 and (limit_dev.dim() != 1 or limit_dev.numel() != B):
+        raise ValueError(f"rstnet_amd.ops: `limit_dev` holds one limit, or one per row as int32 [{B}]; got {tuple(limit_dev.shape)}")
+    if out is None:
+        out = torch.empty(B, device=logits.device, dtype=torch.int64)
+    elif not out.is_cuda or out.dtype != torch.int64 or out.dim() != 1 or out.shape[0] != B:
+        raise ValueError("rstnet_amd.ops: `out` must be an int64 CUDA/HIP vector of length B")
+    rows = limit_dev is not None and limit_dev.numel() == B and B > 1
+    _lib.check(_lib.lib().rst_lm_sample_ps_f32(
+        _ptr(logits), _ptr(noise), _ptr(out), B, V, V, cap, noise.stride(0), out.stride(0) if B > 1 else 1, 1, 1.0, int(limit), _ptr(limit_dev),
+        limit_dev.stride(0) if rows else 0, 0.0, None, 0, _stream(), _ptr(temps), _ptr(top_ks), stride))
+    return out
+
+
+@_on_tensor_device
+def noise_exp_rows(seeds: torch.Tensor, frames: torch.Tensor, n_cols: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Exp(1) noise fp32 ``[B, n_cols]`` for the samplers as a counter-based stream (rst_noise_exp_ps_f32): row ``b``
+    is a pure function of ``seeds[b]`` (int64 ``[B]``, read as uint64), its frame counter -- ``frames`` int64 ``[B]``, or one element for
+    the whole batch -- and the column.  Both are read from device memory by the launch.  ``out``: fp32 ``[B, >= n_cols]`` with unit column
+    stride (columns past ``n_cols`` are left alone); returns the ``[B, n_cols]`` view."""
+    _chk(seeds, "seeds", torch.int64)
+    _chk(frames, "frames", torch.int64)
+    if seeds.dim() != 1 or seeds.numel() < 1:
+        raise ValueError(f"rstnet_amd.ops: noise_exp_rows: `seeds` is int64 [B], got {tuple(seeds.shape)}")
+    B = seeds.numel()
+    if frames.numel() not in (1, B):
+        raise ValueError(f"rstnet_amd.ops: noise_exp_rows: `frames` holds one counter, or one per row as int64 [{B}]; got {tuple(frames.shape)}")
+    n_cols = int(n_cols)
+    if n_cols < 1:
+        raise ValueError(f"rstnet_amd.ops: noise_exp_rows: n_cols = {n_cols}")
+    if out is None:
+        out = torch.empty(B, n_cols, device=seeds.device, dtype=torch.float32)
+    elif not out.is_cuda or out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < n_cols or out.stride(1) != 1 \
+            or (B > 1 and out.stride(0) < n_cols):
+        raise ValueError(f"rstnet_amd.ops: noise_exp_rows: `out` must be float32 [{B}, >= {n_cols}] with unit column stride")
+    with _profiled("noise_exp", 0.0, 4 * B * n_cols + 16 * B, (B, n_cols)):
+        _lib.check(_lib.lib().rst_noise_exp_ps_f32(_ptr(out), B, n_cols, out.stride(0) if B > 1 else max(out.stride(0), n_cols), _ptr(seeds),
+                                                  _ptr(frames), 1 if frames.numel() == B and B > 1 else 0, _stream()))
+    return out[:, :n_cols]
 
 
 @_on_tensor_device

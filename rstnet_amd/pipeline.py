@@ -142,6 +142,15 @@ class StreamingPipeline:
             self._frames[b] = 0
         self._awaiting = sorted(set(self._awaiting) | set(rows)) if self.lm_gen.max_delay > 0 else self._awaiting
 
+    def set_stream_sampling(self, rows, **kw) -> None:
+        """``LMGen.set_stream_sampling``: rows ``rows`` sample by these settings from the next frame on (an ``LMGen`` built with
+        ``per_stream_sampling=True``; in-place table writes between two frames, the captured frame goes on replaying)."""
+        self.lm_gen.set_stream_sampling(rows, **kw)
+
+    def stream_sampling(self, b: int) -> dict:
+        """``LMGen.stream_sampling``: row ``b``'s sampling settings."""
+        return self.lm_gen.stream_sampling(b)
+
     def _reset_decoder_side(self, rows) -> None:
         self.mimi.reset_streams(rows, side="decoder")
         if self._rs_out is not None:

@@ -16,6 +16,8 @@ device (``codec/audio_resample.py``: ``StreamResampler``), which is what the Opu
 
 ``--slots N`` replaces the lock by N rows of one per-stream batch (``SlotServerState`` below): same protocol, N
 conversations at once, 503 instead of waiting when all rows are taken, one sample rate per server (``--client-rate``).
+``--per-slot-sampling`` (with ``--slots``) lets a client pick its own sampling settings and seed with
+``/api/chat?temp=&temp_text=&topk=&topk_text=&seed=&greedy=1`` (``chat_sampling``); without the flag those parameters are refused with 400.
 """
 from __future__ import annotations
 
@@ -126,6 +128,43 @@ def client_geometry(sr: Optional[str], codec_rate: int, frame_size: int):
     except ValueError as e:
         raise ValueError(f"sample rate {rate} cannot be served: {e}") from None
     return rate, frame_in
+
+
+SAMPLING_QUERY = {"temp": "temp", "temp_text": "temp_text", "topk": "top_k", "topk_text": "top_k_text", "seed": "seed", "greedy": "use_sampling"}
+
+
+def chat_sampling(query, per_slot_sampling: bool, top_k_cap: int, top_k_text_cap: int) -> Optional[dict]:
+    """The sampling parameters of ``/api/chat?temp=&temp_text=&topk=&topk_text=&seed=&greedy=1`` -> the ``sampling`` dict of
+    ``SlotServerState.join`` (``set_stream_sampling`` keywords), ``None`` when the client names none.  ``ValueError`` -- answered with 400
+    before the upgrade -- when one is present on a server without ``--per-slot-sampling``, for a value that does not parse (a temperature
+    is a decimal number, top-k and seed are integers, ``greedy`` is 0 or 1) or lies outside its range (``lm.model.check_sampling``: a
+    finite temperature >= 0, a top-k in 1 .. the server's, a seed in 0 .. 2^64 - 1).  ``query``: any mapping of strings (``request.query``).
+    Host arithmetic only."""
+    from .lm.model import check_sampling
+    present = [name for name in SAMPLING_QUERY if query.get(name) not in (None, "")]
+    if not present:
+        return None
+    if not per_slot_sampling:
+        raise ValueError(f"this server samples every conversation alike: ?{present[0]}= needs a server started with --slots N --per-slot-sampling")
+    out = {}
+    for name in present:
+        raw, key = query.get(name), SAMPLING_QUERY[name]
+        try:
+            if name == "greedy":
+                if raw not in ("0", "1"):
+                    raise ValueError
+                out[key] = raw == "0"
+            elif name in ("temp", "temp_text"):
+                out[key] = float(raw)
+            else:
+                out[key] = int(raw)
+        except ValueError:
+            kind = {"greedy": "0 or 1", "temp": "a decimal number", "temp_text": "a decimal number"}.get(name, "an integer")
+            raise ValueError(f"?{name}={raw!r} does not parse: it takes {kind}") from None
+    try:
+        return check_sampling(out, top_k_cap, top_k_text_cap)
+    except ValueError as e:
+        raise ValueError(f"sampling parameters refused: {e}") from None
 
 
 class ServerState:
@@ -298,7 +337,7 @@ class SlotServerState:
     ``pipeline=``: anything with the pipeline's packed surface (the CPU tests pass a stand-in)."""
 
     def __init__(self, mimi, lm, device, slots: int, client_rate: Optional[int] = None, text_tokenizer=None, lm_gen=None, pipeline=None,
-                 max_backlog: int = 4, **lm_gen_kwargs):
+                 max_backlog: int = 4, per_slot_sampling: bool = False, **lm_gen_kwargs):
         from . import slots as SL
         if not 1 <= int(slots) <= 64:
             raise ValueError(f"--slots takes 1 .. 64 rows, got {slots}")
@@ -310,7 +349,8 @@ class SlotServerState:
         if pipeline is None:
             from .lm.model import LMGen
             from .pipeline import StreamingPipeline
-            lm_gen = lm_gen if lm_gen is not None else LMGen(lm, **lm_gen_kwargs)
+            # --per-slot-sampling: every row samples by its own device-table entries, set from its client's query
+            lm_gen = lm_gen if lm_gen is not None else LMGen(lm, **dict(lm_gen_kwargs, **({"per_stream_sampling": True} if per_slot_sampling else {})))
             pipeline = StreamingPipeline(mimi, lm_gen, self.n, client_rate=None if self.client_rate == self.codec_rate else self.client_rate,
                                          per_stream=True)
             pipeline.__enter__()                                           # once: the session is the server's lifetime
@@ -322,6 +362,9 @@ class SlotServerState:
         self.fmt: List[int] = [SL.FMT_FREE] * self.n                       # host mirror of the pipeline's fmt vector
         self.inbox: List[Optional[object]] = [None] * self.n
         self._freed: List[int] = []                                        # rows left since the last tick (their fmt word goes to -1 there)
+        self.per_slot_sampling = bool(per_slot_sampling)
+        self._sampling: dict = {}                                          # joining slot -> its client's sampling settings (applied at the tick)
+        self._custom: set = set()                                          # rows whose tables hold a client's settings, not the server's defaults
         self._on_live: dict = {}                                           # slot -> asyncio.Event set when its reset has been applied
         self._outbox: dict = {}                                            # slot -> asyncio.Queue of (kind, payload)
         self._staged = self.pipe.new_staged()
@@ -335,15 +378,26 @@ class SlotServerState:
 
     # ---- driver API ----------------------------------------------------------------------------------------------------------------
 
-    def join(self, fmt: str) -> Optional[int]:
+    def sampling_caps(self):
+        """``(top_k, top_k_text)`` of the served ``LMGen``: the caps of a client's own values."""
+        d = self.pipe.lm_gen.default_sampling()
+        return max(int(d["top_k"]), 1), max(int(d["top_k_text"]), 1)
+
+    def join(self, fmt: str, sampling: Optional[dict] = None) -> Optional[int]:
         """Claims the lowest free row for a client whose transport is ``fmt`` (``"f32"`` / ``"s16"``); ``None`` when all are taken.  The
-        row starts its conversation at the next tick."""
+        row starts its conversation at the next tick.  ``sampling``: the client's own settings, ``set_stream_sampling`` keywords
+        (validated here, ``ValueError``; applied at that tick, over the server's defaults); ``None``: the server's defaults and a new seed."""
         SL = self.SL
         if fmt not in SL.FMT_CODES:
             raise ValueError(f"unknown pcm format {fmt!r}")
+        if sampling is not None:
+            from .lm.model import check_sampling
+            sampling = check_sampling(sampling, *self.sampling_caps())
         slot = self.table.acquire()
         if slot is None:
             return None
+        if sampling is not None:
+            self._sampling[slot] = sampling
         self.fmt[slot] = SL.FMT_CODES[fmt]
         self.inbox[slot] = SL.Inbox(self.F * SL.sample_width(self.fmt[slot]), self.max_backlog)
         return slot
@@ -357,6 +411,7 @@ class SlotServerState:
     def leave(self, slot: int) -> None:
         """Frees the row.  It goes on computing (on silence) without anything being returned; it is reset when it is next acquired."""
         self.table.release(slot)
+        self._sampling.pop(slot, None)
         self.fmt[slot] = self.SL.FMT_FREE
         self._freed.append(slot)
         self._on_live.pop(slot, None)
@@ -378,6 +433,7 @@ class SlotServerState:
         joined = self.table.rows(SL.JOINING)
         if joined:
             self.pipe.reset_streams(joined)                # ONE call for all of them: a reset's host cost does not grow with the row count
+            self._apply_sampling(joined)
             for b in joined:
                 self.pipe.set_row_format(b, self.fmt[b])
                 self.table.mark_live(b)
@@ -405,6 +461,23 @@ class SlotServerState:
             if ev is not None:
                 ev.set()
         return out
+
+    def _apply_sampling(self, joined: List[int]) -> None:
+        """The sampling settings of the rows that just joined, after their reset (which drew each a new seed): a client's own over the
+        server's defaults; the defaults again for a row whose previous client had its own.  One call for all of them (per-row value
+        lists: one table write per field, not per row) and one for the seeds that clients named.  Rows that never held a client's
+        settings are not touched -- a pipeline without ``set_stream_sampling`` serves any number of joins without ``sampling``."""
+        settings = {b: self._sampling.pop(b, None) for b in joined}
+        rows = [b for b in joined if settings[b] is not None or b in self._custom]
+        if not rows:
+            return
+        defaults = self.pipe.lm_gen.default_sampling()
+        full = [dict(defaults, **{k: v for k, v in (settings[b] or {}).items() if k != "seed"}) for b in rows]
+        self.pipe.set_stream_sampling(rows, **{k: [f[k] for f in full] for k in defaults})
+        seeded = [b for b in rows if settings[b] is not None and "seed" in settings[b]]
+        if seeded:
+            self.pipe.set_stream_sampling(seeded, seed=[settings[b]["seed"] for b in seeded])
+        self._custom = (self._custom - set(rows)) | {b for b in rows if settings[b] is not None}
 
     text_piece = ServerState.text_piece
 
@@ -467,9 +540,10 @@ class SlotServerState:
             framer = make_framer(self.F, kind, rate) if kind == "opus" else None
             if kind != "opus" and kind not in self.SL.FMT_CODES:
                 raise ValueError(f"unknown pcm format {kind!r}")
+            sampling = chat_sampling(request.query, self.per_slot_sampling, *(self.sampling_caps() if self.per_slot_sampling else (1, 1)))
         except (ValueError, RuntimeError) as e:
             raise web.HTTPBadRequest(text=str(e))
-        slot = self.join("f32" if framer is not None else kind)        # an Opus client's row runs as f32 behind its own host framer
+        slot = self.join("f32" if framer is not None else kind, sampling)        # an Opus client's row runs as f32 behind its own host framer
         if slot is None:
             raise web.HTTPServiceUnavailable(text=f"all {self.n} slots are taken; try again when a conversation has ended")
         live, outbox = asyncio.Event(), asyncio.Queue()
@@ -547,7 +621,8 @@ def make_state(mimi, lm, device, args, text_tokenizer=None):
     slots = getattr(args, "slots", None)
     if slots is None:
         return ServerState(mimi, lm, device, text_tokenizer=text_tokenizer)
-    return SlotServerState(mimi, lm, device, slots=slots, client_rate=getattr(args, "client_rate", None), text_tokenizer=text_tokenizer)
+    return SlotServerState(mimi, lm, device, slots=slots, client_rate=getattr(args, "client_rate", None), text_tokenizer=text_tokenizer,
+                           per_slot_sampling=bool(getattr(args, "per_slot_sampling", False)))
 
 
 def build_state(args, log_fn: Callable[[str, str], None] = log):
@@ -603,7 +678,12 @@ def main(argv=None) -> None:
                         "client beyond N is refused with 503.  Without it: one session at a time behind a lock, as the reference serves")
     p.add_argument("--client-rate", type=int, default=None,
                    help="with --slots: the one sample rate of every raw-PCM client (default: the codec's); another ?sr= is refused with 400")
+    p.add_argument("--per-slot-sampling", action="store_true",
+                   help="with --slots: every conversation samples by its own settings and noise stream, set by its client with "
+                        "?temp=&temp_text=&topk=&topk_text=&seed=&greedy=1 (top-k up to the server's values); without it those parameters are refused with 400")
     args = p.parse_args(argv)
+    if args.per_slot_sampling and args.slots is None:
+        p.error("--per-slot-sampling needs --slots")
     if args.slots is not None and not 1 <= args.slots <= 64:
         p.error("--slots takes 1 .. 64")
     if args.client_rate is not None and args.slots is None:
