@@ -1,7 +1,8 @@
 """rst_codec_transformer_frame (csrc/codec_tr.hip) at head dims other than Mimi's 64: the ring attention's thread -> (4 dims, slot
 class) layout, its lane-group sums and its 16-slot batches all depend on D (lane groups of D / 4 = 4 .. 64 lanes, 1024 / D slot
 classes, 16384 / D slots per batch).  Streamed past the ring wrap, several positions and streams per step, against the oracle's
-TransformerStream (modules/transformer.py:376-423,595-690)."""
+TransformerStream (modules/transformer.py:376-423,595-690).
+(Per-step, per-vector bounds against fp64 -- hand-offs, written rows, contexts, no rope, no LayerScale: tests/test_codec_frame_steps_gpu.py.)"""
 import pytest
 import torch
 
