@@ -26,72 +26,7 @@ __device__ unsigned long long ct_stamps[2][CT_STAMPS_PER_LAYER * RST_CTR_MAX_L +
 #define CT_STAMP(i) do {} while (0)
 #endif
 
-// ---- rows of an fp32 weight matrix: RU rows x CU chunks of 512 k (8 floats = two 16-byte loads per lane and chunk)
-template <int RU, int CU> struct CtPre { f32x4 wv[RU][CU][2]; };
-
-template <int RU, int CU>
-__device__ __forceinline__ void ct_rows_load(CtPre<RU, CU>& pre, const float* w, int N, int K, int r0, int kb, int W, int lane) {
-#pragma unroll
-    for (int j = 0; j < RU; ++j)
-#pragma unroll
-        for (int c = 0; c < CU; ++c) {
-            const int r = r0 + j * W, kk = kb + c * 512 + lane * 8;
-            pre.wv[j][c][0] = f32x4{0.f, 0.f, 0.f, 0.f};
-            pre.wv[j][c][1] = pre.wv[j][c][0];
-            if (r < N && kk < K) {
-                const float* q = w + (long)r * K + kk;
-                pre.wv[j][c][0] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q));
-                pre.wv[j][c][1] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q + 4));
-            }
-        }
-}
-
-template <int RU, int CU>
-__device__ __forceinline__ void ct_rows_issue(CtPre<RU, CU>& pre, const float* w, int N, int K, int gw, int W, int lane) {
-    ct_rows_load<RU, CU>(pre, w, N, K, gw, 0, W, lane);
-}
-
-// y[r][0..R) for rows r = gw, gw + W, ...; the first block (rows gw + j W, k < CU * 512) was requested by ct_rows_issue
-template <int R, int RU, int CU, typename Epi>
-__device__ __forceinline__ void ct_rows(CtPre<RU, CU>& pre, const float* w, int N, int K, const float* xs, int gw, int W, int lane, Epi epi) {
-    for (int r0 = gw; r0 < N; r0 += RU * W) {
-        float acc[RU][R];
-#pragma unroll
-        for (int j = 0; j < RU; ++j)
-#pragma unroll
-            for (int b = 0; b < R; ++b) acc[j][b] = 0.f;
-        for (int kb = 0; kb < K; kb += CU * 512) {
-            if (r0 != gw || kb != 0) ct_rows_load<RU, CU>(pre, w, N, K, r0, kb, W, lane);
-#pragma unroll
-            for (int c = 0; c < CU; ++c) {
-                const int kk = kb + c * 512 + lane * 8;
-                if (kk < K) {
-#pragma unroll
-                    for (int b = 0; b < R; ++b) {
-                        const f32x4 x0 = *reinterpret_cast<const f32x4*>(xs + b * K + kk);
-                        const f32x4 x1 = *reinterpret_cast<const f32x4*>(xs + b * K + kk + 4);
-#pragma unroll
-                        for (int j = 0; j < RU; ++j) {
-                            const f32x4 a0 = pre.wv[j][c][0], a1 = pre.wv[j][c][1];
-                            float a = acc[j][b];
-                            a = fmaf(a0[0], x0[0], a); a = fmaf(a0[1], x0[1], a); a = fmaf(a0[2], x0[2], a); a = fmaf(a0[3], x0[3], a);
-                            a = fmaf(a1[0], x1[0], a); a = fmaf(a1[1], x1[1], a); a = fmaf(a1[2], x1[2], a); a = fmaf(a1[3], x1[3], a);
-                            acc[j][b] = a;
-                        }
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < RU; ++j) {
-            const int r = r0 + j * W;
-            float s[R];
-#pragma unroll
-            for (int b = 0; b < R; ++b) s[b] = wave_sum_fast(acc[j][b]);
-            if (lane == 0 && r < N) epi(r, s);
-        }
-    }
-}
+// (the weight rows of every op: DfPre / df_rows_issue / df_rows of persist.h, fp32 weights, no row pairs)
 
 // nn.LayerNorm(E, eps) with affine gamma / beta over every row of x [R][E] -> xs (two-pass statistics, biased variance: the
 // arithmetic of gemv_kernel's prologue 3).  One WAVE per row (R <= 4 = the waves of a workgroup): no barrier inside a row, and
@@ -175,12 +110,12 @@ __global__ __launch_bounds__(DF_THREADS) void codec_tr_kernel(const CodecTrParam
     __shared__ unsigned long long ct_lds_stamps[CT_STAMPS_PER_LAYER * RST_CTR_MAX_L + 2];
     for (int i = tid; i < CT_STAMPS_PER_LAYER * RST_CTR_MAX_L + 2; i += DF_THREADS) ct_lds_stamps[i] = 0;     // (the barrier below orders it)
 #endif
-    CtPre<2, 1> pq;         // in-projection rows of this wave
-    CtPre<1, 1> po;         // out-projection
-    CtPre<2, 1> p1;         // linear1
-    CtPre<1, 4> p2;         // linear2
+    DfPre<true, 2, 1, false> pq;         // in-projection rows of this wave
+    DfPre<true, 1, 1, false> po;         // out-projection
+    DfPre<true, 2, 1, false> p1;         // linear1
+    DfPre<true, 1, 4, false> p2;         // linear2
     CtLn ln1, ln2;          // gamma / beta of the two LayerNorms of a layer
-    ct_rows_issue<2, 1>(pq, p.in_proj[0], 3 * E, E, gw, W, lane);
+    df_rows_issue(pq, p.in_proj[0], 3 * E, E, gw, W, lane);
     ct_ln_issue(ln1, p.n1g[0], p.n1b[0], E, lane);
     for (int i = tid; i < R * E; i += DF_THREADS) xres[i] = p.x[i];
     const long pos = *p.pos_dev;
@@ -197,12 +132,12 @@ __global__ __launch_bounds__(DF_THREADS) void codec_tr_kernel(const CodecTrParam
         ct_ln_issue(ln2, p.n2g[l], p.n2b[l], E, lane);
         CT_STAMP(sb + 0);
         ++eQKV;
-        ct_rows<R, 2, 1>(pq, p.in_proj[l], 3 * E, E, xs, gw, W, lane, [&](int r, float (&s)[R]) {
+        df_rows<R>(pq, p.in_proj[l], 3 * E, E, xs, gw, W, lane, [&](int r, float (&s)[1][R]) {
 #pragma unroll
-            for (int b = 0; b < R; ++b) df_publish(gQKV + (long)b * 3 * E + r, eQKV, s[b]);
+            for (int b = 0; b < R; ++b) df_publish(gQKV + (long)b * 3 * E + r, eQKV, s[0][b]);
         });
         CT_STAMP(sb + 1);
-        ct_rows_issue<1, 1>(po, p.out_proj[l], E, E, gw, W, lane);
+        df_rows_issue(po, p.out_proj[l], E, E, gw, W, lane);
         // ---- attention of (stream, head) = workgroup index
         ++eATT;
         for (int bh = wg; bh < p.B * H; bh += G) {
@@ -371,13 +306,13 @@ __global__ __launch_bounds__(DF_THREADS) void codec_tr_kernel(const CodecTrParam
         df_gather<4>(gATT, R * E, eATT, xs, [](int i) { return i; }, sh, p.status, 4u);
         CT_STAMP(sb + 5);
         ++eX;
-        ct_rows<R, 1, 1>(po, p.out_proj[l], E, E, xs, gw, W, lane, [&](int r, float (&s)[R]) {
+        df_rows<R>(po, p.out_proj[l], E, E, xs, gw, W, lane, [&](int r, float (&s)[1][R]) {
             const float sc1 = p.ls1[l] ? p.ls1[l][r] : 1.0f;
 #pragma unroll
-            for (int b = 0; b < R; ++b) df_publish(gX + (long)b * E + r, eX, xres[b * E + r] + sc1 * s[b]);
+            for (int b = 0; b < R; ++b) df_publish(gX + (long)b * E + r, eX, xres[b * E + r] + sc1 * s[0][b]);
         });
         CT_STAMP(sb + 6);
-        ct_rows_issue<2, 1>(p1, p.lin1[l], F, E, gw, W, lane);
+        df_rows_issue(p1, p.lin1[l], F, E, gw, W, lane);
         df_gather<4>(gX, R * E, eX, xres, [](int i) { return i; }, sh, p.status, 8u);
         CT_STAMP(sb + 7);
         // ---- FFN: x + scale2 * W2 gelu(W1 LN(x))
@@ -385,22 +320,22 @@ __global__ __launch_bounds__(DF_THREADS) void codec_tr_kernel(const CodecTrParam
         if (l + 1 < p.L) ct_ln_issue(ln1, p.n1g[l + 1], p.n1b[l + 1], E, lane);
         CT_STAMP(sb + 8);
         ++eH;
-        ct_rows<R, 2, 1>(p1, p.lin1[l], F, E, xs, gw, W, lane, [&](int r, float (&s)[R]) {
+        df_rows<R>(p1, p.lin1[l], F, E, xs, gw, W, lane, [&](int r, float (&s)[1][R]) {
 #pragma unroll
-            for (int b = 0; b < R; ++b) df_publish(gH + (long)b * F + r, eH, rst_gelu(s[b]));
+            for (int b = 0; b < R; ++b) df_publish(gH + (long)b * F + r, eH, rst_gelu(s[0][b]));
         });
         CT_STAMP(sb + 9);
-        ct_rows_issue<1, 4>(p2, p.lin2[l], E, F, gw, W, lane);
+        df_rows_issue(p2, p.lin2[l], E, F, gw, W, lane);
         df_gather<8>(gH, R * F, eH, xs, [](int i) { return i; }, sh, p.status, 16u);
         CT_STAMP(sb + 10);
         ++eX;
-        ct_rows<R, 1, 4>(p2, p.lin2[l], E, F, xs, gw, W, lane, [&](int r, float (&s)[R]) {
+        df_rows<R>(p2, p.lin2[l], E, F, xs, gw, W, lane, [&](int r, float (&s)[1][R]) {
             const float sc2 = p.ls2[l] ? p.ls2[l][r] : 1.0f;
 #pragma unroll
-            for (int b = 0; b < R; ++b) df_publish(gX + (long)b * E + r, eX, xres[b * E + r] + sc2 * s[b]);
+            for (int b = 0; b < R; ++b) df_publish(gX + (long)b * E + r, eX, xres[b * E + r] + sc2 * s[0][b]);
         });
         CT_STAMP(sb + 11);
-        if (l + 1 < p.L) ct_rows_issue<2, 1>(pq, p.in_proj[l + 1], 3 * E, E, gw, W, lane);
+        if (l + 1 < p.L) df_rows_issue(pq, p.in_proj[l + 1], 3 * E, E, gw, W, lane);
         df_gather<4>(gX, R * E, eX, xres, [](int i) { return i; }, sh, p.status, 32u);
         CT_STAMP(sb + 12);
     }

@@ -49,13 +49,7 @@ __global__ __launch_bounds__(256) void rope_append_kernel(const LmRopeAppendPara
 // KV16: the ring holds bf16 (the reference's cache precision: RingKVCache(..., dtype=torch.bfloat16), modules/transformer.py:228,
 // loaders.py:144) -- keys / values are rounded to nearest-even when appended, the new step's own key / value take part in its
 // attention at that precision too (the reference reads them back from the cache), and the long-context frame reads half the bytes.
-__device__ __forceinline__ unsigned short df_bf16_rne(float f) {
-    const unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);   // NaN stays NaN
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ float df_bf16_round(float f) { return __uint_as_float((unsigned)df_bf16_rne(f) << 16); }
-
+// (bf16_rne / bf16_round: lm_common.h)
 template <bool KV16> struct KvRow;
 template <> struct KvRow<false> {       // fp32 ring: 16 floats of a row
     static __device__ __forceinline__ void load(const void* base, long elem, float (&o)[16]) {
@@ -90,11 +84,11 @@ template <> struct KvRow<true> {        // bf16 ring: the same 16 elements in 32
         for (int i = 0; i < 2; ++i) {
             u32x4 t;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) t[e] = (unsigned)df_bf16_rne(v[8 * i + 2 * e]) | ((unsigned)df_bf16_rne(v[8 * i + 2 * e + 1]) << 16);
+            for (int e = 0; e < 4; ++e) t[e] = (unsigned)bf16_rne(v[8 * i + 2 * e]) | ((unsigned)bf16_rne(v[8 * i + 2 * e + 1]) << 16);
             *reinterpret_cast<u32x4*>(q + 8 * i) = t;
         }
     }
-    static __device__ __forceinline__ float round(float f) { return df_bf16_round(f); }
+    static __device__ __forceinline__ float round(float f) { return bf16_round(f); }
 };
 
 template <int D, bool KV16, int UNR>

@@ -10,17 +10,8 @@ namespace {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-// DPP forms (no LDS crossbar round trip per step: a __shfl_xor butterfly is 6 dependent ds_bpermute, ~0.3 us for a lone wave).
+// DPP forms of wave_sum / wave_max (rst_common.h; no LDS crossbar round trip per step: a __shfl_xor butterfly is 6 dependent
+// ds_bpermute, ~0.3 us for a lone wave).
 // row16_*: over the 16 lanes of a DPP row, result in every lane of the row; wave_*_fast: over the wave, result uniform.  Call with
 // all 64 lanes active.
 template <int CTRL>
@@ -67,6 +58,48 @@ __device__ __forceinline__ float group_sum(float v, int GS) {
 __device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 __device__ __forceinline__ float silu(float v) { return v / (1.0f + expf(-v)); }
+// fp32 -> bf16, round to nearest even, NaN stays NaN (the bf16 KV rings); bf16_round: the rounded value as fp32
+__device__ __forceinline__ unsigned short bf16_rne(float f) {
+    const unsigned u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);
+    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+__device__ __forceinline__ float bf16_round(float f) { return __uint_as_float((unsigned)bf16_rne(f) << 16); }
+
+// a + sum of 8 bf16 weights (16 bytes, k ascending) times x0 | x1: ONE fmaf chain in k order
+__device__ __forceinline__ float bf16_dot8(const u32x4& w, const f32x4& x0, const f32x4& x1, float a) {
+    a = fmaf(bf16_lo(w[0]), x0[0], a); a = fmaf(bf16_hi(w[0]), x0[1], a);
+    a = fmaf(bf16_lo(w[1]), x0[2], a); a = fmaf(bf16_hi(w[1]), x0[3], a);
+    a = fmaf(bf16_lo(w[2]), x1[0], a); a = fmaf(bf16_hi(w[2]), x1[1], a);
+    a = fmaf(bf16_lo(w[3]), x1[2], a); a = fmaf(bf16_hi(w[3]), x1[3], a);
+    return a;
+}
+
+// 8 consecutive k of one weight row: 16 bytes of bf16, or 32 bytes of fp32 (the codec's weights).  The weight chunk of gemv_kernel
+// (lm_step.hip) and of the persistent kernels' row worker (persist.h): zero / non-temporal load / 8 fmaf in k order.
+template <bool F32W> struct WChunk;
+template <> struct WChunk<false> {
+    u32x4 v;
+    __device__ __forceinline__ void zero() { v = u32x4{0u, 0u, 0u, 0u}; }
+    __device__ __forceinline__ void load(const void* w, long elem) {
+        v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(static_cast<const unsigned short*>(w) + elem));
+    }
+    __device__ __forceinline__ float dot(const f32x4& x0, const f32x4& x1, float a) const { return bf16_dot8(v, x0, x1, a); }
+};
+template <> struct WChunk<true> {
+    f32x4 a0, a1;
+    __device__ __forceinline__ void zero() { a0 = f32x4{0.f, 0.f, 0.f, 0.f}; a1 = a0; }
+    __device__ __forceinline__ void load(const void* w, long elem) {
+        const float* q = static_cast<const float*>(w) + elem;
+        a0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q));
+        a1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q + 4));
+    }
+    __device__ __forceinline__ float dot(const f32x4& x0, const f32x4& x1, float a) const {
+        a = fmaf(a0[0], x0[0], a); a = fmaf(a0[1], x0[1], a); a = fmaf(a0[2], x0[2], a); a = fmaf(a0[3], x0[3], a);
+        a = fmaf(a1[0], x1[0], a); a = fmaf(a1[1], x1[1], a); a = fmaf(a1[2], x1[2], a); a = fmaf(a1[3], x1[3], a);
+        return a;
+    }
+};
 
 // Ring slot -> position map of RingKVCache.complete (modules/transformer.py:254-278) incl. the `delta <= 0` quirk (Q1);
 // returns whether `slot` is visible to the query at position `pos` (= the step just appended).

@@ -77,85 +77,7 @@ __device__ __forceinline__ void df_rmsnorm(const float* x, const DfNorm& c, cons
     __syncthreads();
 }
 
-// Rows r = gw, gw + W, ... of w [N][K] (bf16) against xs [B][K] (LDS), in blocks of RU rows x CU chunks of 512 k whose loads are
-// all requested before the first is used.  PAIR: "row" q stands for the rows (q, N/2 + q) of a stacked gated layer.
-// The FIRST block (rows gw + j W, k < CU * 512 -- the whole op at the depth transformer's real shape) can be requested ahead of
-// time: df_rows_issue() before the hand-off that produces xs, df_rows() after it -- the weights do not depend on activations, so
-// their HBM latency hides behind the wait (the "prefetch-credit" of MI355X_MICROARCH.md's price list).  epi(row, sums) on lane 0.
-template <int RU, int CU, bool PAIR> struct DfPre { u32x4 wv[RU][PAIR ? 2 : 1][CU]; };
-
-template <int RU, int CU, bool PAIR>
-__device__ __forceinline__ void df_rows_load(DfPre<RU, CU, PAIR>& pre, const unsigned short* w, int rows, int K, int r0, int kb, int W, int lane) {
-    constexpr int HV = PAIR ? 2 : 1;
-#pragma unroll
-    for (int j = 0; j < RU; ++j)
-#pragma unroll
-        for (int h = 0; h < HV; ++h)
-#pragma unroll
-            for (int c = 0; c < CU; ++c) {
-                const int r = r0 + j * W, kk = kb + c * 512 + lane * 8;
-                pre.wv[j][h][c] = u32x4{0u, 0u, 0u, 0u};
-                if (r < rows && kk < K)
-                    pre.wv[j][h][c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(w + ((long)r + (long)h * rows) * K + kk));
-            }
-}
-
-template <int RU, int CU, bool PAIR>
-__device__ __forceinline__ void df_rows_issue(DfPre<RU, CU, PAIR>& pre, const unsigned short* w, int N, int K, int gw, int W, int lane) {
-    df_rows_load<RU, CU, PAIR>(pre, w, PAIR ? N / 2 : N, K, gw, 0, W, lane);
-}
-
-template <int B, int RU, int CU, bool PAIR, typename Epi>
-__device__ __forceinline__ void df_rows(DfPre<RU, CU, PAIR>& pre, const unsigned short* w, int N, int K, const float* xs, int gw, int W, int lane,
-                                        Epi epi) {
-    constexpr int HV = PAIR ? 2 : 1;
-    const int rows = PAIR ? N / 2 : N;
-    for (int r0 = gw; r0 < rows; r0 += RU * W) {
-        float acc[RU][HV][B];
-#pragma unroll
-        for (int j = 0; j < RU; ++j)
-#pragma unroll
-            for (int h = 0; h < HV; ++h)
-#pragma unroll
-                for (int b = 0; b < B; ++b) acc[j][h][b] = 0.f;
-        for (int kb = 0; kb < K; kb += CU * 512) {
-            if (r0 != gw || kb != 0) df_rows_load<RU, CU, PAIR>(pre, w, rows, K, r0, kb, W, lane);     // the first block was issued ahead
-#pragma unroll
-            for (int c = 0; c < CU; ++c) {
-                const int kk = kb + c * 512 + lane * 8;
-                if (kk < K) {
-#pragma unroll
-                    for (int b = 0; b < B; ++b) {
-                        const f32x4 x0 = *reinterpret_cast<const f32x4*>(xs + b * K + kk);
-                        const f32x4 x1 = *reinterpret_cast<const f32x4*>(xs + b * K + kk + 4);
-#pragma unroll
-                        for (int j = 0; j < RU; ++j)
-#pragma unroll
-                            for (int h = 0; h < HV; ++h) {
-                                const u32x4 v = pre.wv[j][h][c];
-                                float a = acc[j][h][b];
-                                a = fmaf(bf16_lo(v[0]), x0[0], a); a = fmaf(bf16_hi(v[0]), x0[1], a);
-                                a = fmaf(bf16_lo(v[1]), x0[2], a); a = fmaf(bf16_hi(v[1]), x0[3], a);
-                                a = fmaf(bf16_lo(v[2]), x1[0], a); a = fmaf(bf16_hi(v[2]), x1[1], a);
-                                a = fmaf(bf16_lo(v[3]), x1[2], a); a = fmaf(bf16_hi(v[3]), x1[3], a);
-                                acc[j][h][b] = a;
-                            }
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < RU; ++j) {
-            const int r = r0 + j * W;
-            float s[HV][B];
-#pragma unroll
-            for (int h = 0; h < HV; ++h)
-#pragma unroll
-                for (int b = 0; b < B; ++b) s[h][b] = wave_sum_fast(acc[j][h][b]);
-            if (lane == 0 && r < rows) epi(r, s);
-        }
-    }
-}
+// (the weight rows of every op: DfPre / df_rows_issue / df_rows of persist.h, bf16 weights)
 
 // The KV history of the frame's earlier steps: LDS of the head's owner; in the SOLO (repair) launch one workgroup owns every head and
 // the history of all of them lives in a global scratch, read and written with agent-scope (L1-bypassing) accesses.
@@ -205,13 +127,13 @@ __global__ __launch_bounds__(DF_THREADS) void depth_frame_kernel(const DepthFram
     unsigned eX = 0, eQKV = 0, eATT = 0, eH = 0, eLOG = 0, eTOK = 0;      // epochs (number of completed writes) per buffer
     const float att_div = sqrtf((float)D);
 
-    DfPre<3, 2, false> pq;      // in-projection rows of this wave (requested one hand-off ahead)
-    DfPre<1, 2, false> po;      // out-projection
-    DfPre<3, 2, true> pi;       // gated FFN in (u, v row pairs)
-    DfPre<1, 6, false> pf;      // gated FFN out
-    DfPre<2, 2, false> ph;      // head
+    DfPre<false, 3, 2, false> pq;      // in-projection rows of this wave (requested one hand-off ahead)
+    DfPre<false, 1, 2, false> po;      // out-projection
+    DfPre<false, 3, 2, true> pi;       // gated FFN in (u, v row pairs)
+    DfPre<false, 1, 6, false> pf;      // gated FFN out
+    DfPre<false, 2, 2, false> ph;      // head
     DfNorm n1, n2;              // alpha of the two norms of a layer
-    df_rows_issue<3, 2, false>(pq, p.in_proj[0], 3 * E, E, gw, W, lane);
+    df_rows_issue(pq, p.in_proj[0], 3 * E, E, gw, W, lane);
     for (int k = 0; k < dep_q; ++k) {
         df_norm_issue(n1, p.norm1[0], E);
         // ---- input of the step: x = depformer_in[k](h) + emb_k[previous token]   (models/model.py:411-417)
@@ -249,12 +171,12 @@ __global__ __launch_bounds__(DF_THREADS) void depth_frame_kernel(const DepthFram
             df_norm_issue(n2, p.norm2[l], E);
             DF_STAMP(sl + 0);
             ++eQKV;
-            df_rows<B, 3, 2, false>(pq, p.in_proj[l] + (long)k * 3 * E * E, 3 * E, E, xs, gw, W, lane, [&](int r, float (&s)[1][B]) {
+            df_rows<B>(pq, p.in_proj[l] + (long)k * 3 * E * E, 3 * E, E, xs, gw, W, lane, [&](int r, float (&s)[1][B]) {
 #pragma unroll
                 for (int b = 0; b < B; ++b) df_publish(gQKV + (long)b * 3 * E + r, eQKV, s[0][b]);
             });
             DF_STAMP(sl + 1);
-            df_rows_issue<1, 2, false>(po, p.out_proj[l] + (long)k * E * E, E, E, gw, W, lane);
+            df_rows_issue(po, p.out_proj[l] + (long)k * E * E, E, E, gw, W, lane);
             // ---- attention of head `wg` (modules/transformer.py:376-416 on a ring of ring_cap slots, no rope)
             ++eATT;
             for (int h = wg; h < p.H; h += G) {
@@ -305,12 +227,12 @@ __global__ __launch_bounds__(DF_THREADS) void depth_frame_kernel(const DepthFram
             df_gather<4>(gATT, B * E, eATT, xs, [](int i) { return i; }, sh, p.status, 4u);
             DF_STAMP(sl + 5);
             ++eX;
-            df_rows<B, 1, 2, false>(po, p.out_proj[l] + (long)k * E * E, E, E, xs, gw, W, lane, [&](int r, float (&s)[1][B]) {
+            df_rows<B>(po, p.out_proj[l] + (long)k * E * E, E, E, xs, gw, W, lane, [&](int r, float (&s)[1][B]) {
 #pragma unroll
                 for (int b = 0; b < B; ++b) df_publish(gX + (long)b * E + r, eX, xres[b * E + r] + s[0][b]);
             });
             DF_STAMP(sl + 6);
-            df_rows_issue<3, 2, true>(pi, p.gate_in[l][k], 2 * Hd, E, gw, W, lane);
+            df_rows_issue(pi, p.gate_in[l][k], 2 * Hd, E, gw, W, lane);
             df_gather<4>(gX, B * E, eX, xres, [](int i) { return i; }, sh, p.status, 8u);
             DF_STAMP(sl + 7);
             // ---- gated FFN: x + W_out (silu(u) * v), [u ; v] = W_in rmsnorm(x)   (modules/gating.py:12-51)
@@ -318,36 +240,36 @@ __global__ __launch_bounds__(DF_THREADS) void depth_frame_kernel(const DepthFram
             if (l + 1 < p.L) df_norm_issue(n1, p.norm1[l + 1], E);
             DF_STAMP(sl + 8);
             ++eH;
-            df_rows<B, 3, 2, true>(pi, p.gate_in[l][k], 2 * Hd, E, xs, gw, W, lane, [&](int q, float (&s)[2][B]) {
+            df_rows<B>(pi, p.gate_in[l][k], 2 * Hd, E, xs, gw, W, lane, [&](int q, float (&s)[2][B]) {
 #pragma unroll
                 for (int b = 0; b < B; ++b) df_publish(gH + (long)b * Hd + q, eH, silu(s[0][b]) * s[1][b]);
             });
             DF_STAMP(sl + 9);
-            df_rows_issue<1, 6, false>(pf, p.gate_out[l][k], E, Hd, gw, W, lane);
+            df_rows_issue(pf, p.gate_out[l][k], E, Hd, gw, W, lane);
             df_gather<6>(gH, B * Hd, eH, xs, [](int i) { return i; }, sh, p.status, 16u);
             DF_STAMP(sl + 10);
             ++eX;
-            df_rows<B, 1, 6, false>(pf, p.gate_out[l][k], E, Hd, xs, gw, W, lane, [&](int r, float (&s)[1][B]) {
+            df_rows<B>(pf, p.gate_out[l][k], E, Hd, xs, gw, W, lane, [&](int r, float (&s)[1][B]) {
 #pragma unroll
                 for (int b = 0; b < B; ++b) df_publish(gX + (long)b * E + r, eX, xres[b * E + r] + s[0][b]);
             });
             DF_STAMP(sl + 11);
             // the next consumer of x: the next layer's in-projection, or the head of this step
-            if (l + 1 < p.L) df_rows_issue<3, 2, false>(pq, p.in_proj[l + 1] + (long)k * 3 * E * E, 3 * E, E, gw, W, lane);
-            else df_rows_issue<2, 2, false>(ph, p.heads[k], card, E, gw, W, lane);
+            if (l + 1 < p.L) df_rows_issue(pq, p.in_proj[l + 1] + (long)k * 3 * E * E, 3 * E, E, gw, W, lane);
+            else df_rows_issue(ph, p.heads[k], card, E, gw, W, lane);
             df_gather<4>(gX, B * E, eX, xres, [](int i) { return i; }, sh, p.status, 32u);
             DF_STAMP(sl + 12);
         }
 
         // ---- head: logits = linears[k](x)   (models/model.py:425-427; no norm in front)
         ++eLOG;
-        df_rows<B, 2, 2, false>(ph, p.heads[k], card, E, xres, gw, W, lane, [&](int r, float (&s)[1][B]) {
+        df_rows<B>(ph, p.heads[k], card, E, xres, gw, W, lane, [&](int r, float (&s)[1][B]) {
             const float bias = p.head_bias[k] ? p.head_bias[k][r] : 0.f;
 #pragma unroll
             for (int b = 0; b < B; ++b) df_publish(gLOG + (long)b * card + r, eLOG, s[0][b] + bias);
         });
         DF_STAMP(sk + 1 + DF_ST_LAYER * RST_DEPTH_MAX_L);
-        if (k + 1 < dep_q) df_rows_issue<3, 2, false>(pq, p.in_proj[0] + (long)(k + 1) * 3 * E * E, 3 * E, E, gw, W, lane);
+        if (k + 1 < dep_q) df_rows_issue(pq, p.in_proj[0] + (long)(k + 1) * 3 * E * E, 3 * E, E, gw, W, lane);
         // ---- sampler: utils/sampling.py:85-105.  Workgroup b draws the token of batch row b (round 5: with the rows one after the other
         // in workgroup 0 the second row's 14 us sat on every step's critical path at batch 2); the one-workgroup repair launch takes all rows
         ++eTOK;

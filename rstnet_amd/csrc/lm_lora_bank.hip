@@ -24,14 +24,7 @@ constexpr int LB_RPW = 2;                      // adapter rows per wave
 constexpr int LB_SLAB = LB_WAVES * LB_RPW;     // adapter rows per workgroup (r % 16 == 0: slabs are always full)
 constexpr int LB_THREADS = 64 * LB_WAVES;
 
-__device__ __forceinline__ float dot8(const u32x4& w, const f32x4& x0, const f32x4& x1, float a) {
-    a = fmaf(bf16_lo(w[0]), x0[0], a); a = fmaf(bf16_hi(w[0]), x0[1], a);
-    a = fmaf(bf16_lo(w[1]), x0[2], a); a = fmaf(bf16_hi(w[1]), x0[3], a);
-    a = fmaf(bf16_lo(w[2]), x1[0], a); a = fmaf(bf16_hi(w[2]), x1[1], a);
-    a = fmaf(bf16_lo(w[3]), x1[2], a); a = fmaf(bf16_hi(w[3]), x1[3], a);
-    return a;
-}
-
+// (the fmaf chain of 8 k: bf16_dot8, lm_common.h)
 __device__ __forceinline__ u32x4 load8(const unsigned short* w) { return *reinterpret_cast<const u32x4*>(w); }
 
 __global__ __launch_bounds__(LB_THREADS) void lora_bank_shrink_kernel(const LoraBankShrinkParams p) {
@@ -78,8 +71,8 @@ __global__ __launch_bounds__(LB_THREADS) void lora_bank_shrink_kernel(const Lora
     auto fma8 = [&](const u32x4& a0, const u32x4& a1, int at) {
         const f32x4 x0 = *reinterpret_cast<const f32x4*>(xs + at);
         const f32x4 x1 = *reinterpret_cast<const f32x4*>(xs + at + 4);
-        acc0 = dot8(a0, x0, x1, acc0);
-        acc1 = dot8(a1, x0, x1, acc1);
+        acc0 = bf16_dot8(a0, x0, x1, acc0);
+        acc1 = bf16_dot8(a1, x0, x1, acc1);
     };
     if (k < K) {
         fma8(pre0, pre1, k);
@@ -118,8 +111,8 @@ __global__ __launch_bounds__(LB_THREADS) void lora_bank_expand_kernel(const Lora
         const u32x4 b0 = load8(w + j), b1 = load8(w + j + 8);
         const f32x4 a0 = *reinterpret_cast<const f32x4*>(as + j), a1 = *reinterpret_cast<const f32x4*>(as + j + 4);
         const f32x4 a2 = *reinterpret_cast<const f32x4*>(as + j + 8), a3 = *reinterpret_cast<const f32x4*>(as + j + 12);
-        acc = dot8(b0, a0, a1, acc);
-        acc = dot8(b1, a2, a3, acc);
+        acc = bf16_dot8(b0, a0, a1, acc);
+        acc = bf16_dot8(b1, a2, a3, acc);
     }
     float* y = p.y + row * p.ldy + n;
     *y = *y + acc;

@@ -23,12 +23,6 @@ namespace {
 typedef short pf_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float pf_f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ unsigned short pf_bf16_rne(float f) {
-    const unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);   // NaN stays NaN
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 template <bool KV16> struct PfKv;
 template <> struct PfKv<false> {
     typedef float elem;
@@ -39,7 +33,7 @@ template <> struct PfKv<false> {
 template <> struct PfKv<true> {
     typedef unsigned short elem;
     static __device__ __forceinline__ void store2(void* base, long at, float a, float b) {
-        *reinterpret_cast<unsigned*>(static_cast<unsigned short*>(base) + at) = (unsigned)pf_bf16_rne(a) | ((unsigned)pf_bf16_rne(b) << 16);
+        *reinterpret_cast<unsigned*>(static_cast<unsigned short*>(base) + at) = (unsigned)bf16_rne(a) | ((unsigned)bf16_rne(b) << 16);
     }
 };
 

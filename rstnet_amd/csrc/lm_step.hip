@@ -13,37 +13,7 @@ namespace {
 
 constexpr int GEMV_WAVES = 4;
 
-// 8 consecutive k of one weight row: 16 bytes of bf16, or 32 bytes of fp32 (the codec's weights)
-template <bool F32W> struct WChunk;
-template <> struct WChunk<false> {
-    u32x4 v;
-    __device__ __forceinline__ void zero() { v = u32x4{0u, 0u, 0u, 0u}; }
-    __device__ __forceinline__ void load(const void* w, long elem) {
-        v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(static_cast<const unsigned short*>(w) + elem));
-    }
-    __device__ __forceinline__ float dot(const f32x4& x0, const f32x4& x1, float a) const {
-        a = fmaf(bf16_lo(v[0]), x0[0], a); a = fmaf(bf16_hi(v[0]), x0[1], a);
-        a = fmaf(bf16_lo(v[1]), x0[2], a); a = fmaf(bf16_hi(v[1]), x0[3], a);
-        a = fmaf(bf16_lo(v[2]), x1[0], a); a = fmaf(bf16_hi(v[2]), x1[1], a);
-        a = fmaf(bf16_lo(v[3]), x1[2], a); a = fmaf(bf16_hi(v[3]), x1[3], a);
-        return a;
-    }
-};
-template <> struct WChunk<true> {
-    f32x4 a0, a1;
-    __device__ __forceinline__ void zero() { a0 = f32x4{0.f, 0.f, 0.f, 0.f}; a1 = a0; }
-    __device__ __forceinline__ void load(const void* w, long elem) {
-        const float* q = static_cast<const float*>(w) + elem;
-        a0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q));
-        a1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q + 4));
-    }
-    __device__ __forceinline__ float dot(const f32x4& x0, const f32x4& x1, float a) const {
-        a = fmaf(a0[0], x0[0], a); a = fmaf(a0[1], x0[1], a); a = fmaf(a0[2], x0[2], a); a = fmaf(a0[3], x0[3], a);
-        a = fmaf(a1[0], x1[0], a); a = fmaf(a1[1], x1[1], a); a = fmaf(a1[2], x1[2], a); a = fmaf(a1[3], x1[3], a);
-        return a;
-    }
-};
-
+// (the 8-k weight chunk WChunk<F32W>: lm_common.h)
 // y[b][n] = (res ? res[b][n] : 0) + (scale ? scale[n] : 1) * act(bias[n] + sum_k xs[b][k] * W[n][k]),   xs = prologue(x)
 // FUSED instances (B <= 2, bf16) also carry prologue 4 (short-ring attention) and 5 (embedding + RMSNorm); they are kept apart
 // so that their register footprint (the K / V rows of 8 ring slots) does not cost the plain instances their occupancy.

@@ -131,12 +131,6 @@ template <bool KV16, int D> struct TfKv {
     }
 };
 
-__device__ __forceinline__ unsigned short tf_bf16_rne(float f) {
-    const unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 __device__ __forceinline__ void tf_barrier() { __syncthreads(); }
 
 // NG granules per comm thread: i = first + 256 j + tc (i < n), swept (all requested before any is looked at) until every tag == epoch
@@ -712,7 +706,7 @@ __global__ __launch_bounds__(TF_THREADS) void temporal_frame_kernel(const Tempor
                         }
                         if (part > 0) {
                             if (KV16) {
-                                const unsigned short ha = tf_bf16_rne(a), hc = tf_bf16_rne(c);
+                                const unsigned short ha = bf16_rne(a), hc = bf16_rne(c);
                                 a = __uint_as_float((unsigned)ha << 16); c = __uint_as_float((unsigned)hc << 16);
                                 if (split == 0) {
                                     unsigned short* ring = reinterpret_cast<unsigned short*>(const_cast<char*>(tptr(part == 1 ? 6 : 7, l)));

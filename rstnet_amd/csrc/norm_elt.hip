@@ -5,13 +5,8 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// one wave per row; two passes over the row (second one hits L1/L2), fp32 statistics like ATen's CPU LayerNorm
+// one wave per row; two passes over the row (second one hits L1/L2), fp32 statistics like ATen's CPU LayerNorm; the wave's sums in
+// the butterfly order of wave_sum (rst_common.h)
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float* __restrict__ y,
                                                         long rows, int D, float eps) {

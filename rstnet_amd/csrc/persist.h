@@ -16,6 +16,8 @@
 // outputs therefore never leave the stream; the host reads status[1] now and then and retires the persistent path for a device
 // that keeps failing (a repaired frame costs the time-outs plus ~30 ms).
 #pragma once
+#include <type_traits>
+
 #include "lm_common.h"
 
 namespace {
@@ -77,6 +79,82 @@ __device__ __forceinline__ void df_gather(const u64* g, int n, unsigned epoch, f
         }
     }
     __syncthreads();
+}
+
+// The weight-row worker of lm_depth.hip (bf16 weights, F32W = false) and codec_tr.hip (fp32 weights, F32W = true):
+// rows r = gw, gw + W, ... of w [N][K] against xs [B][K] (LDS), in blocks of RU rows x CU chunks of 512 k whose loads are
+// all requested before the first is used.  PAIR: "row" q stands for the rows (q, N/2 + q) of a stacked gated layer.
+// The FIRST block (rows gw + j W, k < CU * 512 -- the whole op at the depth transformer's real shape) can be requested ahead of
+// time: df_rows_issue() before the hand-off that produces xs, df_rows() after it -- the weights do not depend on activations, so
+// their HBM latency hides behind the wait (the "prefetch-credit" of MI355X_MICROARCH.md's price list).  epi(row, sums) on lane 0.
+// k order: ONE fmaf chain per (row, batch row) and lane, gemv_kernel's (lm_step.hip) -- the lane's 8 k of every 512-wide chunk,
+// chunks ascending, through the same WChunk::dot; the 64 lanes then meet in wave_sum_fast (DPP steps where gemv_kernel has the
+// wave_sum butterfly: the one difference in arithmetic, the order of the additions across lanes).
+template <bool F32W, int RU, int CU, bool PAIR> struct DfPre { WChunk<F32W> wv[RU][PAIR ? 2 : 1][CU]; };
+template <bool F32W> using df_weight_t = std::conditional_t<F32W, float, unsigned short>;
+
+template <bool F32W, int RU, int CU, bool PAIR>
+__device__ __forceinline__ void df_rows_load(DfPre<F32W, RU, CU, PAIR>& pre, const df_weight_t<F32W>* w, int rows, int K, int r0, int kb, int W, int lane) {
+    constexpr int HV = PAIR ? 2 : 1;
+#pragma unroll
+    for (int j = 0; j < RU; ++j)
+#pragma unroll
+        for (int h = 0; h < HV; ++h)
+#pragma unroll
+            for (int c = 0; c < CU; ++c) {
+                const int r = r0 + j * W, kk = kb + c * 512 + lane * 8;
+                pre.wv[j][h][c].zero();
+                if (r < rows && kk < K) pre.wv[j][h][c].load(w, ((long)r + (long)h * rows) * K + kk);
+            }
+}
+
+template <bool F32W, int RU, int CU, bool PAIR>
+__device__ __forceinline__ void df_rows_issue(DfPre<F32W, RU, CU, PAIR>& pre, const df_weight_t<F32W>* w, int N, int K, int gw, int W, int lane) {
+    df_rows_load(pre, w, PAIR ? N / 2 : N, K, gw, 0, W, lane);
+}
+
+template <int B, bool F32W, int RU, int CU, bool PAIR, typename Epi>
+__device__ __forceinline__ void df_rows(DfPre<F32W, RU, CU, PAIR>& pre, const df_weight_t<F32W>* w, int N, int K, const float* xs, int gw, int W, int lane,
+                                        Epi epi) {
+    constexpr int HV = PAIR ? 2 : 1;
+    const int rows = PAIR ? N / 2 : N;
+    for (int r0 = gw; r0 < rows; r0 += RU * W) {
+        float acc[RU][HV][B];
+#pragma unroll
+        for (int j = 0; j < RU; ++j)
+#pragma unroll
+            for (int h = 0; h < HV; ++h)
+#pragma unroll
+                for (int b = 0; b < B; ++b) acc[j][h][b] = 0.f;
+        for (int kb = 0; kb < K; kb += CU * 512) {
+            if (r0 != gw || kb != 0) df_rows_load(pre, w, rows, K, r0, kb, W, lane);     // the first block was issued ahead
+#pragma unroll
+            for (int c = 0; c < CU; ++c) {
+                const int kk = kb + c * 512 + lane * 8;
+                if (kk < K) {
+#pragma unroll
+                    for (int b = 0; b < B; ++b) {
+                        const f32x4 x0 = *reinterpret_cast<const f32x4*>(xs + b * K + kk);
+                        const f32x4 x1 = *reinterpret_cast<const f32x4*>(xs + b * K + kk + 4);
+#pragma unroll
+                        for (int j = 0; j < RU; ++j)
+#pragma unroll
+                            for (int h = 0; h < HV; ++h) acc[j][h][b] = pre.wv[j][h][c].dot(x0, x1, acc[j][h][b]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < RU; ++j) {
+            const int r = r0 + j * W;
+            float s[HV][B];
+#pragma unroll
+            for (int h = 0; h < HV; ++h)
+#pragma unroll
+                for (int b = 0; b < B; ++b) s[h][b] = wave_sum_fast(acc[j][h][b]);
+            if (lane == 0 && r < rows) epi(r, s);
+        }
+    }
 }
 
 // End of a SOLO (repair) launch: the frame was recomputed by this one workgroup.

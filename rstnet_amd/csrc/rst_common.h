@@ -102,6 +102,19 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define RST_WAVE 64
 
+// Sum / maximum over the 64 lanes of a wave, result in every lane: the xor butterfly (partners 32, 16, .. 1 lanes away).  THE butterfly
+// order of the library: the LayerNorm statistics (norm_elt.hip, skinny_f32.hip) and the launch-per-op GEMVs (lm_step.hip) reduce with it.
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+
 __device__ __forceinline__ float rst_elu(float v) {
     // ELU, alpha = 1: x > 0 ? x : e^x - 1.  e^x as one v_exp_f32 of the fp32 product x * log2(e): for x <= 0 the product's rounding
     // moves e^x by <= |x| * 2^-24, so e^x - 1 stays within 7e-8 absolute of the exact value -- the same bound as a correctly rounded

@@ -33,15 +33,10 @@ __global__ __launch_bounds__(256) void f32_pack_weight_kernel(const float* __res
 // rows of the packed activation buffer: the kernel is instantiated for 1, 2 or 4 row tiles
 __host__ __device__ inline int sf_rows(int M) { return M <= 32 ? 32 : (M <= 64 ? 64 : 128); }
 
-__device__ __forceinline__ float sf_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // nn.LayerNorm statistics of one row by one wave -- `layernorm_kernel`'s arithmetic (fp32: the lane's sum in column order, the wave's
-// sum in butterfly order, variance of the centred values with fmaf) -- and its application to one element.  Shared by the packing launch
-// below and by the GEMM's row-major operand path, so that both give the bits of LayerNorm followed by the pack.
+// sum in the butterfly order of wave_sum (rst_common.h), variance of the centred values with fmaf) -- and its application to one
+// element.  Shared by the packing launch below and by the GEMM's row-major operand path, so that both give the bits of LayerNorm
+// followed by the pack.
 __device__ __forceinline__ float sf_ln_apply(float v, float mean, float rstd, float g, float b) { return (v - mean) * rstd * g + b; }
 
 __device__ __forceinline__ void sf_row_stats(const float* xr, int K, int lane, float eps, float& mean, float& rstd) {
@@ -50,14 +45,14 @@ __device__ __forceinline__ void sf_row_stats(const float* xr, int K, int lane, f
         const f32x4 v = *reinterpret_cast<const f32x4*>(xr + i);
         s += (v[0] + v[1]) + (v[2] + v[3]);
     }
-    mean = sf_wave_sum(s) / (float)K;
+    mean = wave_sum(s) / (float)K;
     float q = 0.f;
     for (int i = lane * 4; i < K; i += 256) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(xr + i);
 #pragma unroll
         for (int e = 0; e < 4; ++e) { const float d = v[e] - mean; q = fmaf(d, d, q); }
     }
-    rstd = 1.0f / sqrtf(sf_wave_sum(q) / (float)K + eps);
+    rstd = 1.0f / sqrtf(wave_sum(q) / (float)K + eps);
 }
 
 // LayerNorm + pack in ONE launch (round 5): the plain-linear case of the packing below (no window, K = C) with the row's LayerNorm
@@ -92,7 +87,7 @@ __global__ __launch_bounds__(256) void f32_pack_ln_kernel(const float* __restric
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (lane * 4 + 256 * j < K) s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
-        const float mean = sf_wave_sum(s) / (float)K;
+        const float mean = wave_sum(s) / (float)K;
         float q = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -100,7 +95,7 @@ __global__ __launch_bounds__(256) void f32_pack_ln_kernel(const float* __restric
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { const float d = v[j][e] - mean; q = fmaf(d, d, q); }
             }
-        const float rstd = 1.0f / sqrtf(sf_wave_sum(q) / (float)K + eps);
+        const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)K + eps);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int i = lane * 4 + 256 * j;

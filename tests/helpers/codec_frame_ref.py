@@ -178,7 +178,7 @@ def lds_bytes(case, T):
 
 
 def row_rounds(N, K, RU, CU, W):
-    """One `ct_rows<R, RU, CU>` instance over an [N, K] matrix: (row rounds of the wave that owns row 0, k blocks per round)."""
+    """One `df_rows<R>` instance (persist.h, `DfPre<true, RU, CU, false>`) over an [N, K] matrix: (row rounds of the wave that owns row 0, k blocks per round)."""
     return -(-N // (RU * W)), -(-K // (CU * K_CHUNK))
 
 

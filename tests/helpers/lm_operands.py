@@ -4,7 +4,7 @@
   (fp8_packed_index), as index formulas and as the reshapes that decode a whole buffer;
 - split_hi_lo: bit-exact emulation of split_hi_lo8 (hi = the fp32 value truncated to bf16, lo = the residual x - hi rounded
   half-up, i.e. half away from zero in magnitude, by adding 0x8000 to its bits);
-- bf16_rne: fp32 -> bf16 round to nearest even, NaN kept NaN (the ring appends, df_bf16_rne / tf_bf16_rne).
+- bf16_rne: fp32 -> bf16 round to nearest even, NaN kept NaN (the ring appends, bf16_rne of lm_common.h).
 
 All bit patterns are numpy uint16 / uint32 arrays; nothing here needs a GPU."""
 import numpy as np
